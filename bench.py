@@ -19,9 +19,18 @@ N > 1  configs[3]: the archiver's `-p8` split of the same file (csarc.cpp:532-54
        touched the GPU, and relays rank 0's JSON line.
 
 One JSON line on rank 0: the contract fields + `roofline` (dominant kernel k_encode_runs* against the 8 TB/s HBM peak,
-algorithmic bytes per SURVEY.md section 8d) + `cpu_baseline` (the reference built as oracle/_ref -- or the oracle port --
-timed on this box's host cores over a bounded sample: one thread for the single stream, the reference's eight worker processes for
-the task splits (rank 0's host, after the timed region, at every N), the reference archiver `csarc_ref -t8` for `--workload tree`).
+algorithmic bytes per SURVEY.md section 8d).  A plain run does only that: set up, warm up, time the K steps, print the line.
+
+--full  adds every other leg (each off in a plain run): `cpu_baseline` (the reference built as oracle/_ref -- or the oracle
+        port -- timed on this box's host cores over a bounded sample: one thread for the single stream, the reference's eight
+        worker processes for the task splits (rank 0's host, after the timed region, at every N), the reference archiver
+        `csarc_ref -t8` for `--workload tree`), the comparisons with the reference's committed digests (tests/golden/), the
+        steady-state window, `p8_on_one_gpu`, `other_configs`, `multi_stream` and, at N > 1, the hand-over of the streams to
+        rank 0.  --steady-steps / --p8-steps / --other-steps / --multi-streams given explicitly hold in either mode.
+--dump-outputs DIR  after the timed steps, what the timed path handed its caller in its last step, as DIR/<name>.npy
+        (float32 byte values 0..255, float64 lengths; an output longer than DUMP_MAX_BYTES is written as a fixed, evenly
+        spaced sample of it): the encoded stream so far, the bytes the last timed step appended, their lengths.  The inputs
+        are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -61,6 +70,33 @@ def parse_size(s):
     elif s.endswith("m"):
         mul, s = 1 << 20, s[:-1]
     return int(s) * mul
+
+
+DUMP_MAX_BYTES = 4 << 20            # --dump-outputs: at most this many values an array (float32: 16 MiB; three arrays a run)
+
+
+def byte_array(buf):
+    """bytes -> float32 array of the byte values (exact), or a fixed, evenly spaced sample of DUMP_MAX_BYTES of them"""
+    import numpy as np
+    a = buf if isinstance(buf, np.ndarray) else np.frombuffer(bytes(buf), dtype=np.uint8)
+    if a.size > DUMP_MAX_BYTES:
+        a = a[(np.arange(DUMP_MAX_BYTES, dtype=np.int64) * a.size) // DUMP_MAX_BYTES]
+    return np.asarray(a, dtype=np.float32)
+
+
+def write_dump(d, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(d, f"{name}.npy"), a)
+
+
+def check_steps(nsteps, longest, chunk):
+    """every warm-up and timed step must encode a chunk: --steps is the number of steps timed, not an upper bound"""
+    have = (longest + chunk - 1) // chunk
+    if nsteps > have:
+        raise SystemExit(f"bench.py: --warmup + --steps = {nsteps} chunks, but the input has only {have} of {chunk} bytes")
 
 
 def alg_bytes(level, ratio, stats=None):
@@ -386,12 +422,14 @@ def roofline(level, ratio, launches, kern_ms, in_b, kernel, note, traffic=(None,
 def run_single(args, R, lib, src, level, dict_size):
     """N = 1: one libcsc stream (BASELINE configs[1] by default)"""
     torch = R.torch
+    import numpy as np
     from csc_amd.capi import BytesWriter
     L = lib.lib
     task_size = src.size
     props = lib.props_init(min(dict_size, task_size), level)          # csa_worker.cpp:35
     chunk = int(props.raw_blocksize)
     nsteps = args.warmup + args.steps
+    check_steps(nsteps, task_size, chunk)
     if args.config != "enwik9":
         args.steady_steps = 0        # (a 256 MiB / 1 GiB window takes minutes to fill at these levels; the headline config only)
     steady_from = max(nsteps, (int(props.dict_size) + chunk - 1) // chunk) if args.steady_steps > 0 else nsteps
@@ -420,12 +458,14 @@ def run_single(args, R, lib, src, level, dict_size):
         L.CSCMI_GetStats(h, C.byref(s))
         return s
 
-    def region(a, b):
+    def region(a, b, marks=None):
         s0 = stats()
         R.barrier()
         t0 = time.perf_counter()
         nb = 0
         for i in range(a, b):
+            if marks is not None and i == b - 1:
+                marks.append(len(writer.out))        # --dump-outputs: where the last step's bytes begin
             nb += step(i)
         R.barrier()
         dt = time.perf_counter() - t0
@@ -433,8 +473,13 @@ def run_single(args, R, lib, src, level, dict_size):
 
     for i in range(args.warmup):
         step(i)
-    timed_bytes, dt, s0, s1 = region(args.warmup, nsteps)
+    marks = [] if args.dump_outputs else None
+    timed_bytes, dt, s0, s1 = region(args.warmup, nsteps, marks)
     gpu_stream = bytes(writer.out)       # header + every finished chunk (no EOF yet): a prefix of the full stream
+    if args.dump_outputs:
+        last = gpu_stream[marks[0]:] if marks else b""
+        write_dump(args.dump_outputs, {"stream": byte_array(gpu_stream), "last_step": byte_array(last),
+                                       "lengths": np.array([len(gpu_stream), len(last)], dtype=np.float64)})
     launches = s1.encode_launches - s0.encode_launches
     kern_ms = s1.encode_kernel_ms - s0.encode_kernel_ms
     in_b, out_b = s1.input_bytes - s0.input_bytes, s1.output_bytes - s0.output_bytes
@@ -482,9 +527,10 @@ def run_single(args, R, lib, src, level, dict_size):
     return line
 
 
-def run_split(args, R, lib, src, level, dict_size, split, steps, warmup, with_cpu=True):
+def run_split(args, R, lib, src, level, dict_size, split, steps, warmup, with_cpu=True, dump=None):
     """the archiver's -p<split> tasks of the file, dealt over the ranks; one batch launch per step and rank"""
     torch = R.torch
+    import numpy as np
     from csc_amd import corpus, tasks
     from csc_amd.capi import BytesWriter
     L = lib.lib
@@ -492,6 +538,7 @@ def run_split(args, R, lib, src, level, dict_size, split, steps, warmup, with_cp
     mine = tasks.assign(slices, R.world)[R.rank]                     # dispatch order (largest first), i mod N
     chunk = 2 << 20
     nsteps = warmup + steps
+    check_steps(nsteps, max(n for _, n in slices), chunk)
     hs, ws, devs, sizes = [], [], [], []
     for tid in mine:
         off, n = slices[tid]
@@ -534,7 +581,10 @@ def run_split(args, R, lib, src, level, dict_size, split, steps, warmup, with_cp
     R.barrier()
     t0 = time.perf_counter()
     timed = 0
+    marks = None
     for i in range(warmup, nsteps):
+        if dump and i == nsteps - 1:
+            marks = [len(w.out) for w in ws]        # --dump-outputs: where each task's last-step bytes begin
         timed += step(i)
     R.barrier()
     dt = time.perf_counter() - t0
@@ -543,22 +593,33 @@ def run_split(args, R, lib, src, level, dict_size, split, steps, warmup, with_cp
     tot_bytes = R.reduce(timed, "SUM")
     in_b = R.reduce(s1.input_bytes - s0.input_bytes, "SUM")
     out_b = R.reduce(s1.output_bytes - s0.output_bytes, "SUM")
-    # per-task check against what the REFERENCE wrote for the same task (tests/golden/split_prefix_digests.json, recorded by
+    if dump:
+        # every rank's tasks to rank 0, in task order: the streams so far and what the last timed step appended to each
+        outs = {}
+        for part in R.gather_objects({tid: (bytes(w.out), (marks or [len(w.out)] * S)[k]) for k, (tid, w) in enumerate(zip(mine, ws))}):
+            outs.update(part)
+        if R.rank == 0:
+            order = sorted(outs)
+            write_dump(dump, {"stream": byte_array(b"".join(outs[t][0] for t in order)),
+                              "last_step": byte_array(b"".join(outs[t][0][outs[t][1]:] for t in order)),
+                              "lengths": np.array([[len(outs[t][0]), len(outs[t][0]) - outs[t][1]] for t in order], dtype=np.float64)})
+    # --full: per-task check against what the REFERENCE wrote for the same task (tests/golden/split_prefix_digests.json, recorded by
     # tools/make_golden_prefix.py from oracle/_ref): the stream after c chunks is a prefix of the task's stream
-    gold = golden("split_prefix_digests.json")
-    recs = {}
-    for tid, w, nb in zip(mine, ws, sizes):
-        done = (min(nb, nsteps * chunk) + chunk - 1) // chunk
-        s = bytes(w.out)
-        rec = {"chunks": done, "stream_bytes": len(s), "sha256": hashlib.sha256(s).hexdigest(), "rank": R.rank}
-        g = None
-        if gold and src.synthetic and gold["level"] == level and gold["dict"] == dict_size:
-            g = gold["splits"].get(str(len(slices)), {}).get(str(tid), {}).get(str(done))
-        rec["bit_exact_vs_reference"] = None if g is None else bool(g["sha256"] == rec["sha256"] and g["stream_bytes"] == rec["stream_bytes"])
-        recs[tid] = rec
     merged = {}
-    for part in R.gather_objects(recs):
-        merged.update(part)
+    if args.full:
+        gold = golden("split_prefix_digests.json")
+        recs = {}
+        for tid, w, nb in zip(mine, ws, sizes):
+            done = (min(nb, nsteps * chunk) + chunk - 1) // chunk
+            s = bytes(w.out)
+            rec = {"chunks": done, "stream_bytes": len(s), "sha256": hashlib.sha256(s).hexdigest(), "rank": R.rank}
+            g = None
+            if gold and src.synthetic and gold["level"] == level and gold["dict"] == dict_size:
+                g = gold["splits"].get(str(len(slices)), {}).get(str(tid), {}).get(str(done))
+            rec["bit_exact_vs_reference"] = None if g is None else bool(g["sha256"] == rec["sha256"] and g["stream_bytes"] == rec["stream_bytes"])
+            recs[tid] = rec
+        for part in R.gather_objects(recs):
+            merged.update(part)
     # N > 1, outside the timed region: the one exchange of the sharded archiver (csc_amd/sharded.py) -- every rank's
     # encoded streams so far go to rank 0 as a device tensor over RCCL, rank 0 checks the digests
     exchange = None
@@ -599,9 +660,10 @@ def run_split(args, R, lib, src, level, dict_size, split, steps, warmup, with_cp
                                     f"rank 0's GPU: {S} streams per launch, one workgroup each; per-launch time from HIP events on the launch stream",
                                     traffic_from_profile(f"m{level}_d{args.dict}_p{split}", (s1.input_bytes - s0.input_bytes) / nl) if R.world == 1 else (None, "PMC passes are recorded for N = 1"))
         line["tasks_per_rank"] = [len(a) for a in tasks.assign(slices, R.world)]
-        line["tasks"] = [dict(task=t, **merged[t]) for t in sorted(merged)]
-        ex = [r["bit_exact_vs_reference"] for r in merged.values()]
-        line["bit_exact_vs_reference"] = None if any(e is None for e in ex) else bool(all(ex))
+        if args.full:
+            line["tasks"] = [dict(task=t, **merged[t]) for t in sorted(merged)]
+            ex = [r["bit_exact_vs_reference"] for r in merged.values()]
+            line["bit_exact_vs_reference"] = None if any(e is None for e in ex) else bool(all(ex))
         line["cpu_baseline"] = None
         if with_cpu and not args.no_cpu_baseline:
             # rank 0's host cores, after the timed region (the other ranks wait at the closing barrier): the reference's worker
@@ -628,6 +690,7 @@ def other_config(args, R, lib, name):
     cname, lvl, dct = CONFIGS[name]
     a = copy.copy(args)
     a.config, a.dict, a.level, a.steps, a.warmup, a.steady_steps, a.cpu_sample_mib = name, dct, None, args.other_steps, 1, 0, 16
+    a.dump_outputs = None
     line = run_single(a, R, lib, corpus.Source(cname), lvl, parse_size(dct))
     keep = ("value", "unit", "steps", "warmup", "ms_per_step", "ratio", "data", "roofline", "counters", "cpu_baseline", "bit_exact_vs_cpu_baseline")
     out = {k: line[k] for k in keep if k in line}
@@ -731,12 +794,11 @@ def run_tree(args, R, spec):
     tmax = R.reduce(dt, "MAX")
     line = None
     if R.rank == 0:
-        h = hashlib.sha256()
-        with open(arc, "rb") as f:
-            for blk in iter(lambda: f.read(1 << 22), b""):
-                h.update(blk)
-        gold = (golden("tree_workload.json") or {}).get("trees", {}).get(spec)
         asize = os.path.getsize(arc)
+        if args.dump_outputs:
+            import numpy as np
+            write_dump(args.dump_outputs, {"archive": byte_array(np.memmap(arc, dtype=np.uint8, mode="r") if asize else b""),
+                                           "lengths": np.array([asize], dtype=np.float64)})
         props = csc_props_for(level, dict_size)
         line = {
             "metric": f"archive-create MB/s (10^6 input bytes / wall-clock) on the seeded {spec} workload, csarc a -r -m{level} -d{dict_size >> 20}m; archive bit-exact vs reference (-t1 layout)",
@@ -750,21 +812,29 @@ def run_tree(args, R, spec):
                                    f"stream), encoded tasks -> rank 0 over {'RCCL/xGMI' if R.backend == 'nccl' else R.backend}, rank 0 writes container + index; "
                                    f"step = one whole archive; files read from {root} (page cache), H2D inside the timed region",
                        "tasks": st.get("n_tasks"), "files": len(treegen.files(spec)), **props},
-            "ratio": round(asize / max(1, total), 4), "archive_bytes": asize, "archive_sha256": h.hexdigest(),
-            "bit_exact_vs_reference": None if not gold else bool(gold["sha256"] == h.hexdigest() and gold["archive_bytes"] == asize),
+            "ratio": round(asize / max(1, total), 4), "archive_bytes": asize,
             "roofline": {"bound": "hbm", "achieved": round(alg_bytes(level, asize / max(1, total)) * total * args.steps / tmax / 1e9, 4), "peak": HBM_PEAK_GBS * R.world,
                          "unit": "GB/s", "frac": round(alg_bytes(level, asize / max(1, total)) * total * args.steps / tmax / 1e9 / (HBM_PEAK_GBS * R.world), 8),
                          "traffic": (tr := traffic_from_profile(f"{spec}_m{level}_d{dict_size >> 20}m", total * args.steps))[0], "traffic_note": tr[1],
                          "note": "whole job incl. host I/O: algorithmic bytes of the LZ pass / wall-clock against N x 8 TB/s; kernels: k_encode_runs_multi* (one workgroup per task stream)"},
             "cpu_baseline": None,
         }
+        if args.full:
+            # the archive against what the REFERENCE archiver wrote for the same tree (tests/golden/tree_workload.json)
+            h = hashlib.sha256()
+            with open(arc, "rb") as f:
+                for blk in iter(lambda: f.read(1 << 22), b""):
+                    h.update(blk)
+            gold = (golden("tree_workload.json") or {}).get("trees", {}).get(spec)
+            line["archive_sha256"] = h.hexdigest()
+            line["bit_exact_vs_reference"] = None if not gold else bool(gold["sha256"] == h.hexdigest() and gold["archive_bytes"] == asize)
         if not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"] = cpu_baseline_tree(root, spec, level, dict_size)
             except Exception as e:          # never lose the bench line to the CPU leg
                 line["cpu_baseline"] = {"error": repr(e)[:300]}
         line["last_step_stats_rank0"] = {k: (round(v, 3) if isinstance(v, float) else v) for k, v in st.items()}
-        if gold:
+        if args.full and gold:
             line["cpu_reference_seconds_recorded"] = gold.get("reference_seconds")
     return line
 
@@ -811,22 +881,33 @@ def main():
     ap.add_argument("--dict", default=None)
     ap.add_argument("--split", type=int, default=0, help="task split: 0 = one stream at N = 1 (curve 'single_stream'), -p8 at N > 1 (curve 'p8'); S > 0 = the -p<S> tasks of the "
                     "file at any N.  The N = 1 point of the p8 curve -- what a scaling sweep over --gpus 2/4/8 must be compared with -- is `--gpus 1 --split 8` "
-                    "(also reported as `p8_on_one_gpu` in the default N = 1 line), NOT the default single-stream line")
-    ap.add_argument("--steady-steps", type=int, default=3, help="N = 1 single stream: also time this many chunks after the window has filled (0 = skip)")
+                    "(also reported as `p8_on_one_gpu` in the N = 1 line of --full), NOT the default single-stream line")
+    ap.add_argument("--full", action="store_true", help="every leg beyond the headline (CPU baselines, comparisons with the reference, steady state, "
+                    "p8_on_one_gpu, other_configs, multi_stream, the N > 1 hand-over); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what the timed path computed in its "
+                    "last step as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    ap.add_argument("--steady-steps", type=int, default=None, help="N = 1 single stream: also time this many chunks after the window has filled (0 = skip; default 3 with --full, else 0)")
     ap.add_argument("--cpu-sample-mib", type=int, default=48)
     ap.add_argument("--cpu-split-sample-mib", type=int, default=24, help="-p8 line's CPU leg: bytes of each task every reference worker process encodes")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-exchange", action="store_true",
                     help="N > 1: skip the RCCL hand-over of the encoded streams to rank 0 (outside the timed region)")
-    ap.add_argument("--multi-streams", default="127,954",
-                    help="extra (N = 1, enwik9 only): the WHOLE file as -p<S> task splits, all tasks concurrently on this GPU; '' = skip")
+    ap.add_argument("--multi-streams", default=None,
+                    help="extra (N = 1, enwik9 only): the WHOLE file as -p<S> task splits, all tasks concurrently on this GPU; '' = skip (default '127,954' with --full, else '')")
     ap.add_argument("--workload", default="stream", choices=["stream", "tree", "tree_mid", "tree_small"],
                     help="stream: the libcsc stream workloads above (default).  tree: the many-task curve -- a seeded tree of 4096 files / 2048 extension "
                          "groups (2.1 GB) through the archiver path end to end, tasks dealt over the ranks (csc_amd/sharded.py); tree_small: 256 files (tests)")
-    ap.add_argument("--other-steps", type=int, default=2, help="extra (N = 1, default config only): timed chunks of each of the other single-GPU BASELINE configs "
-                    "(silesia -m5 -d256m, mix5 -m2 -d1024m) reported as `other_configs`; 0 = skip")
-    ap.add_argument("--p8-steps", type=int, default=2, help="extra (N = 1, enwik9 only): the N > 1 workload (-p8) on this one GPU for this many steps; 0 = skip")
+    ap.add_argument("--other-steps", type=int, default=None, help="extra (N = 1, default config only): timed chunks of each of the other single-GPU BASELINE configs "
+                    "(silesia -m5 -d256m, mix5 -m2 -d1024m) reported as `other_configs`; 0 = skip (default 2 with --full, else 0)")
+    ap.add_argument("--p8-steps", type=int, default=None, help="extra (N = 1, enwik9 only): the N > 1 workload (-p8) on this one GPU for this many steps; 0 = skip "
+                    "(default 2 with --full, else 0)")
     args = ap.parse_args()
+    # a plain run does what the headline needs and nothing else; --full turns every other leg on, with the defaults it always had
+    for opt, full_default in (("steady_steps", 3), ("multi_streams", "127,954"), ("other_steps", 2), ("p8_steps", 2)):
+        if getattr(args, opt) is None:
+            setattr(args, opt, full_default if args.full else type(full_default)())
+    if not args.full:
+        args.no_cpu_baseline = args.no_exchange = True
     if args.gpus > 1 and "RANK" not in os.environ:
         spawn_ranks(args.gpus, sys.argv[1:])          # does not return
 
@@ -852,14 +933,14 @@ def main():
     if args.workload != "stream":
         line = run_tree(args, R, args.workload)
     elif split:
-        line = run_split(args, R, lib, src, level, dict_size, split, args.steps, args.warmup)
+        line = run_split(args, R, lib, src, level, dict_size, split, args.steps, args.warmup, dump=args.dump_outputs)
     else:
         line = run_single(args, R, lib, src, level, dict_size)
         if args.config == "enwik9" and args.level is None:
             if args.p8_steps > 0:
                 # the point N = 1 of the -p8 curve (what --gpus 2/4/8 run), as an extra field: `value` stays configs[1]
                 p8 = run_split(args, R, lib, src, level, dict_size, 8, args.p8_steps, 1, with_cpu=False)
-                line["p8_on_one_gpu"] = {k: p8[k] for k in ("value", "unit", "ratio", "ms_per_step", "steps", "warmup", "roofline", "bit_exact_vs_reference", "tasks_per_rank")}
+                line["p8_on_one_gpu"] = {k: p8[k] for k in ("value", "unit", "ratio", "ms_per_step", "steps", "warmup", "roofline", "bit_exact_vs_reference", "tasks_per_rank") if k in p8}
                 line["p8_on_one_gpu"]["what"] = p8["config"]["workload"]
                 line["p8_on_one_gpu"]["curve"] = "p8"
                 if not args.no_cpu_baseline:

@@ -60,3 +60,17 @@ def levels_for(name):
 
 def digest(b):
     return hashlib.sha256(b).hexdigest()
+
+
+def corruptions(s):
+    """25 seeded one-bit flips past the header, then three truncations of stream `s` (tests/test_oracle_vs_ref.py,
+    tools/make_golden_vs_ref.py)"""
+    import random
+    rnd = random.Random(5)
+    out = []
+    for _ in range(25):
+        b = bytearray(s)
+        k = rnd.randrange(40, len(b))
+        b[k] ^= 1 << rnd.randrange(8)
+        out.append(bytes(b))
+    return out + [s[:cut] for cut in (len(s) - 3, len(s) // 2, 70000)]

@@ -113,3 +113,28 @@ def csarc_argv(case):
     if o.get("split_count", 1) != 1:
         argv.append(f"-p{o['split_count']}")
     return argv + ["-f", ARCNAME] + list(CSA_CASES[case]["args"])
+
+
+# tasks of several 2 MiB chunks, an empty file, a file that ends at a chunk boundary and one a byte past it
+# (tests/test_gpu_csa.py::test_add_with_multi_chunk_tasks_reads_ahead_and_equals_the_reference); what the reference archiver writes
+# for it with READ_AHEAD_ARGV: tests/golden/csa_read_ahead.json (tools/make_golden_csa_read_ahead.py)
+READ_AHEAD_FILES = {"d/big1.bin": [["silesia", 31, 0, 9 << 20]], "d/big2.txt": [["text", 32, 0, (5 << 20) + 12345]], "d/edge.bin": [["exe", 33, 0, 2 << 20]],
+                    "d/edge1.bin": [["exe", 34, 0, (2 << 20) + 1]], "d/edge2.bin": [["delta", 35, 0, 300000]], "d/small.txt": [["text", 36, 0, 70000]],
+                    "d/empty.txt": []}
+READ_AHEAD_ARGV = ["a", "-m1", "-d4m", "-r", "-t1", "-f", "ref0.csa", "d"]
+
+
+def make_read_ahead_tree(root):
+    """materialise READ_AHEAD_FILES under root (modes and mtimes pinned); returns {relpath: bytes}"""
+    content = {}
+    for rel, parts in READ_AHEAD_FILES.items():
+        path = os.path.join(root, rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        content[rel] = cases.build(parts)
+        with open(path, "wb") as f:
+            f.write(content[rel])
+        os.chmod(path, 0o644)
+        os.utime(path, (MTIME, MTIME))
+    os.chmod(os.path.join(root, "d"), 0o755)
+    os.utime(os.path.join(root, "d"), (MTIME, MTIME))
+    return content

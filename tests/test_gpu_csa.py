@@ -114,29 +114,23 @@ def test_add_is_independent_of_stream_concurrency(csa, tmp_path, monkeypatch):
     assert cases.digest((tmp_path / csa_cases.ARCNAME).read_bytes()) == GOLD["many_files"]["archive_sha256"]
 
 
-@pytest.mark.skipif(not HAVE_REF, reason="oracle/_ref/csarc_ref not in this snapshot")
 def test_add_with_multi_chunk_tasks_reads_ahead_and_equals_the_reference(csa, tmp_path, monkeypatch):
     """tasks of several 2 MiB chunks: from the second chunk on a stream's bytes come from the read-ahead thread that runs during the
     batch encode call (csa_archive.cpp: FillLane 1 -- the reference's reader thread, csa_io.h:215-272), the adler32 pieces of those
-    chunks are folded one round later.  The archive must still be the reference archiver's, byte for byte; an empty file, a file
-    that ends exactly at a chunk boundary and one that is a chunk plus one byte ride along."""
-    files = {"d/big1.bin": [["silesia", 31, 0, 9 << 20]], "d/big2.txt": [["text", 32, 0, (5 << 20) + 12345]], "d/edge.bin": [["exe", 33, 0, 2 << 20]],
-             "d/edge1.bin": [["exe", 34, 0, (2 << 20) + 1]], "d/edge2.bin": [["delta", 35, 0, 300000]], "d/small.txt": [["text", 36, 0, 70000]], "d/empty.txt": []}
-    for rel, parts in files.items():
-        path = tmp_path / rel
-        path.parent.mkdir(parents=True, exist_ok=True)
-        path.write_bytes(cases.build(parts))
-        os.chmod(path, 0o644)
-        os.utime(path, (csa_cases.MTIME, csa_cases.MTIME))
-    os.chmod(tmp_path / "d", 0o755)
-    os.utime(tmp_path / "d", (csa_cases.MTIME, csa_cases.MTIME))
+    chunks are folded one round later.  The archive must still be the reference archiver's, byte for byte (tests/golden/csa_read_ahead.json,
+    and the reference archiver itself when oracle/_ref travelled with the snapshot); an empty file, a file that ends exactly at a chunk
+    boundary and one that is a chunk plus one byte ride along."""
+    content = csa_cases.make_read_ahead_tree(str(tmp_path))
     monkeypatch.chdir(tmp_path)
     rc, st = csa.add("mine.csa", ["d"], level=1, dict_size=4 << 20, recurse=True, overwrite=True)
-    assert rc == 0 and st["raw_bytes"] == sum(len(cases.build(p)) for p in files.values())
-    subprocess.run([CSARC_REF, "a", "-m1", "-d4m", "-r", "-t1", "-f", "ref0.csa", "d"], cwd=tmp_path, check=True, capture_output=True)
-    mine, ref = (tmp_path / "mine.csa").read_bytes(), (tmp_path / "ref0.csa").read_bytes()
+    assert rc == 0 and st["raw_bytes"] == sum(len(v) for v in content.values())
+    mine = (tmp_path / "mine.csa").read_bytes()
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "csa_read_ahead.json")))
     # (the archive name's length enters the index: same length on both sides)
-    assert len("mine.csa") == len("ref0.csa") and mine == ref
+    assert len("mine.csa") == len("ref0.csa") and (len(mine), cases.digest(mine)) == (gold["archive_size"], gold["archive_sha256"])
+    if HAVE_REF:
+        subprocess.run([CSARC_REF] + csa_cases.READ_AHEAD_ARGV, cwd=tmp_path, check=True, capture_output=True)
+        assert mine == (tmp_path / "ref0.csa").read_bytes()
     rc, st2 = csa.test("mine.csa", [])
     assert rc == 0 and st2["verify_failures"] == 0
 
@@ -373,7 +367,7 @@ def test_bench_multi_rank_path_two_processes(tmp_path):
     Two ranks share the one GPU of this box over gloo (CSC_BENCH_BACKEND, tests only; the driver's runs use RCCL)."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(CSC_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--cpu-split-sample-mib", "2"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--cpu-split-sample-mib", "2", "--full"],
                          cwd=tmp_path, env=env, capture_output=True, text=True, timeout=1500)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -397,7 +391,7 @@ def test_bench_tree_workload_small_archive_equals_reference(tmp_path):
     import subprocess
     import sys
     env = dict(os.environ, CSC_TREE_DIR=str(tmp_path))
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tree_small", "--steps", "1", "--warmup", "0"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "tree_small", "--steps", "1", "--warmup", "0", "--full"],
                        env=env, stdout=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
@@ -405,3 +399,26 @@ def test_bench_tree_workload_small_archive_equals_reference(tmp_path):
     assert line["value"] > 0 and line["scaling"] == "strong"
     cb = line["cpu_baseline"]       # the reference archiver itself, timed on this box (oracle/_ref/csarc_ref -t8)
     assert cb and (("error" in cb and "csarc_ref" in cb["error"]) or (cb["value"] > 0 and cb["kind"] == "reference" and cb["cores"] >= 1))
+
+
+def test_bench_plain_run_dumps_the_stream_the_reference_writes(tmp_path):
+    """`bench.py --steps 1 --warmup 1 --dump-outputs DIR`, the plain form: the line holds the contract fields and none of the legs of
+    --full; DIR holds the single stream after its two chunks -- which is, byte for byte, the stream the REFERENCE wrote after two chunks
+    (tests/golden/split_prefix_digests.json, task 0 of the one-task split) -- and the bytes the timed step appended to it"""
+    import hashlib
+    import numpy as np
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--dump-outputs", str(out)],
+                       cwd=tmp_path, stdout=subprocess.PIPE, text=True, timeout=600)
+    assert p.returncode == 0
+    line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 1 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0 and line["higher_is_better"] is True
+    assert line["unit"] == "MB/s" and line["curve"] == "single_stream" and line["cpu_baseline"] is None
+    assert not {"steady", "p8_on_one_gpu", "other_configs", "multi_stream", "bit_exact_vs_cpu_baseline"} & set(line)
+    stream, last, lengths = (np.load(out / f"{n}.npy") for n in ("stream", "last_step", "lengths"))
+    assert stream.dtype == np.float32 and last.dtype == np.float32 and lengths.dtype == np.float64
+    gold = json.load(open(os.path.join(ROOT, "tests", "golden", "split_prefix_digests.json")))["splits"]["1"]["0"]["2"]
+    got = stream.astype(np.uint8).tobytes()
+    assert lengths.tolist() == [len(got), len(last)] and len(got) == gold["stream_bytes"]
+    assert hashlib.sha256(got).hexdigest() == gold["sha256"]
+    assert 0 < len(last) < len(got) and np.array_equal(last, stream[-len(last):])

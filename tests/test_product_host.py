@@ -122,6 +122,20 @@ def test_bench_summary_is_compact_and_carries_the_other_configs():
     assert s["m5"] == [0.57, 9e-6, 4.5, True] and s["m2"][0] == 2.6 and s["p8"][0] == 17.1 and s["p954"][0] == 465.0 and s["p954_dec"] == [670.0, True]
 
 
+def test_bench_dump_arrays_are_exact_and_bounded():
+    """--dump-outputs: byte values go out exactly as float32, and an output longer than DUMP_MAX_BYTES as the same fixed sample of it
+    every time, so that the (at most three) arrays of a run stay under 64 MB"""
+    import numpy as np
+    b = _bench_module()
+    small = bytes(range(256)) * 3
+    a = b.byte_array(small)
+    assert a.dtype == np.float32 and a.tolist() == list(small)
+    big = (np.arange(3 * b.DUMP_MAX_BYTES + 7, dtype=np.int64) * 7919 % 251).astype(np.uint8)
+    s = b.byte_array(big)
+    assert s.dtype == np.float32 and s.size == b.DUMP_MAX_BYTES and np.array_equal(s, b.byte_array(big.tobytes()))
+    assert s[0] == big[0] and set(np.unique(s).tolist()) <= set(range(251)) and 3 * s.nbytes <= 64e6
+
+
 def test_library_exports_only_its_api():
     """a drop-in for libcsc.a must not leak C++ symbols (kernel launch stubs, helpers) into the program it is linked into:
     the dynamic symbol table holds the C API -- CSCEnc* / CSCDec* / CSCEncProps_* (the reference's eleven), CSA_*, the CSCMI_* /

@@ -6,10 +6,10 @@ cd $GRAFT_REPO_ROOT
 TAG=${1:-r05_tree}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-python bench.py --workload tree --steps 2 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
-python bench.py --workload tree --steps 1 --warmup 0 --no-cpu-baseline > $OUT/bench_cold.json 2> $OUT/bench_cold.err
+python bench.py --full --workload tree --steps 2 --warmup 1 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --workload tree --steps 1 --warmup 0 --no-cpu-baseline > $OUT/bench_cold.json 2> $OUT/bench_cold.err
 for SET in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   T=$(echo $SET | tr ' ' '_')
-  rocprofv3 --pmc $SET --kernel-trace --output-format csv -d $OUT/pmc_$T -o p -- python3 bench.py --workload tree --steps 1 --warmup 0 --no-cpu-baseline > $OUT/pmc_$T.json 2> $OUT/pmc_$T.err
+  rocprofv3 --pmc $SET --kernel-trace --output-format csv -d $OUT/pmc_$T -o p -- python3 bench.py --full --workload tree --steps 1 --warmup 0 --no-cpu-baseline > $OUT/pmc_$T.json 2> $OUT/pmc_$T.err
 done
 tail -c 400 $OUT/bench.json
