@@ -149,3 +149,31 @@ def test_library_exports_only_its_api():
         bad = [n for n in names if not re.match(r"^(CSCEnc|CSCDec|CSCEncProps_|CSCMI_|CSA_|CSAMI_|CSCST_)", n)]
         assert not bad, (lib, bad[:10])
         assert any(n == "CSCEnc_Encode" for n in names)
+
+
+def _launched_encoder_kernels():
+    """the kernels named in a hipLaunchKernelGGL of the encoder's chunk launchers (launch_encode_runs*, csc_kernels_blocks.inc)"""
+    src = open(os.path.join(ROOT, "csc_amd", "csrc", "csc_kernels_blocks.inc")).read()
+    names = set()
+    for m in re.finditer(r"\nvoid (launch_encode_runs\w*)\([^)]*\)\s*\{(.*?)\n\}", src, flags=re.S):
+        for k in re.findall(r"hipLaunchKernelGGL\(\(?(k_\w+(?:<[^>]*>)?)\)?\s*,", m.group(2)):
+            names.add(k.replace(" ", ""))
+    return names
+
+
+def test_every_encoder_form_is_in_the_dispatch_matrix():
+    """tests/test_gpu_forms.py's FORMS names every kernel the encoder's launchers can start, and its thresholds are the
+    sources' (kBtMultiMax, kD4MultiMax, kHpMultiMax): a new form or a retuned threshold fails here until the matrix follows"""
+    import test_gpu_forms
+    launched = _launched_encoder_kernels()
+    assert len(launched) == 14, sorted(launched)
+    in_forms = {f[k] for f in test_gpu_forms.FORMS.values() for k in ("single", "multi", "over")}
+    assert launched == in_forms, (sorted(launched - in_forms), sorted(in_forms - launched))
+    srcs = "".join(open(os.path.join(ROOT, "csc_amd", "csrc", f)).read() for f in ("csc_kernels_bt.inc", "csc_kernels_dp4.inc", "csc_kernels_hp.inc"))
+    for name, value in test_gpu_forms.THRESHOLDS.items():
+        assert int(re.search(rf"constexpr uint32_t {name} = (\d+);", srcs).group(1)) == value, name
+    assert {f["threshold"] for f in test_gpu_forms.FORMS.values()} - {None} == set(test_gpu_forms.THRESHOLDS)
+    for row, f in test_gpu_forms.FORMS.items():           # every threshold is tested at its value and one above
+        if f["threshold"] and f["multi"] != f["over"]:
+            t = test_gpu_forms.THRESHOLDS[f["threshold"]]
+            assert {(row, t), (row, t + 1)} <= set(test_gpu_forms.THRESHOLD_CASES), row
