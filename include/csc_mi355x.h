@@ -80,6 +80,12 @@ void CSCDec_ReadProperties(CSCProps *props, uint8_t *stream);                   
 CSCDecHandle CSCDec_Create(const CSCProps *props, ISeqInStream *instream, ISzAlloc *alloc);   /* csc_dec.h:13-15 */
 void CSCDec_Destroy(CSCDecHandle p);                                               /* csc_dec.h:17 */
 int CSCDec_Decode(CSCDecHandle p, ISeqOutStream *outstream, ICompressProgress *progress);     /* csc_dec.h:19-21 */
+/* LIMIT: a single packet coded in more than 32 768 model bits is refused with DECODE_ERROR (earlier runs and blocks delivered,
+ * no byte of that run or block).  No encoder writes one, but valid streams that the reference decodes can hold one in two ways:
+ *   - an LZ copy longer than 32 768 x 143 bytes: needs raw_blocksize > ~4.5 MiB in the header (the default is 2 MiB);
+ *   - an RLE run of a delta block (DT_DLT) whose CODED length exceeds 32 768 x 143: the reference clips a run at the block's
+ *     size whatever was coded, so this is reachable at the default geometry, in a block of a few bytes.
+ * Parity with the reference is knowingly not reached for these two. */
 
 /* ---- extensions of this library (measurement + device-resident input); not in the reference ---- */
 typedef struct {

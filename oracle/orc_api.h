@@ -79,4 +79,13 @@ void orc_inverse_delta(uint8_t *buf, uint32_t size, uint32_t chn);
 /* the two float-built tables */
 void orc_tables(uint32_t p2bits[512], uint32_t logtab[513]);
 
+
+/* ---- stream synthesizer (orc_synth.c): a script of packets -> a stream body, through the oracle's coder and model ---- */
+enum {
+    ORC_OP_BLOCK = 1, ORC_OP_LIT, ORC_OP_MATCH, ORC_OP_REP, ORC_OP_REP0LEN1, ORC_OP_END_RUN, ORC_OP_RESTART,
+    ORC_OP_BAD, ORC_OP_ENTROPY, ORC_OP_DLT, ORC_OP_RLE_LIT, ORC_OP_RLE_RUN, ORC_OP_EOF, ORC_OP_RAW_TYPE,
+    ORC_OP_LITS, ORC_OP_FLUSH
+};
+int orc_synth(const CSCProps *props, const uint32_t *script, size_t words, ISeqOutStream *out, ISzAlloc *alloc);
+
 #endif

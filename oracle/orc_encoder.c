@@ -19,95 +19,9 @@
 
 #include "orc_api.h"
 
-#define KB 1024u
-#define MB 1048576u
-#define MIN_BLOCK (8u * KB)       /* csc_typedef.h:9 MinBlockSize */
-#define UMIN(a, b) ((a) < (b) ? (a) : (b))
+#include "orc_enc_int.h"
 
-/* block types, csc_typedef.h:20-40 */
-enum {
-    DT_NORMAL = 1, DT_ENGTXT = 2, DT_EXE = 3, DT_FAST = 4, DT_NO_LZ = 5,
-    DT_ENTROPY = 7, DT_BAD = 8, SIG_EOF = 9, DT_DLT = 0x10, DT_SKIP = 0x1E
-};
 static const uint32_t kDltIndex[5] = {1, 2, 3, 4, 8};
-
-#define HT2_SIZE (16u * KB)       /* csc_mf.h:18 */
-#define HT3_SIZE (64u * KB)       /* csc_mf.h:17 */
-#define MF_CAND_LIMIT 32          /* csc_mf.h:34 */
-#define AP_LIMIT 2048             /* csc_lz.h:43 */
-
-typedef struct { uint32_t len; uint32_t dist; } MFUnit; /* len doubles as price, csc_mf.h:8-14 */
-
-typedef struct {
-    uint32_t dist, state;
-    int back_pos, next_pos;
-    uint32_t price, lit;
-    uint32_t rep_dist[4];
-} APUnit; /* csc_lz.h:33-41 */
-
-typedef struct {
-    uint32_t next[26];
-    uint8_t symbol;
-} TrieNode; /* csc_filters.h:30-33 */
-
-typedef struct OrcEnc {
-    ISzAlloc *alloc;
-    ISeqOutStream *os;
-    CSCProps props;
-    jmp_buf on_error;             /* replaces `throw (int)` of csc_coder.h:11 */
-
-    /* ---- MemIO + Coder, csc_coder.h:15-64 ---- */
-    uint32_t bsize;
-    uint8_t *rc_buf, *bc_buf;
-    uint32_t rc_size, bc_size;
-    uint64_t rc_low, rc_cachesize;
-    uint32_t rc_range;
-    uint8_t rc_cache;
-    uint32_t bc_curbits, bc_curval;
-    int64_t outsize;
-
-    /* ---- Model, csc_model.h:58-122 ---- */
-    uint32_t p_state[64 * 3];
-    uint32_t state, ctx;
-    uint32_t p_rle_flag;
-    uint32_t *p_lit, *p_delta;
-    uint32_t p_repdist[64 * 4];
-    uint32_t p_dist[8 + 16 * 2 + 32 * 4];
-    uint32_t p_longlen;
-    uint32_t p_2_bits[512];
-    uint32_t p_len_slot[2], p_len_x1[8], p_len_x2[8], p_len_x3[128];
-    uint32_t p_dist_extra[29 * 16];
-    uint32_t len_price[32];
-    uint32_t lp_rebuild_int;
-
-    /* ---- MatchFinder, csc_mf.h:16-53 ---- */
-    uint8_t *wnd;
-    uint32_t wnd_size, vld_rge;
-    uint32_t *mfbuf, *ht2, *ht3, *ht6, *bt_head, *bt_nodes;
-    uint64_t mf_size;
-    uint32_t ht_bits, ht_width, ht_low;
-    uint32_t bt_bits, bt_size, bt_pos;
-    uint32_t ht_cyc, bt_cyc, good_len;
-    uint32_t pos;
-    MFUnit mfcand[MF_CAND_LIMIT];
-
-    /* ---- LZ, csc_lz.h:19-56 ---- */
-    uint32_t wnd_curpos;
-    uint32_t rep_dist[4];
-    uint32_t lz_good_len, lz_bt_cyc, lz_ht_cyc;
-    MFUnit *appt;
-    APUnit *ap;
-
-    /* ---- Analyzer, csc_analyzer.h:19 ---- */
-    uint32_t log_table[(MIN_BLOCK >> 4) + 1];
-
-    /* ---- Filters, csc_filters.h:26-62 ---- */
-    TrieNode trie[300];
-    uint8_t *swap_buf;
-    uint32_t swap_size;
-    uint32_t x0, x1, ei, ek;
-    uint8_t ecs;
-} OrcEnc;
 
 /* ===================================================================== */
 /* default allocator, csc_default_alloc.cpp:5-17                          */
@@ -117,7 +31,7 @@ static ISzAlloc g_default_alloc = {def_alloc, def_free};
 
 /* ===================================================================== */
 /* MemIO::WriteBlock, csc_memio.cpp:83-108                               */
-static int write_block(OrcEnc *e, uint8_t *buf, uint32_t size, int rc1bc0)
+ORC_INT int write_block(OrcEnc *e, uint8_t *buf, uint32_t size, int rc1bc0)
 {
     uint8_t fb = (uint8_t)(rc1bc0 << 7);
     if (size == e->bsize) fb |= (1 << 6);
@@ -133,14 +47,14 @@ static int write_block(OrcEnc *e, uint8_t *buf, uint32_t size, int rc1bc0)
 
 /* ===================================================================== */
 /* Coder, csc_coder.cpp                                                  */
-static void coder_reset_state(OrcEnc *e) /* csc_coder.cpp:9-16,65-73 */
+ORC_INT void coder_reset_state(OrcEnc *e) /* csc_coder.cpp:9-16,65-73 */
 {
     e->rc_low = 0; e->rc_range = 0xFFFFFFFFu; e->rc_cachesize = 1; e->rc_cache = 0;
     e->rc_size = e->bc_size = 0; e->bc_curbits = e->bc_curval = 0;
 }
 
 /* Coder::RC_ShiftLow, csc_coder.cpp:89-112 */
-static void rc_shift_low(OrcEnc *e)
+ORC_INT void rc_shift_low(OrcEnc *e)
 {
     if ((uint32_t)e->rc_low < 0xFF000000u || (int32_t)(e->rc_low >> 32) != 0) {
         uint8_t temp = e->rc_cache;
@@ -160,24 +74,6 @@ static void rc_shift_low(OrcEnc *e)
     e->rc_low = (uint64_t)((uint32_t)e->rc_low << 8);
 }
 
-/* EncodeBit macro, csc_coder.h:67-81 */
-static inline void enc_bit(OrcEnc *e, uint32_t v, uint32_t *p)
-{
-    uint32_t bound = (e->rc_range >> 12) * *p;
-    if (v) {
-        e->rc_range = bound;
-        *p += (0xFFF - *p) >> 5;
-    } else {
-        e->rc_low += bound;
-        e->rc_range -= bound;
-        *p -= *p >> 5;
-    }
-    if (e->rc_range < (1u << 24)) {
-        e->rc_range <<= 8;
-        rc_shift_low(e);
-    }
-}
-
 /* BCWCheckBound, csc_coder.h:7-16 */
 static void bc_check_bound(OrcEnc *e)
 {
@@ -190,7 +86,7 @@ static void bc_check_bound(OrcEnc *e)
 }
 
 /* Coder::EncDirect16, csc_coder.cpp:76-87 */
-static void enc_direct16(OrcEnc *e, uint32_t val, uint32_t len)
+ORC_INT void enc_direct16(OrcEnc *e, uint32_t val, uint32_t len)
 {
     e->bc_curval = (e->bc_curval << len) | val;
     e->bc_curbits += len;
@@ -202,7 +98,7 @@ static void enc_direct16(OrcEnc *e, uint32_t val, uint32_t len)
 }
 
 /* EncodeDirect macro, csc_coder.h:83-88 */
-static void enc_direct(OrcEnc *e, uint32_t v, uint32_t l)
+ORC_INT void enc_direct(OrcEnc *e, uint32_t v, uint32_t l)
 {
     if (l <= 16) enc_direct16(e, v, l);
     else { enc_direct16(e, v >> 16, l - 16); enc_direct16(e, v & 0xFFFF, 16); }
@@ -210,7 +106,7 @@ static void enc_direct(OrcEnc *e, uint32_t v, uint32_t l)
 
 /* Coder::Flush, csc_coder.cpp:40-74.  The byte at rc_buf[rc_size] is NOT
  * stored (stale content of the persistent buffer). */
-static void coder_flush(OrcEnc *e)
+ORC_INT void coder_flush(OrcEnc *e)
 {
     for (int i = 0; i < 5; i++) rc_shift_low(e);
     e->rc_size++;
@@ -242,9 +138,9 @@ static void fill_p2bits(uint32_t t[512]) /* csc_model.cpp:68-70: log(float) is t
         t[i] = (uint32_t)(128 * logf((float)(i * 8 + 4) / 4096) / log(0.5));
 }
 
-static void fill_probs(uint32_t *p, int n) { for (int i = 0; i < n; i++) p[i] = 2048; }
+ORC_INT void fill_probs(uint32_t *p, int n) { for (int i = 0; i < n; i++) p[i] = 2048; }
 
-static void model_reset(OrcEnc *e) /* csc_model.cpp:88-111 */
+ORC_INT void model_reset(OrcEnc *e) /* csc_model.cpp:88-111 */
 {
     e->alloc->Free(e->alloc, e->p_delta);
     e->p_delta = NULL;
@@ -294,7 +190,7 @@ static void encode_matchlen_1(OrcEnc *e, uint32_t len)
 }
 
 /* Model::encode_matchlen_2, csc_model.cpp:147-159 */
-static void encode_matchlen_2(OrcEnc *e, uint32_t len)
+ORC_INT void encode_matchlen_2(OrcEnc *e, uint32_t len)
 {
     if (len >= 143) {
         encode_matchlen_1(e, 143);
@@ -306,14 +202,14 @@ static void encode_matchlen_2(OrcEnc *e, uint32_t len)
 }
 
 /* literal bits under an order-1 context row, shared by csc_model.cpp:176-183,431-441,452-459,504-509 */
-static void encode_byte_tree(OrcEnc *e, uint32_t *row, uint32_t c)
+ORC_INT void encode_byte_tree(OrcEnc *e, uint32_t *row, uint32_t c)
 {
     c |= 0x100;
     do { enc_bit(e, (c >> 7) & 1, &row[c >> 8]); c <<= 1; } while (c < 0x10000);
 }
 
 /* Model::EncodeLiteral, csc_model.cpp:169-183 */
-static void encode_literal(OrcEnc *e, uint32_t c)
+ORC_INT void encode_literal(OrcEnc *e, uint32_t c)
 {
     enc_bit(e, 0, &e->p_state[e->state * 3 + 0]);
     e->state = (e->state * 4) & 0x3F;
@@ -333,7 +229,7 @@ static uint32_t literal_price(const OrcEnc *e, uint32_t fstate, uint32_t fctx, u
 }
 
 /* Model::EncodeRep0Len1, csc_model.cpp:198-207 */
-static void encode_rep0len1(OrcEnc *e)
+ORC_INT void encode_rep0len1(OrcEnc *e)
 {
     enc_bit(e, 1, &e->p_state[e->state * 3 + 0]);
     enc_bit(e, 0, &e->p_state[e->state * 3 + 1]);
@@ -350,7 +246,7 @@ static uint32_t rep0len1_price(const OrcEnc *e, uint32_t fs)
 }
 
 /* Model::EncodeRepDistMatch, csc_model.cpp:218-232 */
-static void encode_rep_match(OrcEnc *e, uint32_t rep_idx, uint32_t match_len)
+ORC_INT void encode_rep_match(OrcEnc *e, uint32_t rep_idx, uint32_t match_len)
 {
     enc_bit(e, 1, &e->p_state[e->state * 3 + 0]);
     enc_bit(e, 0, &e->p_state[e->state * 3 + 1]);
@@ -426,7 +322,7 @@ static uint32_t dist_slot(uint32_t dist)
 }
 
 /* Model::EncodeMatch, csc_model.cpp:301-366 */
-static void encode_match(OrcEnc *e, uint32_t dist, uint32_t len)
+ORC_INT void encode_match(OrcEnc *e, uint32_t dist, uint32_t len)
 {
     enc_bit(e, 1, &e->p_state[e->state * 3 + 0]);
     enc_bit(e, 1, &e->p_state[e->state * 3 + 1]);
@@ -461,7 +357,7 @@ static uint32_t match_dist_price(const OrcEnc *e, uint32_t fs, uint32_t dist)
 }
 
 /* Model::EncodeInt, csc_model.cpp:389-414 */
-static void encode_int(OrcEnc *e, uint32_t num)
+ORC_INT void encode_int(OrcEnc *e, uint32_t num)
 {
     uint32_t tmp = num, slot = 0;
     while (tmp) { tmp >>= 1; slot++; }
@@ -472,7 +368,7 @@ static void encode_int(OrcEnc *e, uint32_t num)
 }
 
 /* Model::CompressLiterals, csc_model.cpp:448-461 */
-static void compress_literals(OrcEnc *e, const uint8_t *src, uint32_t size)
+ORC_INT void compress_literals(OrcEnc *e, const uint8_t *src, uint32_t size)
 {
     encode_int(e, size);
     for (uint32_t i = 0; i < size; i++) {
@@ -484,36 +380,47 @@ static void compress_literals(OrcEnc *e, const uint8_t *src, uint32_t size)
 }
 
 /* Model::CompressBad, csc_model.cpp:463-469 */
-static void compress_bad(OrcEnc *e, const uint8_t *src, uint32_t size)
+ORC_INT void compress_bad(OrcEnc *e, const uint8_t *src, uint32_t size)
 {
     encode_int(e, size);
     for (uint32_t i = 0; i < size; i++) enc_direct16(e, src[i], 8);
 }
 
-/* Model::CompressRLE, csc_model.cpp:471-513 */
-static void compress_rle(OrcEnc *e, const uint8_t *src, uint32_t size)
+/* Model::CompressRLE, csc_model.cpp:471-513, in the three pieces it is made of */
+ORC_INT void rle_begin(OrcEnc *e, uint32_t size)
 {
-    uint32_t i, j, len, sctx = 0;
     encode_int(e, size);
     if (e->p_delta == NULL) {
         e->p_delta = (uint32_t *)e->alloc->Alloc(e->alloc, 256 * 256 * 4);
         fill_probs(e->p_delta, 256 * 256);
     }
+}
+ORC_INT void rle_lit(OrcEnc *e, uint32_t sctx, uint32_t c)
+{
+    enc_bit(e, 0, &e->p_rle_flag);
+    encode_byte_tree(e, &e->p_delta[sctx * 256], c);
+}
+ORC_INT void rle_run(OrcEnc *e, uint32_t len) /* a run of len + 11 */
+{
+    enc_bit(e, 1, &e->p_rle_flag);
+    encode_matchlen_2(e, len);
+}
+static void compress_rle(OrcEnc *e, const uint8_t *src, uint32_t size)
+{
+    uint32_t i, j, len, sctx = 0;
+    rle_begin(e, size);
     for (i = 0; i < size;) {
         if (i > 0 && size - i > 3 && src[i - 1] == src[i] && src[i] == src[i + 1] && src[i] == src[i + 2]) {
             j = i + 3; len = 3;
             while (j < size && src[j] == src[j - 1]) { len++; j++; }
             if (len > 10) {
                 sctx = src[j - 1];
-                len -= 11;
-                enc_bit(e, 1, &e->p_rle_flag);
-                encode_matchlen_2(e, len);
+                rle_run(e, len - 11);
                 i = j;
                 continue;
             }
         }
-        enc_bit(e, 0, &e->p_rle_flag);
-        encode_byte_tree(e, &e->p_delta[sctx * 256], src[i]);
+        rle_lit(e, sctx, src[i]);
         sctx = src[i];
         i++;
     }
