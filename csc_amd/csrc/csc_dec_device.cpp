@@ -9,6 +9,8 @@
 //     "other" kind.
 //   * CSCDec_Decode (csc_dec.cpp:740-777) loops over Decompress calls; each is one or more launches
 //     of the resumable kernel; the decoded run is copied back and handed to ISeqOutStream::Write.
+//   * CSCMI_DecodeDeviceBatch is the path without callbacks: streams that lie in device memory, raw bytes that stay
+//     there; block reader and run delivery are in the kernel (k_decode_dev*), the host only relaunches live streams.
 // No CPU decoding path exists in this library.
 #include <hip/hip_runtime.h>
 
@@ -27,6 +29,7 @@ namespace cscmi {
 void launch_decode_init(DecState *D, hipStream_t st);
 void launch_decode_run(DecState *D, hipStream_t st);
 void launch_decode_run_multi(DecState *const *states, uint32_t n, hipStream_t st);
+void launch_decode_dev(DecState *const *states, DecState *first, uint32_t n, hipStream_t st);
 hipStream_t pooled_stream(int device);                     // csc_host.cpp
 void pooled_stream_release(int device, hipStream_t s);
 }
@@ -64,6 +67,10 @@ std::mutex g_dec_mu;
 std::vector<DecRes *> g_dec_cache;
 size_t g_dec_cache_bytes = 0;
 constexpr size_t kDecCacheMaxBytes = 32ull << 30;
+// CSCMI_DecodeDeviceBatch: output a launch delivers per stream before it returns (a few MiB = a second or two of kernel time at the
+// 2.4-5.5 MB/s a stream decodes at; not tuned by measurement: profiles/decode_device.md), streams a group
+constexpr uint64_t kDevLaunchBytes = 4ull << 20;
+constexpr size_t kDevGroupMax = 1024;
 
 void dec_res_destroy(DecRes *r)
 {
@@ -125,6 +132,52 @@ void dec_res_put(DecRes *r)
         }
     }
     dec_res_destroy(r);
+}
+
+size_t dec_cache_bytes()
+{
+    std::lock_guard<std::mutex> lk(g_dec_mu);
+    return g_dec_cache_bytes;
+}
+
+// where a decoder's pieces lie in its device slab and its pinned slab (both sizes are the resource cache's key)
+struct DecLayout {
+    size_t o_wnd, o_plit, o_out, o_swap, o_q0, o_q1, o_qs0, o_qs1, o_ua, o_uv, o_words, o_state, dsize;
+    size_t p_read, p_block, p_out, hsize;
+};
+bool dec_props_ok(const CSCProps *props)   // csc_dec.cpp:697-700
+{
+    if (props->dict_size > 1024 * kMB || props->dict_size < 32 * kKB) return false;
+    return props->csc_blocksize != 0 && props->raw_blocksize != 0;
+}
+// fills the configuration words of `h` from the properties and returns the layout that goes with them
+DecLayout dec_layout(const CSCProps *props, DecState &h)
+{
+    h.wnd_size = (uint32_t)props->dict_size; h.bsize = props->csc_blocksize; h.raw_blocksize = props->raw_blocksize;
+    h.qslots = 2 * (props->raw_blocksize / props->csc_blocksize + 1) + 16;
+    DecLayout l;
+    size_t doff = 0, hoff = 0;
+    auto dtake = [&](size_t bytes) { size_t o = doff; doff += (bytes + 255) & ~(size_t)255; return o; };
+    auto htake = [&](size_t bytes) { size_t o = hoff; hoff += (bytes + 255) & ~(size_t)255; return o; };
+    l.o_wnd = dtake((size_t)h.wnd_size + 256); l.o_plit = dtake(2 * 65536 * sizeof(uint32_t));
+    l.o_out = dtake((size_t)h.raw_blocksize + 256); l.o_swap = dtake(2 * (size_t)h.raw_blocksize + 256);
+    l.o_q0 = dtake((size_t)h.qslots * h.bsize + 256); l.o_q1 = dtake((size_t)h.qslots * h.bsize + 256);
+    l.o_qs0 = dtake(sizeof(uint32_t) * h.qslots); l.o_qs1 = dtake(sizeof(uint32_t) * h.qslots);
+    l.o_ua = dtake(sizeof(uint32_t) * kDecUndoCap); l.o_uv = dtake(sizeof(uint32_t) * kDecUndoCap);
+    l.o_words = dtake(sizeof(kWords)); l.o_state = dtake(sizeof(DecState));
+    l.p_read = htake(sizeof(DecState)); l.p_block = htake(h.bsize); l.p_out = htake(h.raw_blocksize);
+    l.dsize = doff; l.hsize = hoff;
+    return l;
+}
+// the device pointers of `h` inside slab D, and the stream's start phase
+void dec_place(DecState &h, uint8_t *D, const DecLayout &l)
+{
+    h.wnd = D + l.o_wnd; h.p_lit = (uint32_t *)(D + l.o_plit); h.out = D + l.o_out; h.swap = D + l.o_swap;
+    h.q[0] = D + l.o_q0; h.q[1] = D + l.o_q1; h.qsize[0] = (uint32_t *)(D + l.o_qs0); h.qsize[1] = (uint32_t *)(D + l.o_qs1);
+    h.undo_addr = (uint32_t *)(D + l.o_ua); h.undo_val = (uint32_t *)(D + l.o_uv);
+    h.words = D + l.o_words;
+    h.p_delta = h.p_lit + 65536;
+    h.phase = DEC_PH_PRIME0;
 }
 
 struct DecInstance {
@@ -232,47 +285,30 @@ void CSCDec_ReadProperties(CSCProps *props, uint8_t *s)   // csc_dec.cpp:733-738
 CSCDecHandle CSCDec_Create(const CSCProps *props, ISeqInStream *instream, ISzAlloc *alloc)   // csc_dec.cpp:692-720
 {
     if (alloc == NULL) alloc = &g_default_alloc;
-    if (props->dict_size > 1024 * kMB || props->dict_size < 32 * kKB) return NULL;
-    if (props->csc_blocksize == 0 || props->raw_blocksize == 0) return NULL;
+    if (!dec_props_ok(props)) return NULL;
     if (CSCMI_DeviceCheck() != 0) return NULL;
     DecInstance *x = (DecInstance *)alloc->Alloc(alloc, sizeof(DecInstance));
     if (!x) return NULL;
     memset(x, 0, sizeof(*x));
     x->magic = kMagicDec; x->alloc = alloc; x->is = instream;
     DecState &h = x->h;
-    h.wnd_size = (uint32_t)props->dict_size; h.bsize = props->csc_blocksize; h.raw_blocksize = props->raw_blocksize;
-    h.qslots = 2 * (props->raw_blocksize / props->csc_blocksize + 1) + 16;
     bool ok = hipGetDevice(&x->device) == hipSuccess;
     // one device slab (zero-filled) and one pinned slab
-    size_t doff = 0, hoff = 0;
-    auto dtake = [&](size_t bytes) { size_t o = doff; doff += (bytes + 255) & ~(size_t)255; return o; };
-    auto htake = [&](size_t bytes) { size_t o = hoff; hoff += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t o_wnd = dtake((size_t)h.wnd_size + 256), o_plit = dtake(2 * 65536 * sizeof(uint32_t));
-    const size_t o_out = dtake((size_t)h.raw_blocksize + 256), o_swap = dtake(2 * (size_t)h.raw_blocksize + 256);
-    const size_t o_q0 = dtake((size_t)h.qslots * h.bsize + 256), o_q1 = dtake((size_t)h.qslots * h.bsize + 256);
-    const size_t o_qs0 = dtake(sizeof(uint32_t) * h.qslots), o_qs1 = dtake(sizeof(uint32_t) * h.qslots);
-    const size_t o_ua = dtake(sizeof(uint32_t) * kDecUndoCap), o_uv = dtake(sizeof(uint32_t) * kDecUndoCap);
-    const size_t o_words = dtake(sizeof(kWords)), o_state = dtake(sizeof(DecState));
-    const size_t p_read = htake(sizeof(DecState)), p_block = htake(h.bsize), p_out = htake(h.raw_blocksize);
-    if (ok) { x->res = dec_res_get(x->device, doff, hoff); ok = x->res != nullptr; }
+    const DecLayout l = dec_layout(props, h);
+    if (ok) { x->res = dec_res_get(x->device, l.dsize, l.hsize); ok = x->res != nullptr; }
     if (ok) {
         uint8_t *D = x->res->dslab, *H = x->res->hslab;
         x->stream = x->res->stream;
-        h.wnd = D + o_wnd; h.p_lit = (uint32_t *)(D + o_plit); h.out = D + o_out; h.swap = D + o_swap;
-        h.q[0] = D + o_q0; h.q[1] = D + o_q1; h.qsize[0] = (uint32_t *)(D + o_qs0); h.qsize[1] = (uint32_t *)(D + o_qs1);
-        h.undo_addr = (uint32_t *)(D + o_ua); h.undo_val = (uint32_t *)(D + o_uv);
-        h.words = D + o_words;
-        x->d_state = (DecState *)(D + o_state);
-        x->h_read = (DecState *)(H + p_read); x->h_block = H + p_block; x->h_out = H + p_out;
-        ok = hipMemsetAsync(D, 0, doff, x->stream) == hipSuccess
-          && hipMemcpyAsync(D + o_words, kWords, sizeof(kWords), hipMemcpyHostToDevice, x->stream) == hipSuccess;
+        dec_place(h, D, l);
+        x->d_state = (DecState *)(D + l.o_state);
+        x->h_read = (DecState *)(H + l.p_read); x->h_block = H + l.p_block; x->h_out = H + l.p_out;
+        ok = hipMemsetAsync(D, 0, l.dsize, x->stream) == hipSuccess
+          && hipMemcpyAsync(D + l.o_words, kWords, sizeof(kWords), hipMemcpyHostToDevice, x->stream) == hipSuccess;
     }
     x->h_qsize[0] = (uint32_t *)calloc(h.qslots, sizeof(uint32_t));
     x->h_qsize[1] = (uint32_t *)calloc(h.qslots, sizeof(uint32_t));
     ok = ok && x->h_qsize[0] && x->h_qsize[1];
     if (ok) {
-        h.p_delta = h.p_lit + 65536;
-        h.phase = DEC_PH_PRIME0;
         ok = hipMemcpyAsync(x->d_state, &h, sizeof(DecState), hipMemcpyHostToDevice, x->stream) == hipSuccess;
         if (ok) {
             launch_decode_init(x->d_state, x->stream);
@@ -399,6 +435,122 @@ int CSCMI_DecodeBatch(int n, CSCDecHandle *hs, ISeqOutStream *const *oss, int *r
     }
     (void)hipFree(d_list);
     (void)hipHostFree(h_list);
+    return dev_rc;
+}
+
+// Not in the reference: whole streams that lie in device memory decoded into device memory, n at once.  The block reader
+// (csc_dec_blocks.h) and the delivery of every run are in the kernel (k_decode_dev*), so a round is: the list of live streams up,
+// ONE launch, the small states back -- no payload and no run crosses the bus, and no callback is made.  A launch ends when its
+// stream does or after opts->launch_bytes of output (kDevLaunchBytes by default), which bounds kernel time; the host relaunches
+// what is still live.  jobs[i].rc / produced / dst are what CSCDec_Create + CSCDec_Decode give over a reader of src and a writer
+// that refuses the run which would pass dst_cap (include/csc_mi355x.h).
+int CSCMI_DecodeDeviceBatch(int n, CSCMIDevDecode *jobs, const CSCMIDevDecodeOpts *opts, CSCMIDevDecodeStats *stats)
+{
+    if (stats) { stats->launches = stats->rounds = 0; stats->kernel_ms = 0; }
+    if (n <= 0) return 0;
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return CSCMI_DEVICE_ERROR;
+    uint64_t budget64 = opts && opts->launch_bytes ? opts->launch_bytes : kDevLaunchBytes;
+    const uint32_t launch_budget = budget64 > 0x7FFFFFFFull ? 0x7FFFFFFFu : (uint32_t)budget64;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess) {
+        if (ev[0]) (void)hipEventDestroy(ev[0]);
+        return CSCMI_DEVICE_ERROR;
+    }
+    for (int i = 0; i < n; i++) { jobs[i].produced = 0; jobs[i].consumed = 0; jobs[i].rc = CSCMI_DEVICE_ERROR; }
+    struct Slot { int job; DecRes *res; DecState *d_state, *h_read; };
+    int dev_rc = 0, next = 0;
+    while (next < n && !dev_rc) {
+        // a group: as many of the remaining jobs as the free device memory (and what the resource cache holds) can carry
+        std::vector<Slot> grp;
+        size_t free_b = 0, total_b = 0, used = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { dev_rc = CSCMI_DEVICE_ERROR; break; }
+        const size_t room = (free_b + dec_cache_bytes()) / 8 * 7;
+        hipStream_t st = nullptr;
+        for (; next < n && grp.size() < kDevGroupMax && !dev_rc; next++) {
+            CSCMIDevDecode &job = jobs[next];
+            // where CSCDec_Create refuses before it reads (an empty source is its first read failing)
+            if (!dec_props_ok(&job.props) || job.src_size == 0 || job.src == NULL) { job.rc = CSCMI_NO_DECODER; continue; }
+            DecState h;
+            memset(&h, 0, sizeof(h));
+            const DecLayout l = dec_layout(&job.props, h);
+            if (!grp.empty() && used + l.dsize > room) break;
+            DecRes *r = dec_res_get(device, l.dsize, l.hsize);
+            if (!r) {
+                if (!grp.empty()) break;                     // this group first; the job is tried again with its memory back
+                fprintf(stderr, "csc-mi355x: decoder device allocation failed\n");
+                continue;                                      // (rc stays CSCMI_DEVICE_ERROR; the other jobs proceed)
+            }
+            used += l.dsize;
+            if (!st) st = r->stream;
+            uint8_t *D = r->dslab;
+            dec_place(h, D, l);
+            h.src = (const uint8_t *)job.src; h.src_size = job.src_size; h.src_pos = 0;
+            h.dst = (uint8_t *)job.dst; h.dst_cap = job.dst_cap; h.produced = 0;
+            h.launch_budget = launch_budget;
+            Slot s = {next, r, (DecState *)(D + l.o_state), (DecState *)(r->hslab + l.p_read)};
+            *s.h_read = h;                                     // (pinned: the upload below reads it when the stream gets there)
+            bool ok = hipMemsetAsync(D, 0, l.dsize, st) == hipSuccess
+                   && hipMemcpyAsync(D + l.o_words, kWords, sizeof(kWords), hipMemcpyHostToDevice, st) == hipSuccess
+                   && hipMemcpyAsync(s.d_state, s.h_read, sizeof(DecState), hipMemcpyHostToDevice, st) == hipSuccess;
+            if (ok) { launch_decode_init(s.d_state, st); ok = hipGetLastError() == hipSuccess; }
+            grp.push_back(s);
+            if (!ok) dev_rc = CSCMI_DEVICE_ERROR;
+        }
+        DecState **d_list = nullptr, **h_list = nullptr;
+        std::vector<size_t> live;
+        for (size_t k = 0; k < grp.size(); k++) live.push_back(k);
+        if (!grp.empty() && !dev_rc) {
+            if (hipMalloc((void **)&d_list, sizeof(DecState *) * grp.size()) != hipSuccess
+                || hipHostMalloc((void **)&h_list, sizeof(DecState *) * grp.size(), hipHostMallocDefault) != hipSuccess) dev_rc = CSCMI_DEVICE_ERROR;
+        }
+        while (!live.empty() && !dev_rc) {
+            for (size_t k = 0; k < live.size(); k++) h_list[k] = grp[live[k]].d_state;
+            bool ok = hipMemcpyAsync(d_list, h_list, sizeof(DecState *) * live.size(), hipMemcpyHostToDevice, st) == hipSuccess
+                   && hipEventRecord(ev[0], st) == hipSuccess;
+            if (ok) {
+                launch_decode_dev(d_list, h_list[0], (uint32_t)live.size(), st);
+                ok = hipGetLastError() == hipSuccess && hipEventRecord(ev[1], st) == hipSuccess;
+            }
+            for (size_t k = 0; k < live.size() && ok; k++) {
+                const Slot &s = grp[live[k]];
+                ok = hipMemcpyAsync(s.h_read, s.d_state, offsetof(DecState, probs), hipMemcpyDeviceToHost, st) == hipSuccess;
+            }
+            ok = ok && hipStreamSynchronize(st) == hipSuccess;
+            float ms = 0;
+            ok = ok && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
+            if (!ok) { dev_rc = CSCMI_DEVICE_ERROR; break; }
+            if (stats) { stats->launches++; stats->rounds++; stats->kernel_ms += ms; }
+#ifdef CSCMI_TIMERS
+            fprintf(stderr, "csc-mi355x: decode launch: %zu streams, %.3f ms\n", live.size(), ms);      // (development build only)
+#endif
+            std::vector<size_t> keep;
+            for (size_t k : live) {
+                const Slot &s = grp[k];
+                const DecState &r = *s.h_read;
+                CSCMIDevDecode &job = jobs[s.job];
+                job.produced = (size_t)r.produced;
+                job.consumed = (size_t)r.src_pos;
+                switch (r.status) {
+                case DEC_DONE: keep.push_back(k); break;                  // the launch budget: more to come
+                case DEC_END: job.rc = 0; break;
+                case DEC_ERR_MINUS1: job.rc = -1; break;
+                case DEC_ERR_READ: job.rc = READ_ERROR; break;
+                case DEC_ERR_WRITE: job.rc = WRITE_ERROR; break;
+                case DEC_NO_DECODER: job.rc = CSCMI_NO_DECODER; break;
+                default: job.rc = DECODE_ERROR;
+                }
+            }
+            live.swap(keep);
+        }
+        if (st) (void)hipStreamSynchronize(st);
+        if (d_list) (void)hipFree(d_list);
+        if (h_list) (void)hipHostFree(h_list);
+        for (const Slot &s : grp) dec_res_put(s.res);
+    }
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
     return dev_rc;
 }
 

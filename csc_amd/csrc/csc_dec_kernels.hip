@@ -11,10 +11,15 @@
 // current packet back (probability updates are journalled since the last checkpoint), stores its
 // state and returns NEED_RC / NEED_BC; the host reads blocks exactly like MemIO::ReadBlock would,
 // uploads them and relaunches.  The read pattern seen by the caller is the reference's.
+//
+// A stream that lies in device memory needs none of that: k_decode_dev* (CSCMI_DecodeDeviceBatch) instantiate the same state machine
+// with the block reader (csc_dec_blocks.h) and the delivery of each run inside -- where k_decode_run leaves for a block or with a
+// run, they fetch the block from DecState::src / copy the run to DecState::dst and go on.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "csc_device.h"
+#include "csc_dec_blocks.h"
 
 namespace cscmi {
 
@@ -956,6 +961,51 @@ DDEV bool dprime(Dc &c)
     return true;
 }
 
+// ---- device-resident decode (k_decode_dev*): the block reader and the delivery of a run, in the kernel --------------------------
+// MemIO::ReadBlock over DecState::src (csc_dec_blocks.h): blocks are read from the cursor until one of `kind` has arrived, each
+// payload copied lane-wide into the next slot of its own kind's ring (the ring's slack behind a payload -- the next slot, or the
+// 256 bytes behind the last one -- is what next_byte and the fast loop read past a block's end; `src` itself is never read in place:
+// nothing says that 64 bytes behind a block belong to the caller).  The header bytes are loaded as scalars, after a bounds test
+// each; a payload is touched only once all of it is known to lie inside [src, src + src_size).  Cursor and block counts live in
+// the DecState; true = a block of `kind` is queued.  A function of its own: see DNOINL above.
+DNOINL uint32_t d_read_block(gDecState *Dv, uint32_t kind_v, uint32_t taken0_v, uint32_t taken1_v)
+{
+    auto U64 = [](uint64_t v) { return ((uint64_t)DUNI((uint32_t)(v >> 32)) << 32) | DUNI((uint32_t)v); };
+    gDecState *const D = (gDecState *)U64((uint64_t)Dv);
+    const uint32_t lane = threadIdx.x & 63u, kind = DUNI(kind_v), taken0 = DUNI(taken0_v), taken1 = DUNI(taken1_v);
+    const dgu8 *const src = (const dgu8 *)U64((uint64_t)D->src);
+    dgu8 *const q0 = (dgu8 *)U64((uint64_t)D->q[0]), *const q1 = (dgu8 *)U64((uint64_t)D->q[1]);
+    dgu32 *const qs0 = (dgu32 *)U64((uint64_t)D->qsize[0]), *const qs1 = (dgu32 *)U64((uint64_t)D->qsize[1]);
+    const uint64_t src_size = U64(D->src_size);
+    uint64_t pos = U64(D->src_pos);
+    const uint32_t bsize = DUNI(D->bsize), qslots = DUNI(D->qslots);
+    uint32_t avail0 = DUNI(D->avail[0]), avail1 = DUNI(D->avail[1]);
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    const int rc = dec_read_block([&](uint64_t o) { return DUNI((uint32_t)src[o]); }, src_size, &pos, bsize, kind, qslots,
+                                  &avail0, &avail1, taken0, taken1,
+                                  [&](const DecBlock &b, uint32_t slot) {
+                                      dgu8 *to = (b.kind ? q1 : q0) + (size_t)slot * bsize;
+                                      const dgu8 *from = src + b.payload;
+                                      for (uint32_t t = lane; t < b.size; t += 64) to[t] = from[t];
+                                      (b.kind ? qs1 : qs0)[slot] = b.size;                  // (every lane the same word to the same place)
+                                  });
+    D->src_pos = pos; D->avail[0] = avail0; D->avail[1] = avail1;
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    return rc == 0 ? 1u : 0u;
+}
+// the decoded run to its place in the caller's buffer: lane-strided bytes, the destination has no alignment
+DNOINL void d_deliver(dgu8 *dst, const dgu8 *src, uint32_t n)
+{
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    for (uint32_t t = threadIdx.x & 63u; t < n; t += 64) dst[t] = src[t];
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+}
+
+// DEV = false: one Decompress call, left with DEC_NEED_RC / DEC_NEED_BC whenever a block is wanted that the host has not uploaded
+// (k_decode_run*).  DEV = true (k_decode_dev*): the same machine, but where it would leave for a block -- rolled back to its
+// checkpoint, `need` set -- d_read_block fetches it from DecState::src and the machine goes on; a completed call's run is copied to
+// DecState::dst and the next call starts, until the stream ends or this launch has delivered launch_budget bytes.
+template <bool DEV>
 DDEV void decode_stream(gDecState *D, DecLds &lds)
 {
     Dc c;
@@ -1001,6 +1051,14 @@ DDEV void decode_stream(gDecState *D, DecLds &lds)
     const uint32_t max = DUNI(D->raw_blocksize);
     Ck k;
     bool done = false;
+    uint64_t produced = 0, dst_cap = 0;
+    uint32_t launch_out = 0, launch_budget = 0;
+    dgu8 *dst = nullptr;
+    if (DEV) {
+        produced = U64(D->produced); dst_cap = U64(D->dst_cap); dst = (dgu8 *)U64((uint64_t)D->dst);
+        launch_budget = DUNI(D->launch_budget);
+    }
+    for (;;) {
     while (!done && !c.need && c.status == DEC_RUNNING) {
         switch (c.phase) {
         case DEC_PH_PRIME0:
@@ -1084,6 +1142,29 @@ DDEV void decode_stream(gDecState *D, DecLds &lds)
             c.status = DEC_ERR_DECODE;
         }
     }
+    if (!DEV || c.status != DEC_RUNNING) break;
+    if (c.need) {
+        // every place that sets `need` has put the machine back to its checkpoint: fetch the block, go on from there
+        // (CSCDec_Create reads the first two blocks: csc_dec.cpp:336-337; a re-prime that finds none: :669-671; elsewhere :17-18)
+        if (!DUNI(d_read_block(D, c.need == DEC_NEED_RC ? 1u : 0u, c.taken[0], c.taken[1]))) {
+            c.status = c.phase == DEC_PH_PRIME0 ? DEC_NO_DECODER : c.phase == DEC_PH_PRIME ? DEC_ERR_MINUS1 : DEC_ERR_READ;
+            break;
+        }
+        c.avail[0] = DUNI(D->avail[0]); c.avail[1] = DUNI(D->avail[1]);
+        c.need = 0;
+        continue;
+    }
+    // a Decompress call is complete: CSCDec_Decode's loop body (csc_dec.cpp:755-771) with a Write that takes a run whole or not at all
+    done = false;
+    c.woff[0] = c.woff[1] = 64;          // (a re-prime has moved on to new blocks: the byte windows are refetched, as at a launch's start)
+    const uint32_t size = c.out_size;
+    if (size == 0) { c.status = DEC_END; break; }
+    if (size > dst_cap - produced) { c.status = DEC_ERR_WRITE; break; }
+    d_deliver(dst + produced, c.out, size);
+    produced += size;
+    launch_out += size;
+    if (launch_out >= launch_budget) break;
+    }
     // store the stream state
     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
     for (uint32_t i = c.lane; i < P_COUNT; i += 64) D->probs[i] = lds.P[i];
@@ -1104,13 +1185,14 @@ DDEV void decode_stream(gDecState *D, DecLds &lds)
         D->phase = c.phase; D->type = c.type; D->run_size = c.run_size; D->i = c.i; D->copied = c.copied; D->copied_from = c.copied_from;
         D->out_size = c.out_size; D->p_delta_ready = c.p_delta_ready;
         D->status = c.status != DEC_RUNNING ? c.status : (c.need ? c.need : DEC_DONE);
+        if (DEV) { D->produced = produced; D->launch_out = launch_out; }
     }
 }
 
 // one stream: CSCDec_Decode
 __global__ __launch_bounds__(64) void k_decode_run(DecState *D)
 {
-    decode_stream((gDecState *)D, g_dec_lds);
+    decode_stream<false>((gDecState *)D, g_dec_lds);
 }
 // many independent streams (the tasks of an archive): workgroup b advances stream b until it needs input or its
 // Decompress call is complete; one stream per CU (the literal table fills most of the LDS)
@@ -1119,7 +1201,19 @@ __global__ __launch_bounds__(64) void k_decode_run_multi(DecState *const *states
     // the pointer is the same in every lane; say so, or everything loaded through it is treated as per-lane data
     const uint64_t a = (uint64_t)states[blockIdx.x];
     const uint64_t u = ((uint64_t)DUNI((uint32_t)(a >> 32)) << 32) | DUNI((uint32_t)a);
-    decode_stream((gDecState *)u, g_dec_lds);
+    decode_stream<false>((gDecState *)u, g_dec_lds);
+}
+// The device-resident forms (CSCMI_DecodeDeviceBatch): the stream is read from DecState::src and its runs go to DecState::dst, both
+// in HBM; a launch ends with the stream or once it has delivered DecState::launch_budget bytes, not at a block or a run.
+__global__ __launch_bounds__(64) void k_decode_dev(DecState *D)
+{
+    decode_stream<true>((gDecState *)D, g_dec_lds);
+}
+__global__ __launch_bounds__(64) void k_decode_dev_multi(DecState *const *states)
+{
+    const uint64_t a = (uint64_t)states[blockIdx.x];
+    const uint64_t u = ((uint64_t)DUNI((uint32_t)(a >> 32)) << 32) | DUNI((uint32_t)a);
+    decode_stream<true>((gDecState *)u, g_dec_lds);
 }
 
 __global__ void k_decode_init(DecState *D)
@@ -1137,6 +1231,11 @@ void launch_decode_run(DecState *D, hipStream_t st)
 void launch_decode_run_multi(DecState *const *states, uint32_t n, hipStream_t st)
 {
     hipLaunchKernelGGL(k_decode_run_multi, dim3(n), dim3(64), 0, st, states);
+}
+void launch_decode_dev(DecState *const *states, DecState *first, uint32_t n, hipStream_t st)
+{
+    if (n == 1) hipLaunchKernelGGL(k_decode_dev, dim3(1), dim3(64), 0, st, first);
+    else hipLaunchKernelGGL(k_decode_dev_multi, dim3(n), dim3(64), 0, st, states);
 }
 
 }  // namespace cscmi

@@ -112,6 +112,39 @@ int CSCMI_FlushBatch(int n, CSCEncHandle *hs);
  * workgroup each); block reads and Write calls happen on the calling thread, per stream in the order CSCDec_Decode
  * would make them.  rcs[i] = what CSCDec_Decode(hs[i], oss[i], NULL) would return.  Returns 0 or CSCMI_DEVICE_ERROR. */
 int CSCMI_DecodeBatch(int n, CSCDecHandle *hs, ISeqOutStream *const *oss, int *rcs);
+/* Device-resident decode: n whole streams that lie in device memory, decoded into device memory.  The block reader and the
+ * delivery of the decoded runs are inside the kernel: no payload and no run crosses the bus, no callback is made, and a launch
+ * does not end at a coder block.  One-shot: per-stream state comes from the decoder's resource cache and goes back to it; any
+ * n >= 0, in groups sized to the free device memory; launches go to the library's pooled stream and the call returns when all
+ * jobs have their answer.
+ *
+ * jobs[i].rc and dst[0 .. produced) are exactly what CSCDec_Create + CSCDec_Decode give over an ISeqInStream that serves
+ * src[0 .. src_size) with full-size reads and an ISeqOutStream that accepts a Write only while the total stays <= dst_cap and
+ * returns a short count otherwise:
+ *   rc        0, -1, DECODE_ERROR, READ_ERROR or WRITE_ERROR as CSCDec_Decode returns them; CSCMI_NO_DECODER where CSCDec_Create
+ *             would have returned NULL for this stream (illegal props, or the first RC or BC block missing or cut);
+ *             CSCMI_DEVICE_ERROR if this job could not get its device memory (the other jobs proceed)
+ *   dst       a run that does not fit in dst_cap is not delivered at all and ends the stream with WRITE_ERROR; the LIMIT above
+ *             (a packet of more than 32 768 model bits) keeps its DECODE_ERROR; bytes of src behind the end-of-stream signal are
+ *             ignored; nothing outside [src, src + src_size) is loaded and nothing outside [dst, dst + dst_cap) is stored
+ * Returns 0, or CSCMI_DEVICE_ERROR if the GPU side failed or no device is visible; without a visible device no field of any
+ * job is touched.  opts and stats may be NULL; one launch is made per host round, so stats->rounds == stats->launches.
+ * Where the two differ, the answer is the REFERENCE's, not this library's CSCDec_Create: for a stream whose first block is a
+ * bit-coder block the reference (and this call) takes it from the queue, while CSCDec_Create here always reads on for a second. */
+#define CSCMI_NO_DECODER (-92)   /* where CSCDec_Create would have returned NULL for this stream */
+typedef struct {
+    CSCProps props;          /* in: as CSCDec_ReadProperties gives them (host memory) */
+    const void *src;         /* in: device pointer, the stream AFTER its 10 property bytes; any alignment */
+    size_t src_size;
+    void *dst;               /* in: device pointer, any alignment; must not overlap src */
+    size_t dst_cap;
+    size_t produced;         /* out: bytes written to dst */
+    size_t consumed;         /* out: bytes of src the block reader took (defined when rc == 0) */
+    int rc;                  /* out */
+} CSCMIDevDecode;
+typedef struct { uint64_t launch_bytes; } CSCMIDevDecodeOpts;   /* output per stream after which a launch returns; 0 = the library's default (4 MiB) */
+typedef struct { uint64_t launches, rounds; double kernel_ms; } CSCMIDevDecodeStats;   /* kernel launches, host rounds, HIP-event time of the launches */
+int CSCMI_DecodeDeviceBatch(int n, CSCMIDevDecode *jobs, const CSCMIDevDecodeOpts *opts, CSCMIDevDecodeStats *stats);
 /* Host-memory variant used by CSCEnc_Encode itself. */
 int CSCMI_EncodeHostChunk(CSCEncHandle p, const void *host_ptr, size_t size);
 void CSCMI_GetStats(CSCEncHandle p, CSCMIStats *out);
