@@ -24,6 +24,7 @@
 
 #include "../../include/csc_mi355x.h"
 #include "csc_device.h"
+#include "csc_tables.h"
 
 namespace cscmi {
 void launch_decode_init(DecState *D, hipStream_t st);
@@ -42,17 +43,6 @@ constexpr uint32_t kMagicDec = 0x43534344;   // "CSCD"
 void *def_alloc(void *, size_t n) { return malloc(n); }
 void def_free(void *, void *a) { free(a); }
 ISzAlloc g_default_alloc = {def_alloc, def_free};
-
-const char kWords[122][8] = {   // csc_filters.cpp:8-38; symbol 0x82+i expands to kWords[i]
-    "ac","ad","ai","al","am","an","ar","as","at","ea","ec","ed","ee","el","en","er","es","et","id","ie",
-    "ig","il","in","io","is","it","of","ol","on","oo","or","os","ou","ow","ul","un","ur","us","ba","be",
-    "ca","ce","co","ch","de","di","ge","gh","ha","he","hi","ho","ra","re","ri","ro","rs","la","le","li",
-    "lo","ld","ll","ly","se","si","so","sh","ss","st","ma","me","mi","ne","nc","nd","ng","nt","pa","pe",
-    "ta","te","ti","to","th","tr","wa","ve",
-    "all","and","but","dow","for","had","hav","her","him","his","man","mor","not","now","one","out",
-    "she","the","was","wer","whi","whe","wit","you","any","are",
-    "that","said","with","have","this","from","were","tion",
-};
 
 // A decoder's device state is ONE allocation (zero-filled on every use) and its pinned staging ONE allocation;
 // both, and the HIP stream, are recycled through a per-process cache keyed by (device, sizes): an archive reader

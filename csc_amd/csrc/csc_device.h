@@ -101,7 +101,6 @@ struct EncState {
     const uint16_t *trie_next; // [300*26] word trie, csc_filters.cpp:87-111
     const uint8_t *trie_sym;   // [300]
     BlockInfo *binfo;          // [kMaxBlocksPerChunk]
-    uint32_t *dup_flags;       // [kMaxBlocksPerChunk] IsDuplicateBlock results
 
     // ---- dynamic scalar state carried between launches ----
     uint32_t pos, bt_pos, wnd_curpos, p_delta_ready;

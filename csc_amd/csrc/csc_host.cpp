@@ -3,12 +3,10 @@
 //
 // What stays on the host (SURVEY.md section 3.1 puts the device boundary inside
 // CSCEncoder::Compress): the user callbacks (always on the calling thread), the 2 MiB read loop
-// (csc_enc.cpp:160-191), the run segmentation over the analyzer's per-block verdicts
-// (csc_encoder_main.cpp:85-147 -- a few integer compares per 8 KiB block plus the one
-// `>= bpb * 0.95` double compare) and the RC/BC block framing (csc_memio.cpp:83-108).  Everything
-// that touches the data -- analyzer, filters, match finder, parser, model, range/bit coder -- runs
-// in HIP kernels on state that lives in HBM.  There is NO CPU fallback: without a HIP device
-// CSCEnc_Create fails loudly and returns NULL.
+// (csc_enc.cpp:160-191) and the RC/BC block framing (csc_memio.cpp:83-108).  Everything that
+// touches the data -- analyzer, run segmentation over its per-block verdicts, filters, match
+// finder, parser, model, range/bit coder -- runs in HIP kernels on state that lives in HBM.
+// There is NO CPU fallback: without a HIP device CSCEnc_Create fails loudly and returns NULL.
 #include <hip/hip_runtime.h>
 #include <chrono>
 
@@ -22,12 +20,12 @@
 
 #include "../../include/csc_mi355x.h"
 #include "csc_device.h"
+#include "csc_tables.h"
 
 namespace cscmi {
 hipError_t upload_tables();
 void launch_init_state(EncState *S, hipStream_t st);
 void launch_analyze(EncState *S, uint32_t chunk_size, const double *ent_coef, hipStream_t st);
-void launch_dup_check(EncState *S, uint32_t chunk_size, uint32_t first, uint32_t count, hipStream_t st);
 void launch_encode_runs(int parser, EncState *S, const RunDesc *runs, uint32_t nruns, uint32_t reset_arena, hipStream_t st);
 void launch_encode_eof(EncState *S, hipStream_t st);
 void launch_encode_runs_multi(int parser, uint32_t nstreams, EncState *const *states, const RunDesc *const *runs,
@@ -44,7 +42,6 @@ using namespace cscmi;
 namespace {
 
 constexpr uint32_t kMagicEnc = 0x43534345;           // "CSCE"
-constexpr int kEventPairs = 32;
 
 void *def_alloc(void *, size_t n) { return malloc(n); }   // csc_default_alloc.cpp:5-17
 void def_free(void *, void *a) { free(a); }
@@ -59,18 +56,6 @@ ISzAlloc g_default_alloc = {def_alloc, def_free};
             return CSCMI_DEVICE_ERROR;                                                            \
         }                                                                                         \
     } while (0)
-
-// the 122 words of the dictionary filter -- data the stream format is defined by (csc_filters.cpp:8-38)
-const char *const kWords[122] = {
-    "ac","ad","ai","al","am","an","ar","as","at","ea","ec","ed","ee","el","en","er","es","et","id","ie",
-    "ig","il","in","io","is","it","of","ol","on","oo","or","os","ou","ow","ul","un","ur","us","ba","be",
-    "ca","ce","co","ch","de","di","ge","gh","ha","he","hi","ho","ra","re","ri","ro","rs","la","le","li",
-    "lo","ld","ll","ly","se","si","so","sh","ss","st","ma","me","mi","ne","nc","nd","ng","nt","pa","pe",
-    "ta","te","ti","to","th","tr","wa","ve",
-    "all","and","but","dow","for","had","hav","her","him","his","man","mor","not","now","one","out",
-    "she","the","was","wer","whi","whe","wit","you","any","are",
-    "that","said","with","have","this","from","were","tion",
-};
 
 // Filters::MakeWordTree, csc_filters.cpp:87-111: node numbering follows insertion order
 void build_trie(uint16_t *next, uint8_t *sym)
@@ -92,7 +77,7 @@ void build_trie(uint16_t *next, uint8_t *sym)
 
 
 // Per-handle resources that do not depend on the stream's content are recycled: creating a handle
-// costs a pinned allocation, a stream and ~70 events otherwise, and an archive job creates one handle
+// costs a pinned allocation, a stream and four events otherwise, and an archive job creates one handle
 // per task (hundreds).  HostRes = pinned staging slab + HIP stream + events, keyed by (device, size);
 // DevSlab = the ONE device allocation all of a handle's HBM state is carved from, keyed by
 // (device, size) and zero-filled again on every reuse (the reference's determinism condition).
@@ -102,7 +87,7 @@ struct HostRes {
     uint8_t *hslab;
     uint8_t *h_in;              // lazily allocated: only CSCEnc_Encode / CSCMI_EncodeHostChunk stage input on the host
     hipStream_t stream;
-    hipEvent_t ev[32][2];       // created on first use (host_events): a handle that is only ever driven through a batch launch records none
+    hipEvent_t ev[2];           // created on first use (host_events): a handle that is only ever driven through a batch launch records none
     hipEvent_t ev_an[2];
     bool have_events;
 };
@@ -112,7 +97,7 @@ std::mutex g_cache_mu;
 std::vector<HostRes *> g_host_cache;
 std::vector<DevSlab> g_dev_cache;
 size_t g_dev_cache_bytes = 0;
-constexpr size_t kHostCacheMax = 4096;            // entries (~90 KiB pinned each; coder blocks are read back through the calling thread's buffer, thread_pinned)
+constexpr size_t kHostCacheMax = 4096;            // entries (256 B pinned each; coder blocks are read back through the calling thread's buffer, thread_pinned)
 constexpr size_t kDevCacheMaxBytes = 48ull << 30;
 
 }  // namespace
@@ -161,7 +146,7 @@ void host_res_destroy(HostRes *r)
     if (!r) return;
     if (r->hslab) (void)hipHostFree(r->hslab);
     if (r->h_in) (void)hipHostFree(r->h_in);
-    for (auto &pr : r->ev) for (auto &e : pr) if (e) (void)hipEventDestroy(e);
+    for (auto &e : r->ev) if (e) (void)hipEventDestroy(e);
     for (auto &e : r->ev_an) if (e) (void)hipEventDestroy(e);
     if (r->stream) pooled_stream_release(r->device, r->stream);
     delete r;
@@ -194,7 +179,7 @@ HostRes *host_res_get(int device, size_t hsize)
 hipError_t host_events(HostRes *r)
 {
     if (r->have_events) return hipSuccess;
-    for (auto &pr : r->ev) for (auto &e : pr) if (!e) { hipError_t err = hipEventCreate(&e); if (err != hipSuccess) return err; }
+    for (auto &e : r->ev) if (!e) { hipError_t err = hipEventCreate(&e); if (err != hipSuccess) return err; }
     for (auto &e : r->ev_an) if (!e) { hipError_t err = hipEventCreate(&e); if (err != hipSuccess) return err; }
     r->have_events = true;
     return hipSuccess;
@@ -294,35 +279,23 @@ struct EncInstance {
     hipStream_t stream;
     EncState *d_state;
     EncState h;                 // host mirror of the configuration + device pointers
-    RunDesc *d_runs;
     double *d_entcoef;
     uint8_t *d_trie;            // next (u16[7800]) + sym (u8[300])
+#ifdef CSCMI_STAGE_TEST
+    uint32_t *d_result;         // CSCST_Filter's result word
+#endif
     void *dslab;                // everything above and in `h` is carved from this one allocation
     size_t dsize;
     HostRes *res;               // stream, events and the pinned slab the pointers below point into
     // pinned staging
     uint8_t *h_in;
-    BlockInfo *h_binfo;
-    RunDesc *h_runs;
-    uint32_t *h_dup;
     uint32_t *h_small;
-    hipEvent_t (*ev)[2];        // res->ev
+    hipEvent_t *ev;             // res->ev
     hipEvent_t *ev_an;          // res->ev_an
     // accounting
     int64_t outsize;            // GetCompressedSize, csc_encoder_main.cpp:174
     CSCMIStats stats;
     int parser;
-    // a chunk whose final launch is deferred to a batch launch (CSCMI_EncodeDeviceChunkBatch)
-    uint32_t pend_a, pend_b;
-    bool pend_first;
-    int pend_ev;
-    // the run segmentation of the chunk in hand, resumable (seg_advance): it stops where LZ::IsDuplicateBlock must look at the tables
-    // as the runs so far leave them (csc_encoder_main.cpp:123-126), so that a batch of streams can take that step together
-    struct Seg {
-        uint32_t nruns, launched, last_type, last_begin, last_size, bpb, dup_from, dup_to, blk, i, need_blk, need_cnt;
-        bool first_launch;
-        int ev_used;
-    } seg;
 };
 // Per-thread resources, recycled through process-wide free lists: a thread that ends hands them back (its thread_local holder's
 // destructor makes no HIP call -- it may run while the runtime shuts down), the next thread that needs one takes it over.  So
@@ -334,7 +307,7 @@ struct EncInstance {
 //    reset flags), one set per calling thread and device, + the {bytes, error} pair of every stream of a batch.
 struct PinBuf { uint8_t *p = nullptr; size_t cap = 0; };
 struct BatchArgs {
-    int device = -1; void **d = nullptr; void **h = nullptr; void **d2 = nullptr; void **h2 = nullptr; hipStream_t side = nullptr;
+    int device = -1; void **d = nullptr; void **h = nullptr;
     uint32_t *small = nullptr;
 };
 std::mutex g_thread_res_mu;
@@ -409,21 +382,6 @@ int write_block(EncInstance *e, const uint8_t *buf, uint32_t size, uint32_t rc1b
     return 0;
 }
 
-// launch [a, b) of the chunk's run list
-int launch_runs(EncInstance *e, uint32_t a, uint32_t b, bool &first_launch, int &ev_used)
-{
-    if (a == b) return 0;
-    HIPCHK(hipMemcpyAsync(e->d_runs + a, e->h_runs + a, sizeof(RunDesc) * (b - a), hipMemcpyHostToDevice, e->stream));
-    bool timed = ev_used < kEventPairs;
-    if (timed) HIPCHK(hipEventRecord(e->ev[ev_used][0], e->stream));
-    launch_encode_runs(e->parser, e->d_state, e->d_runs + a, b - a, first_launch ? 1u : 0u, e->stream);
-    HIPCHK(hipGetLastError());
-    if (timed) { HIPCHK(hipEventRecord(e->ev[ev_used][1], e->stream)); ev_used++; }
-    e->stats.encode_launches++;
-    first_launch = false;
-    return 0;
-}
-
 // hand the coder blocks of one chunk (a host copy of the stream's arena) to the user's stream, in the order they were finished
 int write_arena(EncInstance *e, const uint8_t *h_arena, uint32_t used)
 {
@@ -446,14 +404,12 @@ int report_device_error(uint32_t err)
 }
 
 // read the finished coder blocks of this chunk back and hand them to the user's stream
-int drain_arena(EncInstance *e, int ev_used)
+int drain_arena(EncInstance *e, bool timed)
 {
     HIPCHK(hipMemcpyAsync(e->h_small, &e->d_state->arena_used, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
-    for (int i = 0; i < ev_used; i++) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, e->ev[i][0], e->ev[i][1]) == hipSuccess) e->stats.encode_kernel_ms += ms;
-    }
+    float ms = 0;
+    if (timed && hipEventElapsedTime(&ms, e->ev[0], e->ev[1]) == hipSuccess) e->stats.encode_kernel_ms += ms;
     uint32_t used = e->h_small[0], err = e->h_small[1];
     if (err != ERR_NONE) return report_device_error(err);
     uint8_t *pin = nullptr;
@@ -466,149 +422,23 @@ int drain_arena(EncInstance *e, int ev_used)
     return write_arena(e, pin, used);
 }
 
-// CSCEncoder::Compress, csc_encoder_main.cpp:85-147, with the data work on the device.
-// Three stages so that many handles can be driven through one multi-stream launch:
-//   chunk_begin   upload the chunk, launch the analyzer, start the verdict read-back (no wait)
-//   chunk_segment wait for the verdicts, build the run list (may launch + wait for duplicate-block
-//                 checks), then either launch the remaining runs or leave them pending
-//   chunk_finish  read the coder blocks back and call the user's Write
-// The chunk's blocks are walked by the encode kernel itself (enc_compress_chunk, csc_kernels_blocks.inc): typing, duplicate-block
-// checks and run formation need no host round trip.  CSCMI_HOST_SEGMENT=1 (diagnostics) keeps the walk on the host as rounds
-// 1-3 had it: the run list is built here, every IsDuplicateBlock verdict costs a launch boundary.
-bool host_segment()
-{
-    static const bool v = [] { const char *s = getenv("CSCMI_HOST_SEGMENT"); return s && atoi(s) != 0; }();
-    return v;
-}
-
+// CSCEncoder::Compress, csc_encoder_main.cpp:85-147, with the data work on the device: chunk_begin uploads the chunk and
+// launches the analyzer (no wait), then ONE encode launch per chunk.  The chunk's blocks are walked by the encode kernel itself
+// (seg_next, csc_kernels_blocks.inc): typing, duplicate-block checks and run formation need no host round trip.
 int chunk_begin(EncInstance *e, const void *src, size_t size, bool on_device, hipStream_t st = nullptr)
 {
     if (size == 0 || size > e->props.raw_blocksize) return -1;
     HIPCHK(hipSetDevice(e->device));
     const bool timed = st == nullptr;                // (a batch queues every stream's analyzer on the lead's stream: not timed one by one)
     if (!st) st = e->stream;
-    if (!host_segment()) {
-        HIPCHK(hipMemcpyAsync(e->h.inbuf, src, size, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
-        if ((e->props.DLTFilter + e->props.EXEFilter + e->props.TXTFilter) != 0) {
-            if (timed) HIPCHK(hipEventRecord(e->ev_an[0], st));
-            launch_analyze(e->d_state, (uint32_t)size, e->d_entcoef, st);
-            HIPCHK(hipGetLastError());
-            if (timed) HIPCHK(hipEventRecord(e->ev_an[1], st));
-        }
-        return 0;
-    }
-    HIPCHK(hipMemcpyAsync(e->h.inbuf, src, size, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, e->stream));
-    const uint32_t csize = (uint32_t)size;
-    const uint32_t nblk = (csize + kMinBlock - 1) / kMinBlock;
-    const bool use_filters = (e->props.DLTFilter + e->props.EXEFilter + e->props.TXTFilter) != 0;   // csc_encoder_main.cpp:27-31
-    if (use_filters) {
-        HIPCHK(hipEventRecord(e->ev_an[0], e->stream));
-        launch_analyze(e->d_state, csize, e->d_entcoef, e->stream);
+    HIPCHK(hipMemcpyAsync(e->h.inbuf, src, size, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, st));
+    if ((e->props.DLTFilter + e->props.EXEFilter + e->props.TXTFilter) != 0) {   // csc_encoder_main.cpp:27-31
+        if (timed) HIPCHK(hipEventRecord(e->ev_an[0], st));
+        launch_analyze(e->d_state, (uint32_t)size, e->d_entcoef, st);
         HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e->ev_an[1], e->stream));
-        HIPCHK(hipMemcpyAsync(e->h_binfo, e->h.binfo, sizeof(BlockInfo) * nblk, hipMemcpyDeviceToHost, e->stream));
+        if (timed) HIPCHK(hipEventRecord(e->ev_an[1], st));
     }
     return 0;
-}
-
-// start the segmentation of the chunk chunk_begin has uploaded: waits for the analyzer's verdicts
-int seg_begin(EncInstance *e)
-{
-    const bool use_filters = (e->props.DLTFilter + e->props.EXEFilter + e->props.TXTFilter) != 0;
-    HIPCHK(hipStreamSynchronize(e->stream));
-    if (use_filters) {
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, e->ev_an[0], e->ev_an[1]) == hipSuccess) e->stats.analyze_kernel_ms += ms;
-    }
-    EncInstance::Seg &g = e->seg;
-    g = EncInstance::Seg();
-    g.first_launch = true;
-    g.last_type = DT_NORMAL;
-    return 0;
-}
-
-// Walk the chunk's blocks on (CSCEncoder::Compress, csc_encoder_main.cpp:85-147).  Returns 1 when block g.need_blk (and the
-// g.need_cnt - 1 blocks behind it that may need the same) must be tested by IsDuplicateBlock against the tables as the runs
-// [g.launched, g.nruns) leave them: the caller launches those runs, then k_dup_check, reads the flags back (h_dup), sets
-// g.launched = g.nruns, g.dup_from / g.dup_to, and calls again.  Returns 0 when the run list is complete.
-int seg_advance(EncInstance *e, size_t size)
-{
-    EncInstance::Seg &g = e->seg;
-    const uint32_t csize = (uint32_t)size;
-    const uint32_t nblk = (csize + kMinBlock - 1) / kMinBlock;
-    const bool use_filters = (e->props.DLTFilter + e->props.EXEFilter + e->props.TXTFilter) != 0;
-    auto close_run = [&](uint32_t tail) {
-        RunDesc &r = e->h_runs[g.nruns++];
-        r.type = g.last_type; r.offset = g.last_begin; r.size = g.last_size; r.tail = tail;
-    };
-    while (g.i < csize) {
-        const uint32_t blk = g.blk;
-        uint32_t cur = csize - g.i < kMinBlock ? csize - g.i : kMinBlock;
-        uint32_t this_type = DT_NORMAL;
-        const BlockInfo *bi = use_filters ? &e->h_binfo[blk] : nullptr;
-        uint32_t bpb = g.bpb;
-        if (use_filters) {
-            this_type = bi->type;
-            if (this_type != DT_SKIP) bpb = bi->bpb;
-        }
-        if (this_type == DT_SKIP) this_type = g.last_type;
-        if (this_type != DT_NORMAL) {
-            if (this_type == DT_EXE && e->props.EXEFilter == 0) this_type = DT_NORMAL;
-            else if (this_type == DT_ENGTXT && e->props.TXTFilter == 0) this_type = DT_NORMAL;
-            else if (this_type >= DT_DLT && e->props.DLTFilter == 0) this_type = DT_NORMAL;
-        }
-        if (this_type >= DT_DLT && (double)bi->dlt_bpb[this_type - DT_DLT] >= bpb * 0.95)   // :117-121
-            this_type = DT_NORMAL;
-        if (this_type >= DT_NO_LZ) {   // :123-126 LZ::IsDuplicateBlock against the tables as of the pending run
-            if (!(g.launched == g.nruns && blk >= g.dup_from && blk < g.dup_to)) {
-                uint32_t cnt = 1;   // test the whole stretch of blocks that may need it under this state
-                while (blk + cnt < nblk && (e->h_binfo[blk + cnt].type >= DT_NO_LZ)) cnt++;
-                g.need_blk = blk; g.need_cnt = cnt;
-                return 1;           // (nothing of this block has been committed: the walk resumes at it)
-            }
-            if (e->h_dup[blk]) this_type = DT_NORMAL;
-        }
-        g.bpb = bpb;
-        if (g.last_type != this_type || g.last_size + cur > e->props.raw_blocksize) {
-            if (g.last_size) close_run(0);
-            g.last_begin = g.i;
-            g.last_size = 0;
-        }
-        g.last_type = this_type;
-        g.last_size += cur;
-        g.i += cur;
-        g.blk++;
-    }
-    if (g.last_size) { close_run(1); g.last_size = 0; }
-    return 0;
-}
-
-int chunk_segment(EncInstance *e, size_t size, bool defer_final)
-{
-    int rc = seg_begin(e);
-    if (rc) return rc;
-    EncInstance::Seg &g = e->seg;
-    const uint32_t csize = (uint32_t)size;
-    while ((rc = seg_advance(e, size)) == 1) {
-        rc = launch_runs(e, g.launched, g.nruns, g.first_launch, g.ev_used);
-        if (rc) return rc;
-        g.launched = g.nruns;
-        launch_dup_check(e->d_state, csize, g.need_blk, g.need_cnt, e->stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(e->h_dup + g.need_blk, e->h.dup_flags + g.need_blk, sizeof(uint32_t) * g.need_cnt, hipMemcpyDeviceToHost, e->stream));
-        HIPCHK(hipStreamSynchronize(e->stream));
-        g.dup_from = g.need_blk; g.dup_to = g.need_blk + g.need_cnt;
-    }
-    if (rc < 0) return rc;
-    e->stats.chunks++;
-    e->stats.input_bytes += size;
-    if (defer_final) {
-        e->pend_a = g.launched; e->pend_b = g.nruns; e->pend_first = g.first_launch; e->pend_ev = g.ev_used;
-        return 0;
-    }
-    rc = launch_runs(e, g.launched, g.nruns, g.first_launch, g.ev_used);
-    e->pend_ev = g.ev_used;
-    return rc;
 }
 
 int encode_chunk(EncInstance *e, const void *src, size_t size, bool on_device)
@@ -618,23 +448,18 @@ int encode_chunk(EncInstance *e, const void *src, size_t size, bool on_device)
     HIPCHK(host_events(e->res));
     int rc = chunk_begin(e, src, size, on_device);
     if (rc) return rc;
-    if (!host_segment()) {
-        HIPCHK(hipEventRecord(e->ev[0][0], e->stream));
-        launch_encode_runs(e->parser, e->d_state, e->d_runs, kSelfSegment | (uint32_t)size, 1u, e->stream);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(e->ev[0][1], e->stream));
-        e->stats.encode_launches++;
-        e->stats.chunks++;
-        e->stats.input_bytes += size;
-        rc = drain_arena(e, 1);
-        float ms = 0;
-        if ((e->props.DLTFilter + e->props.EXEFilter + e->props.TXTFilter) != 0 && hipEventElapsedTime(&ms, e->ev_an[0], e->ev_an[1]) == hipSuccess)
-            e->stats.analyze_kernel_ms += ms;
-        return rc;
-    }
-    rc = chunk_segment(e, size, false);
-    if (rc) return rc;
-    return drain_arena(e, e->pend_ev);
+    HIPCHK(hipEventRecord(e->ev[0], e->stream));
+    launch_encode_runs(e->parser, e->d_state, nullptr, kSelfSegment | (uint32_t)size, 1u, e->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(e->ev[1], e->stream));
+    e->stats.encode_launches++;
+    e->stats.chunks++;
+    e->stats.input_bytes += size;
+    rc = drain_arena(e, true);
+    float ms = 0;
+    if ((e->props.DLTFilter + e->props.EXEFilter + e->props.TXTFilter) != 0 && hipEventElapsedTime(&ms, e->ev_an[0], e->ev_an[1]) == hipSuccess)
+        e->stats.analyze_kernel_ms += ms;
+    return rc;
 }
 
 // the calling thread's launch tables + read-back pool, on `device`
@@ -652,18 +477,12 @@ int batch_args_ready(int device)
         fprintf(stderr, "csc-mi355x: batch tables: %s\n", hipGetErrorString(err));
         if (b.d) (void)hipFree(b.d);
         if (b.h) (void)hipHostFree(b.h);
-        if (b.d2) (void)hipFree(b.d2);
-        if (b.h2) (void)hipHostFree(b.h2);
-        if (b.side) (void)hipStreamDestroy(b.side);
         if (b.small) (void)hipHostFree(b.small);
         return CSCMI_DEVICE_ERROR;
     };
     hipError_t err;
     if ((err = hipMalloc((void **)&b.d, sizeof(void *) * 4 * kMaxBatch)) != hipSuccess) return fail(err);
     if ((err = hipHostMalloc((void **)&b.h, sizeof(void *) * 4 * kMaxBatch, hipHostMallocDefault)) != hipSuccess) return fail(err);
-    if ((err = hipMalloc((void **)&b.d2, sizeof(void *) * 4 * kMaxBatch)) != hipSuccess) return fail(err);
-    if ((err = hipHostMalloc((void **)&b.h2, sizeof(void *) * 4 * kMaxBatch, hipHostMallocDefault)) != hipSuccess) return fail(err);
-    if ((err = hipStreamCreateWithFlags(&b.side, hipStreamNonBlocking)) != hipSuccess) return fail(err);
     if ((err = hipHostMalloc((void **)&b.small, sizeof(uint32_t) * 2 * kMaxBatch, hipHostMallocDefault)) != hipSuccess) return fail(err);
     b.device = device;
     t_batch = b;
@@ -858,16 +677,15 @@ CSCEncHandle CSCEnc_Create(const CSCProps *props, ISeqOutStream *outstream, ISzA
     const size_t o_rc = dtake((size_t)h.bsize + 64), o_bc = dtake((size_t)h.bsize + 64);
     const size_t o_in = dtake((size_t)h.raw_blocksize + 256), o_swap = dtake(4 * (size_t)h.raw_blocksize + 512);
     const size_t o_arena = dtake((size_t)h.arena_cap + 64), o_binfo = dtake(sizeof(BlockInfo) * kMaxBlocksPerChunk);
-    const size_t o_dup = dtake(sizeof(uint32_t) * kMaxBlocksPerChunk);
-    const size_t o_runs = dtake(sizeof(RunDesc) * (kMaxBlocksPerChunk + 2));
+#ifdef CSCMI_STAGE_TEST
+    const size_t o_result = dtake(256);                                 // CSCST_Filter's result word
+#endif
     const size_t o_undo = dtake(h.bt_bits ? kBtUndoBytes : 0);          // (its own region: the filter scratch can be smaller than the log when raw_blocksize is)
     const size_t o_state = dtake(sizeof(EncState));
     e->dsize = doff;
     // ---- one pinned slab
     size_t hoff = 0;
     auto htake = [&](size_t bytes) { size_t o = hoff; hoff += (bytes + 255) & ~(size_t)255; return o; };
-    const size_t p_binfo = htake(sizeof(BlockInfo) * kMaxBlocksPerChunk);
-    const size_t p_runs = htake(sizeof(RunDesc) * (kMaxBlocksPerChunk + 2)), p_dup = htake(sizeof(uint32_t) * kMaxBlocksPerChunk);
     const size_t p_small = htake(64);
 
     if (ok) { e->res = host_res_get(e->device, hoff); ok = e->res != nullptr; }
@@ -878,11 +696,13 @@ CSCEncHandle CSCEnc_Create(const CSCProps *props, ISeqOutStream *outstream, ISzA
         h.wnd = D + o_wnd; h.mfbuf = (uint32_t *)(D + o_mf); h.p_lit = (uint32_t *)(D + o_plit); h.p_delta = (uint32_t *)(D + o_pdelta);
         h.rc_buf = D + o_rc; h.bc_buf = D + o_bc; h.inbuf = D + o_in; h.swapbuf = D + o_swap; h.arena = D + o_arena;
         h.bt_undo = h.bt_bits ? D + o_undo : nullptr;
-        h.binfo = (BlockInfo *)(D + o_binfo); h.dup_flags = (uint32_t *)(D + o_dup); e->d_trie = dt.trie;
-        e->d_runs = (RunDesc *)(D + o_runs); e->d_entcoef = dt.coef; e->d_state = (EncState *)(D + o_state);
+        h.binfo = (BlockInfo *)(D + o_binfo); e->d_trie = dt.trie;
+        e->d_entcoef = dt.coef; e->d_state = (EncState *)(D + o_state);
+#ifdef CSCMI_STAGE_TEST
+        e->d_result = (uint32_t *)(D + o_result);
+#endif
         e->h_in = e->res->h_in;
-        e->h_binfo = (BlockInfo *)(H + p_binfo); e->h_runs = (RunDesc *)(H + p_runs);
-        e->h_dup = (uint32_t *)(H + p_dup); e->h_small = (uint32_t *)(H + p_small);
+        e->h_small = (uint32_t *)(H + p_small);
         ok = hipMemsetAsync(e->dslab, 0, e->dsize, e->stream) == hipSuccess;
     }
     hipStream_t st = e->stream;
@@ -948,181 +768,52 @@ int CSCMI_EncodeDeviceChunkBatch(int n, CSCEncHandle *hs, const void *const *dev
     HIPCHK(host_events(lead->res));
     void **const d_batch = t_batch.d, **const h_batch = t_batch.h;
     int rc = 0;
-    static const bool trace = getenv("CSCMI_BATCH_TRACE") != nullptr;      // development: one line per round on stderr
+    static const bool trace = getenv("CSCMI_BATCH_TRACE") != nullptr;      // development: one line per call on stderr
     auto tnow = [] { return std::chrono::steady_clock::now(); };
     auto tms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     const auto t_begin = tnow();
-    if (!host_segment()) {
-        // every stream walks its chunk itself: upload + analyzer per stream, then ONE launch per kernel flavour, one workgroup a stream
-        for (int i = 0; i < n && !rc; i++) {
-            if (!sizes[i]) continue;
-            EncInstance *e = (EncInstance *)hs[i];
-            if (e->stats.chunks == 0 && e->stream != lead->stream) HIPCHK(hipStreamSynchronize(e->stream));   // (its state was initialised on its own stream)
-            rc = chunk_begin(e, device_ptrs[i], sizes[i], true, lead->stream);
-        }
-        if (rc) return rc;
-        for (int parser = 2; parser <= 63; parser++) {
-            if ((parser & 3) < 2) continue;
-            uint32_t m = 0;
-            EncState **st = (EncState **)h_batch;
-            const RunDesc **rl = (const RunDesc **)(h_batch + kMaxBatch);
-            uint32_t *cnt = (uint32_t *)(h_batch + 2 * kMaxBatch);
-            uint32_t *rst = (uint32_t *)(h_batch + 3 * kMaxBatch);
-            for (int i = 0; i < n; i++) {
-                EncInstance *e = (EncInstance *)hs[i];
-                if (!sizes[i] || e->parser != parser) continue;
-                st[m] = e->d_state; rl[m] = e->d_runs; cnt[m] = kSelfSegment | (uint32_t)sizes[i]; rst[m] = 1u;
-                m++;
-            }
-            if (!m) continue;
-            HIPCHK(hipMemcpyAsync(d_batch, h_batch, sizeof(void *) * 4 * kMaxBatch, hipMemcpyHostToDevice, lead->stream));
-            HIPCHK(hipEventRecord(lead->ev[0][0], lead->stream));
-            launch_encode_runs_multi(parser, m, (EncState *const *)d_batch, (const RunDesc *const *)(d_batch + kMaxBatch),
-                                     (const uint32_t *)(d_batch + 2 * kMaxBatch), (const uint32_t *)(d_batch + 3 * kMaxBatch), lead->stream);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(lead->ev[0][1], lead->stream));
-            HIPCHK(hipStreamSynchronize(lead->stream));          // (the pointer tables are reused by the next flavour)
-            float ms = 0;
-            if (hipEventElapsedTime(&ms, lead->ev[0][0], lead->ev[0][1]) == hipSuccess) lead->stats.encode_kernel_ms += ms;
-            lead->stats.encode_launches++;
-        }
-        const auto t_dr = tnow();
-        for (int i = 0; i < n; i++) {
-            if (!sizes[i]) continue;
-            EncInstance *e = (EncInstance *)hs[i];
-            e->stats.chunks++;
-            e->stats.input_bytes += sizes[i];
-        }
-        rc = drain_batch(n, hs, sizes, lead->stream);
-        if (trace) fprintf(stderr, "batch trace: %d streams, kernels walk their chunks: launches %.1f ms, drain %.1f ms\n", n, tms(t_begin, t_dr), tms(t_dr, tnow()));
-        return rc;
+    // every stream walks its chunk itself: upload + analyzer per stream, then ONE launch per kernel flavour, one workgroup a stream
+    for (int i = 0; i < n && !rc; i++) {
+        if (!sizes[i]) continue;
+        EncInstance *e = (EncInstance *)hs[i];
+        if (e->stats.chunks == 0 && e->stream != lead->stream) HIPCHK(hipStreamSynchronize(e->stream));   // (its state was initialised on its own stream)
+        rc = chunk_begin(e, device_ptrs[i], sizes[i], true, lead->stream);
     }
-    for (int i = 0; i < n; i++) HIPCHK(host_events(((EncInstance *)hs[i])->res));
-    for (int i = 0; i < n && !rc; i++) rc = sizes[i] ? chunk_begin((EncInstance *)hs[i], device_ptrs[i], sizes[i], true) : 0;
-    const auto t_cb = tnow();
-    for (int i = 0; i < n && !rc; i++) rc = sizes[i] ? seg_begin((EncInstance *)hs[i]) : 0;
     if (rc) return rc;
-    if (trace) fprintf(stderr, "batch trace: %d streams: chunk_begin %.1f ms, seg_begin %.1f ms\n", n, tms(t_begin, t_cb), tms(t_cb, tnow()));
-    double ms_dup = 0;
-    // Rounds: every stream's run segmentation goes on until it needs an IsDuplicateBlock verdict (csc_encoder_main.cpp:123-126: the
-    // runs so far must have been encoded first) or is complete.  The streams that wait for a verdict have their runs so far
-    // launched TOGETHER (one launch per parser flavour, one workgroup per stream), then their duplicate checks, one wait for all;
-    // the last round launches what is left of every stream.  (Stream by stream -- as CSCEnc_Encode does it for one handle -- a
-    // batch of streams with high-entropy / delta blocks ran one workgroup at a time.)
-    std::vector<uint8_t> state(n, 0);                // 0 walking, 1 waits for a verdict, 2 run list complete
-    int round = 0;
-    uint32_t side_used = 0;
-    bool side_any = false;
-    for (;;) {
-        const auto t_round = std::chrono::steady_clock::now();
-        uint32_t tr_streams = 0, tr_wait = 0;
-        round++;
-        bool any_wait = false, all_done = true;
+    for (int parser = 2; parser <= 63; parser++) {
+        if ((parser & 3) < 2) continue;
+        uint32_t m = 0;
+        EncState **st = (EncState **)h_batch;
+        const RunDesc **rl = (const RunDesc **)(h_batch + kMaxBatch);
+        uint32_t *cnt = (uint32_t *)(h_batch + 2 * kMaxBatch);
+        uint32_t *rst = (uint32_t *)(h_batch + 3 * kMaxBatch);
         for (int i = 0; i < n; i++) {
-            if (!sizes[i] || state[i] == 2) continue;
             EncInstance *e = (EncInstance *)hs[i];
-            int r = seg_advance(e, sizes[i]);
-            if (r < 0) return r;
-            state[i] = r == 1 ? 1 : 2;
-            any_wait = any_wait || r == 1;
+            if (!sizes[i] || e->parser != parser) continue;
+            st[m] = e->d_state; rl[m] = nullptr; cnt[m] = kSelfSegment | (uint32_t)sizes[i]; rst[m] = 1u;
+            m++;
         }
-        for (int i = 0; i < n; i++) all_done = all_done && (!sizes[i] || state[i] == 2);
-        // this round's launches.  A stream whose run list is COMPLETE needs nothing from the host any more: its remaining runs go out
-        // at once on a stream of their own (`side`) and run while the streams that wait for verdicts go through their rounds (the
-        // reference's workers do not wait for each other either, csarc.cpp:361-398); the waiting streams' runs so far go out on the
-        // lead's stream, which every round waits for.
-        for (int pass = 0; pass < 2; pass++) {                    // 0: complete streams -> side, 1: waiting streams -> lead's stream
-            for (int parser = 2; parser <= 63; parser++) {
-                if ((parser & 3) < 2) continue;
-                hipStream_t lst = pass == 0 ? t_batch.side : lead->stream;
-                void **hb = pass == 0 ? t_batch.h2 + side_used : h_batch, **db = pass == 0 ? t_batch.d2 + side_used : d_batch;
-                uint32_t m = 0;
-                EncState **st = (EncState **)hb;
-                const RunDesc **rl = (const RunDesc **)(hb + kMaxBatch);
-                uint32_t *cnt = (uint32_t *)(hb + 2 * kMaxBatch);
-                uint32_t *rst = (uint32_t *)(hb + 3 * kMaxBatch);
-                for (int i = 0; i < n; i++) {
-                    EncInstance *e = (EncInstance *)hs[i];
-                    if (!sizes[i] || e->parser != parser) continue;
-                    if (state[i] != (pass == 0 ? 2 : 1)) continue;
-                    EncInstance::Seg &g = e->seg;
-                    if (g.launched == g.nruns) continue;
-                    HIPCHK(hipMemcpyAsync(e->d_runs + g.launched, e->h_runs + g.launched, sizeof(RunDesc) * (g.nruns - g.launched),
-                                          hipMemcpyHostToDevice, lst));
-                    st[m] = e->d_state; rl[m] = e->d_runs + g.launched; cnt[m] = g.nruns - g.launched; rst[m] = g.first_launch ? 1u : 0u;
-                    g.launched = g.nruns; g.first_launch = false;
-                    m++;
-                }
-                if (!m) continue;
-                tr_streams += m;
-                if (pass == 0) {
-                    // (the four arrays of this launch start at entry side_used of the second table; nothing overwrites them before the end)
-                    for (int q = 0; q < 4; q++)
-                        HIPCHK(hipMemcpyAsync(db + q * kMaxBatch, hb + q * kMaxBatch, sizeof(void *) * m, hipMemcpyHostToDevice, lst));
-                    if (!side_any) HIPCHK(hipEventRecord(lead->ev[1][0], lst));
-                    launch_encode_runs_multi(parser, m, (EncState *const *)db, (const RunDesc *const *)(db + kMaxBatch),
-                                             (const uint32_t *)(db + 2 * kMaxBatch), (const uint32_t *)(db + 3 * kMaxBatch), lst);
-                    HIPCHK(hipGetLastError());
-                    side_used += m; side_any = true;
-                    lead->stats.encode_launches++;
-                    continue;
-                }
-                HIPCHK(hipMemcpyAsync(d_batch, h_batch, sizeof(void *) * 4 * kMaxBatch, hipMemcpyHostToDevice, lead->stream));
-                HIPCHK(hipEventRecord(lead->ev[0][0], lead->stream));
-                launch_encode_runs_multi(parser, m, (EncState *const *)d_batch, (const RunDesc *const *)(d_batch + kMaxBatch),
-                                         (const uint32_t *)(d_batch + 2 * kMaxBatch), (const uint32_t *)(d_batch + 3 * kMaxBatch), lead->stream);
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipEventRecord(lead->ev[0][1], lead->stream));
-                HIPCHK(hipStreamSynchronize(lead->stream));          // (the pointer tables are reused by the next flavour / round)
-                float ms = 0;
-                if (hipEventElapsedTime(&ms, lead->ev[0][0], lead->ev[0][1]) == hipSuccess) lead->stats.encode_kernel_ms += ms;
-                lead->stats.encode_launches++;
-            }
-        }
-        if (trace) {
-            for (int i = 0; i < n; i++) tr_wait += sizes[i] && state[i] == 1;
-            fprintf(stderr, "batch trace: round %d: %u streams launched, %u wait for a verdict, %.1f ms%s\n", round, tr_streams, tr_wait,
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_round).count(), all_done ? " (last)" : "");
-        }
-        if (all_done) break;
-        // the verdicts the waiting streams asked for, all in flight before the one wait
-        const auto t_dup = tnow();
-        for (int i = 0; i < n; i++) {
-            if (!sizes[i] || state[i] != 1) continue;
-            EncInstance *e = (EncInstance *)hs[i];
-            EncInstance::Seg &g = e->seg;
-            launch_dup_check(e->d_state, (uint32_t)sizes[i], g.need_blk, g.need_cnt, lead->stream);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipMemcpyAsync(e->h_dup + g.need_blk, e->h.dup_flags + g.need_blk, sizeof(uint32_t) * g.need_cnt, hipMemcpyDeviceToHost, lead->stream));
-        }
-        HIPCHK(hipStreamSynchronize(lead->stream));
-        for (int i = 0; i < n; i++) {
-            if (!sizes[i] || state[i] != 1) continue;
-            EncInstance::Seg &g = ((EncInstance *)hs[i])->seg;
-            g.dup_from = g.need_blk; g.dup_to = g.need_blk + g.need_cnt;
-            state[i] = 0;
-        }
-        ms_dup += tms(t_dup, tnow());
-    }
-    if (side_any) {
-        HIPCHK(hipEventRecord(lead->ev[1][1], t_batch.side));
-        HIPCHK(hipStreamSynchronize(t_batch.side));
+        if (!m) continue;
+        HIPCHK(hipMemcpyAsync(d_batch, h_batch, sizeof(void *) * 4 * kMaxBatch, hipMemcpyHostToDevice, lead->stream));
+        HIPCHK(hipEventRecord(lead->ev[0], lead->stream));
+        launch_encode_runs_multi(parser, m, (EncState *const *)d_batch, (const RunDesc *const *)(d_batch + kMaxBatch),
+                                 (const uint32_t *)(d_batch + 2 * kMaxBatch), (const uint32_t *)(d_batch + 3 * kMaxBatch), lead->stream);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(lead->ev[1], lead->stream));
+        HIPCHK(hipStreamSynchronize(lead->stream));          // (the pointer tables are reused by the next flavour)
         float ms = 0;
-        if (hipEventElapsedTime(&ms, lead->ev[1][0], lead->ev[1][1]) == hipSuccess) lead->stats.encode_kernel_ms += ms;
+        if (hipEventElapsedTime(&ms, lead->ev[0], lead->ev[1]) == hipSuccess) lead->stats.encode_kernel_ms += ms;
+        lead->stats.encode_launches++;
     }
-    const auto t_drain = tnow();
+    const auto t_dr = tnow();
     for (int i = 0; i < n; i++) {
         if (!sizes[i]) continue;
         EncInstance *e = (EncInstance *)hs[i];
         e->stats.chunks++;
         e->stats.input_bytes += sizes[i];
     }
-    for (int i = 0; i < n; i++) {
-        if (!sizes[i]) continue;
-        int r = drain_arena((EncInstance *)hs[i], 0);
-        if (r && !rc) rc = r;
-    }
-    if (trace) fprintf(stderr, "batch trace: %d rounds, duplicate checks %.1f ms, drain %.1f ms, whole call %.1f ms\n", round, ms_dup, tms(t_drain, tnow()), tms(t_begin, tnow()));
+    rc = drain_batch(n, hs, sizes, lead->stream);
+    if (trace) fprintf(stderr, "batch trace: %d streams, kernels walk their chunks: launches %.1f ms, drain %.1f ms\n", n, tms(t_begin, t_dr), tms(t_dr, tnow()));
     return rc;
 }
 
@@ -1160,8 +851,7 @@ int CSCEnc_Encode_Flush(CSCEncHandle p)
     HIPCHK(hipSetDevice(e->device));
     launch_encode_eof(e->d_state, e->stream);
     HIPCHK(hipGetLastError());
-    int ev_used = 0;
-    return drain_arena(e, ev_used);
+    return drain_arena(e, false);
 }
 
 // CSCEnc_Encode_Flush for many handles of one device: every EOF kernel queued on one stream, one wait, the last blocks handed to
@@ -1214,11 +904,13 @@ int CSCST_Analyze(CSCEncHandle p, const void *host, size_t size, uint32_t *out)
     HIPCHK(hipMemsetAsync(e->h.binfo, 0xEE, sizeof(BlockInfo) * nblk, e->stream));
     launch_analyze(e->d_state, (uint32_t)size, e->d_entcoef, e->stream);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(e->h_binfo, e->h.binfo, sizeof(BlockInfo) * nblk, hipMemcpyDeviceToHost, e->stream));
+    BlockInfo *bi = (BlockInfo *)thread_pinned(sizeof(BlockInfo) * nblk);
+    if (!bi) return CSCMI_DEVICE_ERROR;
+    HIPCHK(hipMemcpyAsync(bi, e->h.binfo, sizeof(BlockInfo) * nblk, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     for (uint32_t b = 0; b < nblk; b++) {
-        out[b * 7] = e->h_binfo[b].type; out[b * 7 + 1] = e->h_binfo[b].bpb;
-        for (int k = 0; k < 5; k++) out[b * 7 + 2 + k] = e->h_binfo[b].dlt_bpb[k];
+        out[b * 7] = bi[b].type; out[b * 7 + 1] = bi[b].bpb;
+        for (int k = 0; k < 5; k++) out[b * 7 + 2 + k] = bi[b].dlt_bpb[k];
     }
     return 0;
 }
@@ -1230,10 +922,10 @@ int CSCST_Filter(CSCEncHandle p, int kind, void *buf, size_t size, uint32_t chn,
     if (!e || size == 0 || size > e->props.raw_blocksize) return -1;
     HIPCHK(hipSetDevice(e->device));
     HIPCHK(hipMemcpyAsync(e->h.inbuf, buf, size, hipMemcpyHostToDevice, e->stream));
-    launch_stage_filter(e->d_state, (uint32_t)kind, (uint32_t)size, chn, e->h.dup_flags, e->stream);
+    launch_stage_filter(e->d_state, (uint32_t)kind, (uint32_t)size, chn, e->d_result, e->stream);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(buf, e->h.inbuf, size, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(hipMemcpyAsync(e->h_small, e->h.dup_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
+    HIPCHK(hipMemcpyAsync(e->h_small, e->d_result, sizeof(uint32_t), hipMemcpyDeviceToHost, e->stream));
     HIPCHK(hipStreamSynchronize(e->stream));
     if (result) *result = e->h_small[0];
     return 0;

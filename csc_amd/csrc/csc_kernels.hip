@@ -1,9 +1,8 @@
 // csc_kernels.hip -- gfx950 (CDNA4) kernels for the libcsc encode path.
 //
 // Design (DESIGN.md has the long form):
-//  * k_analyze / k_dup_check are wide kernels: one workgroup per 8 KiB block
-//     -- these are the embarrassingly parallel
-//    stages.
+//  * k_analyze is a wide kernel: one workgroup per 8 KiB block (SURVEY.md section 8a
+//    rows a4-a6) -- the embarrassingly parallel stage.
 //  * k_encode_runs is ONE WORKGROUP per stream.  A libcsc stream is a strictly
 //    serial dependency chain (adaptive probabilities -> prices -> parse ->
 //    match-finder state), so a wavefront executes that protocol with

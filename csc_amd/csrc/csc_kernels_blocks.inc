@@ -713,45 +713,6 @@ __global__ __launch_bounds__(256) void k_analyze(EncState *S, uint32_t chunk_siz
     if (tid == 0) { out->type = type; out->bpb = bpb; }
 }
 
-// ==========================================================================================
-// k_dup_check: LZ::IsDuplicateBlock / MatchFinder::TestFind (csc_lz.cpp:102-112, csc_mf.cpp:526-568)
-// for blocks [first, first+count) of the chunk against the CURRENT tables; one workgroup per block.
-// The bucket index lacks `+i` in the reference (:538), so only slot 0 is ever probed.
-__global__ __launch_bounds__(256) void k_dup_check(EncState *S, uint32_t chunk_size, uint32_t first)
-{
-    __shared__ uint32_t hit;
-    const uint32_t blk = first + blockIdx.x;
-    const uint8_t *src = S->inbuf + (size_t)blk * kMinBlock;
-    uint32_t size = umin(kMinBlock, chunk_size - blk * kMinBlock);
-    if (threadIdx.x == 0) hit = 0;
-    __syncthreads();
-    const uint32_t pos = S->pos, vld = S->vld_rge, wnd_size = S->wnd_size, wpos = S->wnd_curpos;
-    for (uint32_t i = threadIdx.x; i < size; i += blockDim.x) {
-        const uint8_t *p = src + i;
-        uint32_t lo = (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24);
-        uint32_t hi2 = (uint32_t)p[4] | ((uint32_t)p[5] << 8);
-        if (hash2_of(lo) % 16) continue;
-        uint32_t hv = hash6_mul(lo, hi2);
-        uint32_t limit = size - i;
-        uint32_t dists[2], nd = 0;
-        if (S->ht_width) dists[nd++] = pos - S->ht6[(size_t)(hv >> (32 - S->ht_bits)) * S->ht_width];
-        if (S->bt_head) dists[nd++] = pos - S->bt_head[hv >> (32 - S->bt_bits)];
-        for (uint32_t k = 0; k < nd; k++) {
-            uint32_t dist = dists[k];
-            if (dist >= vld) continue;
-            uint32_t cp = wpos >= dist ? wpos - dist : wpos + wnd_size - dist;
-            uint32_t climit = umin(limit, wnd_size - cp);
-            if (climit <= 18) continue;
-            const uint8_t *q = S->wnd + cp;
-            uint32_t n = 0;
-            while (n < 19 && p[n] == q[n]) n++;
-            if (n > 18) hit = 1;
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) S->dup_flags[blk] = hit;
-}
-
 #ifdef CSCMI_STAGE_TEST
 // Test-only (tests/stage/libcsc_stage.so, never in the product library): one forward filter over the chunk buffer, so that the
 // filter kernels can be held against the reference's own outputs (tests/golden/stages.json) stage by stage.
@@ -843,10 +804,6 @@ void launch_analyze(EncState *S, uint32_t chunk_size, const double *ent_coef, hi
 {
     uint32_t nblk = (chunk_size + kMinBlock - 1) / kMinBlock;
     hipLaunchKernelGGL(k_analyze, dim3(nblk), dim3(256), 0, st, S, chunk_size, ent_coef);
-}
-void launch_dup_check(EncState *S, uint32_t chunk_size, uint32_t first, uint32_t count, hipStream_t st)
-{
-    hipLaunchKernelGGL(k_dup_check, dim3(count), dim3(256), 0, st, S, chunk_size, first);
 }
 // (development: tools/ab_variant.sh three -DCSCMI_ONE_DYNLDS=13312 -- dynamic LDS that is never touched, to hold the one-wavefront form at THREE streams a CU instead of four)
 #ifndef CSCMI_ONE_DYNLDS

@@ -94,7 +94,7 @@ typedef struct {
     uint64_t output_bytes;        /* coder payload bytes (GetCompressedSize, csc_encoder_main.cpp:174) */
     uint64_t encode_launches;     /* k_encode_runs launches */
     double encode_kernel_ms;      /* HIP-event time of those launches, on the stream they ran on */
-    double analyze_kernel_ms;     /* k_analyze + k_dup_check */
+    double analyze_kernel_ms;     /* k_analyze */
     uint64_t find_match_calls, slide_positions, bt_steps, literals, matches;
 } CSCMIStats;
 

@@ -436,16 +436,19 @@ def test_batch_with_duplicate_block_checks_equals_oracle(prod, orc, zalloc, leve
         assert rc == 0 and bytes(w.out) == want, (i, len(w.out), len(want))
 
 
-def test_host_segmentation_diagnostic_path_gives_the_same_streams(prod, orc, zalloc):
-    """CSCMI_HOST_SEGMENT=1 keeps CSCEncoder::Compress's block walk on the host (run lists, a launch boundary per IsDuplicateBlock
-    verdict: the arrangement of rounds 1-3, kept for diagnostics).  Same bytes as the kernels' own walk, i.e. the oracle's."""
+def test_host_segment_variable_is_no_longer_read(prod, orc, zalloc):
+    """CSCMI_HOST_SEGMENT=1 once kept CSCEncoder::Compress's block walk on the host (run lists, a launch boundary per
+    IsDuplicateBlock verdict: the arrangement of rounds 1-3).  That encoder is gone and the variable is not read: with it set the
+    streams are still the oracle's, and a chunk is ONE encode launch.  `dup_blocks` is the case that tells: the analyzer types the
+    four blocks of its second `random` part DT_BAD and IsDuplicateBlock turns them into normal ones (as the oracle does: its walk
+    was printed once to confirm), which the host walk could only learn between two launches."""
     import subprocess
     import sys
     code = f"""
 import ctypes as C, os, sys
 sys.path.insert(0, {ROOT!r}); sys.path.insert(0, os.path.join({ROOT!r}, "tests"))
 import cases, csc_amd
-from csc_amd.capi import CscLib
+from csc_amd.capi import CscLib, BytesWriter
 lib = csc_amd.load()
 orc = CscLib(os.path.join({ROOT!r}, "oracle", "liborc.so")); orc.lib.orc_zero_alloc.restype = C.c_void_p; za = orc.lib.orc_zero_alloc()
 for name in ("mix_types", "dup_blocks", "delta_200k"):
@@ -453,6 +456,26 @@ for name in ("mix_types", "dup_blocks", "delta_200k"):
     data = cases.build(spec)
     for lv in (2, 3, 5):
         assert lib.encode(data, lv, d, clamp_dict=clamp) == orc.encode(data, lv, d, alloc=za, clamp_dict=clamp), (name, lv)
+spec, d, clamp, _ = cases.STREAM_CASES["dup_blocks"]
+data = cases.build(spec)
+assert len(data) == 146384
+L = lib.lib
+L.CSCMI_EncodeHostChunk.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
+L.CSCMI_GetStats.argtypes = [C.c_void_p, C.c_void_p]
+p = lib.props_init(min(d, len(data)), 3)
+w = BytesWriter()
+h = L.CSCEnc_Create(C.byref(p), C.cast(w.ptr(), C.c_void_p), None)
+assert h
+w.out += lib.write_properties(p)
+assert L.CSCMI_EncodeHostChunk(h, data, len(data)) == 0
+class St(C.Structure):
+    _fields_ = [("chunks", C.c_uint64), ("input_bytes", C.c_uint64), ("output_bytes", C.c_uint64), ("encode_launches", C.c_uint64), ("rest", C.c_uint64 * 8)]
+st = St()
+L.CSCMI_GetStats(h, C.byref(st))
+assert st.encode_launches == st.chunks == 1, (st.encode_launches, st.chunks)
+assert L.CSCEnc_Encode_Flush(h) == 0
+L.CSCEnc_Destroy(h)
+assert bytes(w.out) == orc.encode(data, 3, d, alloc=za, clamp_dict=clamp)[1]
 print("HOSTSEG_OK")
 """
     out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, CSCMI_HOST_SEGMENT="1"), capture_output=True, text=True, timeout=600)
