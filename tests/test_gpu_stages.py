@@ -10,10 +10,12 @@ import numpy as np
 import pytest
 
 import cases
+import filter_cases as F
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 STAGES = json.load(open(os.path.join(ROOT, "tests", "golden", "stages.json")))
+EDGES = json.load(open(os.path.join(ROOT, "tests", "golden", "filter_edges.json")))
 
 
 @pytest.fixture(scope="module")
@@ -79,6 +81,61 @@ def test_filter_kernels_match_reference_outputs(stage, key):
         d = np.frombuffer(src, dtype=np.uint8).copy()
         assert lib.lib.CSCST_Filter(h, 2, d.ctypes.data, n, chn, C.byref(res)) == 0
         assert cases.digest(d.tobytes()) == want[f"delta{chn}_sha256"], (key, chn)
+
+
+@pytest.fixture(scope="module")
+def edge_groups(orc):
+    return F.all_cases(orc.lib)
+
+
+@pytest.mark.parametrize("group", ["e89", "dict", "delta"])
+def test_filter_kernels_on_adversarial_cases(stage, orc, edge_groups, group):
+    """tests/filter_cases.py through CSCST_Filter: every case against the digest the REFERENCE recorded
+    (tests/golden/filter_edges.json) and byte for byte against the oracle; all differing cases are reported"""
+    lib, h, _ = stage
+    probes = F.Probes(orc.lib, "orc")
+    kind = {"e89": 0, "dict": 1, "delta": 2}[group]
+    assert edge_groups[group]
+    bad = []
+    for name, case in edge_groups[group].items():
+        data, chn = (case[0], case[1]) if group == "delta" else (case[0] if group == "dict" else case, 0)
+        a = np.frombuffer(data, dtype=np.uint8).copy()
+        res = C.c_uint32(0)
+        assert lib.lib.CSCST_Filter(h, kind, a.ctypes.data, len(a), chn, C.byref(res)) == 0, name
+        got = a.tobytes()
+        r, want = probes.run(f"forward_{group}", data, *([chn] if group == "delta" else []))
+        if group == "dict" and (res.value != EDGES[name]["dict_ok"] or res.value != r):
+            bad.append(f"{name}: accepted {res.value}, the reference {EDGES[name]['dict_ok']}, the oracle {r}")
+        elif got != want:
+            bad.append(f"{name}: {F.first_difference(got, want)}")
+        elif F.digest(got) != EDGES[name]["sha256"]:
+            bad.append(f"{name}: equals the oracle, not the reference's digest")
+    assert not bad, f"{len(bad)} of {len(edge_groups[group])} cases differ:\n" + "\n".join(bad[:20])
+
+
+def test_analyzer_kernel_on_adversarial_cases(stage, edge_groups):
+    """short last blocks on either side of 512 bytes, constant, alternating and ramp blocks: the reference's rows, under the
+    rules of test_analyzer_kernel_matches_reference_verdicts"""
+    lib, h, _ = stage
+    bad = []
+    for name, data in edge_groups["analyze"].items():
+        rows = EDGES[name]["rows"]
+        buf = np.frombuffer(data, dtype=np.uint8).copy()
+        assert len(rows) == (len(buf) + 8191) // 8192
+        out = (C.c_uint32 * (7 * len(rows)))()
+        assert lib.lib.CSCST_Analyze(h, buf.ctypes.data, len(buf), out) == 0, name
+        for b, want in enumerate(rows):
+            got = [int(v) for v in out[b * 7:b * 7 + 7]]
+            t = got[0]
+            if t != want[0]:
+                ok = False
+            elif t == 0x1E:                                     # DT_SKIP: bpb untouched in the reference, all five channel figures
+                ok = got[2:7] == want[2:7]
+            else:
+                ok = got[1] == want[1] and (not 0x10 <= t < 0x15 or got[2 + t - 0x10] == want[2 + t - 0x10])
+            if not ok:
+                bad.append(f"{name} block {b}: got {got}, the reference {want}")
+    assert not bad, f"{len(bad)} blocks differ:\n" + "\n".join(bad[:20])
 
 
 def test_dict_filter_reject_paths_are_the_references(stage):

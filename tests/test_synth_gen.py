@@ -14,6 +14,7 @@ import os
 import numpy as np
 import pytest
 
+import filter_cases as F
 import synth_gen as G
 from csc_amd.capi import CscLib
 
@@ -94,10 +95,35 @@ def complete():
         want.add(("refused", name))
     for g in G.GEOMETRY:
         want.add(("geometry",) + g)
+    # family `filters`, DT_ENGTXT runs: one cell for each thing its list promises
+    for n in G.TXT_SIZES:
+        want.add(("flt", "txt_size", n))
+    for follow in ("hi", "lo"):                                 # the byte behind the run: >= 0x82, < 0x82
+        for length in G.RUN254:
+            for start in G.RUN254_STARTS:
+                want.add(("flt", "run254", length, start, follow))
+        want.add(("flt", "whole_step_of_254", follow))          # the carry's lead == 64 branch
+    for where in ("serial", "tail"):                            # run of <= 66 bytes / the serial tail behind vector steps
+        want |= {("flt", "last_254", where), ("flt", "last_but_one_254_hi", where)}
+    for name in G.TAIL_BOUNDARY:
+        want.add(("flt", "tail_boundary", name))
+    for b in (0x82, 0xFB, 0xFC, 0xFD, 0xFF):
+        want.add(("flt", "byte", b))
+    want.add(("flt", "pair_254_254"))
+    for wl in (2, 3, 4):
+        for room in (1, 2, 3):
+            want.add(("flt", "clip", wl, room))
+    for r in range(4):
+        want.add(("flt", "all_four_letter", r))
+    for f in ("n", "0", "1MiB"):
+        want.add(("flt", "size_field", f))
+    for name in F.e89_cases():                                  # DT_EXE runs: the forward E89 case list as the filtered side
+        want.add(("flt", "exe", name))
     return want
 
 
-CASES = {"walk": 12, "lengths": 64, "distances": 4, "edges": 22, "blocks": 12, "geometry": 6, "refused": 36, "long_chain": 1, "long_rle": 1}
+CASES = {"walk": 12, "lengths": 64, "distances": 4, "edges": 22, "blocks": 12, "geometry": 6, "refused": 36, "long_chain": 1, "long_rle": 1,
+         "filters": 12}
 
 
 def test_coverage_table_is_complete(orc):
@@ -147,3 +173,44 @@ def test_streams_decode_as_predicted(orc, zalloc, golden, family, seed):
 def test_golden_has_no_stale_lines(orc, golden):
     ids = {G.case_id(c) for f, s in FAMILY_SEEDS for c in _cases(orc, f, s)}
     assert set(golden) == ids
+
+
+# ---- family `filters`: the prediction's own footing, and what its runs are sensitive to -----------------------------------
+
+@pytest.fixture(scope="module")
+def txt_runs(orc):
+    words = F.words(orc.lib)
+    return words, [(name, src, out) for name, runs in G.txt_runs(words).items() for src, out, _ in runs]
+
+
+def test_filter_runs_stay_inside_their_buffers_and_invert_as_restated(orc, txt_runs):
+    """the condition of the header's kept-out list: Inverse_Dict reads no source index at or behind a run's size; and the
+    restated inverses are the oracle's (and the reference's, where oracle/_ref is built) on every run of the family"""
+    words, runs = txt_runs
+    probes = [F.Probes(orc.lib, "orc")] + ([F.Probes(CscLib(REF).lib, "ref")] if os.path.exists(REF) else [])
+    assert len(runs) > 80
+    for name, src, out in runs:
+        got, hi = G.inverse_dict(src, words)
+        assert got == out and hi < len(src), (name, len(src), hi)
+        assert G.inverse_dict_steps(src, words) == out, (name, len(src))
+        for p in probes:
+            assert p.run("inverse_dict", src)[1] == out, (name, len(src))
+    for name, runs_ in G.exe_runs().items():
+        for coded, plain, _ in runs_:
+            for p in probes:
+                assert p.run("inverse_e89", coded)[1] == plain, name
+                assert p.run("forward_e89", plain)[1] == coded, name
+
+
+@pytest.mark.parametrize("mistake,witness", [
+    ("parity_not_carried", "txt_254_lo"),
+    ("run_of_64_even", "txt_254_hi"),
+    ("guard_dropped", "txt_tail"),
+    ("not_clipped", "txt_clip"),
+    ("max_symbol_fd", "txt_symbols"),
+])
+def test_filter_runs_catch_a_planted_mistake(txt_runs, mistake, witness):
+    """Inverse_Dict restated the way a 64-lane step computes it, with one mistake planted: a run of the named case differs"""
+    words, runs = txt_runs
+    hits = {name for name, src, out in runs if G.inverse_dict_steps(src, words, mistake) != out}
+    assert witness in hits, f"{mistake}: caught by {sorted(hits)}"
