@@ -20,10 +20,12 @@
 
 #include "../../include/csc_mi355x.h"
 #include "csc_device.h"
+#include "csc_enc_frame.h"
 #include "csc_tables.h"
 
 namespace cscmi {
 hipError_t upload_tables();
+void launch_frame_blocks(const FrameItem *items, FrameJob *jobs, FrameStatus *status, uint32_t nstreams, hipStream_t st);   // csc_enc_frame.hip
 void launch_init_state(EncState *S, hipStream_t st);
 void launch_analyze(EncState *S, uint32_t chunk_size, const double *ent_coef, hipStream_t st);
 void launch_encode_runs(int parser, EncState *S, const RunDesc *runs, uint32_t nruns, uint32_t reset_arena, hipStream_t st);
@@ -619,6 +621,7 @@ CSCEncHandle CSCEnc_Create(const CSCProps *props, ISeqOutStream *outstream, ISzA
 {
     if (alloc == NULL) alloc = &g_default_alloc;
     if (CSCMI_DeviceCheck() != 0) return NULL;
+    // (enc_props_ok below restates this refusal for CSCMI_EncodeDeviceBatch, which must tell it from a device failure: keep the two in step)
     if (props->csc_blocksize == 0 || props->csc_blocksize >= 16 * kMB || props->raw_blocksize == 0
         || props->raw_blocksize >= 16 * kMB || props->hash_width > 32
         || (props->lz_mode != 1 && props->lz_mode != 2 && props->lz_mode != 3)
@@ -874,6 +877,189 @@ int CSCMI_FlushBatch(int n, CSCEncHandle *hs)
         if (r) return r;
     }
     return 0;
+}
+
+// Not in the reference: whole inputs that lie in device memory encoded into streams that lie in device memory, n at once -- the
+// mirror image of CSCMI_DecodeDeviceBatch.  Per-stream state is a CSCEnc_Create handle without an output stream (so a recycled
+// slab is initialised exactly as CSCEnc_Create initialises it) that goes back to the caches when the call ends.  A round is what
+// CSCMI_EncodeDeviceChunkBatch queues -- chunk_begin for every live stream, one encode launch per kernel flavour -- and then, in
+// place of drain_batch, ONE launch of k_frame_blocks (csc_enc_frame.hip) that frames every stream's arena into its destination
+// under the dst_cap rule.  The last round queues k_encode_eof for every stream and frames again.  The host reads back one
+// FrameStatus {error, rc, produced} per live stream per round, 16 bytes, and nothing else: no coder block crosses the bus.
+static bool enc_props_ok(const CSCProps *props)      // CSCEnc_Create's refusal, restated (a note there points here): the two change together
+{
+    return !(props->csc_blocksize == 0 || props->csc_blocksize >= 16 * kMB || props->raw_blocksize == 0
+             || props->raw_blocksize >= 16 * kMB || props->hash_width > 32
+             || (props->lz_mode != 1 && props->lz_mode != 2 && props->lz_mode != 3)
+             || (props->hash_width && (props->hash_bits < 1 || props->hash_bits > 28))
+             || (props->bt_size && props->bt_hash_bits && (props->bt_hash_bits > 28)));
+}
+
+int CSCMI_EncodeDeviceBatch(int n, CSCMIDevEncode *jobs, CSCMIDevEncodeStats *stats)
+{
+    if (stats) { stats->launches = stats->rounds = stats->readback_bytes = 0; stats->kernel_ms = 0; }
+    if (n <= 0) return 0;
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
+    int device = 0;
+    HIPCHK(hipGetDevice(&device));
+    { int r = batch_args_ready(device); if (r) return r; }
+    void **const d_batch = t_batch.d, **const h_batch = t_batch.h;
+    hipStream_t st = pooled_stream(device);
+    if (!st) return CSCMI_DEVICE_ERROR;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};       // [0], [1] around an encode or a framing launch, [2], [3] around the flush kernels
+    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess || hipEventCreate(&ev[2]) != hipSuccess
+        || hipEventCreate(&ev[3]) != hipSuccess) {
+        for (hipEvent_t x : ev) if (x) (void)hipEventDestroy(x);
+        pooled_stream_release(device, st);
+        return CSCMI_DEVICE_ERROR;
+    }
+    static const bool trace = getenv("CSCMI_BATCH_TRACE") != nullptr;      // development: one line per call on stderr
+    double frame_ms = 0, all_ms = 0;
+    uint64_t launches = 0, rounds = 0, readback = 0;
+    for (int i = 0; i < n; i++) { jobs[i].produced = 0; jobs[i].rc = CSCMI_DEVICE_ERROR; }
+    struct Slot { int job; EncInstance *e; uint64_t chunks; bool live; };
+    int dev_rc = 0, next = 0;
+    while (next < n && !dev_rc) {
+        // a group: as many of the remaining jobs as the free device memory (and what the slab cache holds) can carry, kMaxBatch at most
+        std::vector<Slot> grp;
+        size_t free_b = 0, total_b = 0, used = 0, cached = 0;
+        if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { dev_rc = CSCMI_DEVICE_ERROR; break; }
+        { std::lock_guard<std::mutex> lk(g_cache_mu); cached = g_dev_cache_bytes; }
+        const size_t room = (free_b + cached) / 8 * 7;
+        for (; next < n && grp.size() < (size_t)kMaxBatch; next++) {
+            CSCMIDevEncode &job = jobs[next];
+            if (!enc_props_ok(&job.props)) { job.rc = CSCMI_NO_ENCODER; continue; }
+            EncInstance *e = (EncInstance *)CSCEnc_Create(&job.props, nullptr, nullptr);
+            if (!e) {
+                if (!grp.empty()) break;                       // this group first; the job is tried again with its memory back
+                continue;                                      // (rc stays CSCMI_DEVICE_ERROR; the other jobs proceed)
+            }
+            if (!grp.empty() && used + e->dsize > room) { CSCEnc_Destroy(e); break; }
+            used += e->dsize;
+            const uint64_t raw = job.props.raw_blocksize;
+            grp.push_back(Slot{next, e, ((uint64_t)job.src_size + raw - 1) / raw, true});
+        }
+        if (grp.empty()) continue;
+        const size_t m = grp.size();
+        // device: the job records (they persist across the rounds), the round's items and its status array; pinned: their host sides
+        uint8_t *d_mem = nullptr, *h_mem = nullptr;
+        const size_t per = sizeof(FrameJob) + sizeof(FrameItem) + sizeof(FrameStatus);
+        bool ok = hipMalloc((void **)&d_mem, per * m) == hipSuccess && hipHostMalloc((void **)&h_mem, per * m, hipHostMallocDefault) == hipSuccess;
+        FrameJob *d_jobs = (FrameJob *)d_mem, *h_jobs = (FrameJob *)h_mem;
+        FrameItem *d_items = (FrameItem *)(d_mem + sizeof(FrameJob) * m), *h_items = (FrameItem *)(h_mem + sizeof(FrameJob) * m);
+        FrameStatus *d_status = (FrameStatus *)(d_mem + (sizeof(FrameJob) + sizeof(FrameItem)) * m);
+        FrameStatus *h_status = (FrameStatus *)(h_mem + (sizeof(FrameJob) + sizeof(FrameItem)) * m);
+        uint64_t max_chunks = 0;
+        if (ok) {
+            for (size_t k = 0; k < m; k++) {
+                const CSCMIDevEncode &job = jobs[grp[k].job];
+                h_jobs[k] = FrameJob{(uint8_t *)job.dst, (uint64_t)job.dst_cap, 0, 0, 0};
+                if (grp[k].chunks > max_chunks) max_chunks = grp[k].chunks;
+            }
+            ok = hipMemcpyAsync(d_jobs, h_jobs, sizeof(FrameJob) * m, hipMemcpyHostToDevice, st) == hipSuccess;
+        }
+        std::vector<size_t> in_round;
+        // frame what the round's kernels left in the arenas of `in_round`, read the status array back, retire what has ended
+        auto frame_round = [&]() -> bool {
+            const size_t c = in_round.size();
+            if (!c) return true;
+            for (size_t k = 0; k < c; k++) h_items[k] = FrameItem{grp[in_round[k]].e->d_state, (uint32_t)in_round[k], 0};
+            bool good = hipMemcpyAsync(d_items, h_items, sizeof(FrameItem) * c, hipMemcpyHostToDevice, st) == hipSuccess
+                     && hipEventRecord(ev[0], st) == hipSuccess;
+            if (good) {
+                launch_frame_blocks(d_items, d_jobs, d_status, (uint32_t)c, st);
+                good = hipGetLastError() == hipSuccess && hipEventRecord(ev[1], st) == hipSuccess;
+            }
+            good = good && hipMemcpyAsync(h_status, d_status, sizeof(FrameStatus) * c, hipMemcpyDeviceToHost, st) == hipSuccess
+                        && hipStreamSynchronize(st) == hipSuccess;
+            float ms = 0;
+            good = good && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess;
+            if (!good) return false;
+            launches++; readback += sizeof(FrameStatus) * c; frame_ms += ms; all_ms += ms;
+            for (size_t k = 0; k < c; k++) {
+                Slot &s = grp[in_round[k]];
+                CSCMIDevEncode &job = jobs[s.job];
+                job.produced = (size_t)h_status[k].produced;
+                if (h_status[k].error != ERR_NONE) {               // (rc stays CSCMI_DEVICE_ERROR)
+                    if (h_status[k].error == kFrameErrArena) fprintf(stderr, "csc-mi355x: device encoder error 0x%x (a coder block record does not lie inside the arena)\n", kFrameErrArena);
+                    else (void)report_device_error(h_status[k].error);
+                    s.live = false;
+                }
+                else if (h_status[k].rc != 0) { job.rc = h_status[k].rc; s.live = false; }
+            }
+            return true;
+        };
+        for (uint64_t r = 0; r < max_chunks && ok; r++) {
+            in_round.clear();
+            for (size_t k = 0; k < m && ok; k++) {
+                Slot &s = grp[k];
+                if (!s.live || r >= s.chunks) continue;
+                const CSCMIDevEncode &job = jobs[s.job];
+                const uint64_t raw = job.props.raw_blocksize, off = r * raw;
+                const size_t size = (size_t)(job.src_size - off < raw ? job.src_size - off : raw);
+                ok = chunk_begin(s.e, (const uint8_t *)job.src + off, size, true, st) == 0;
+                in_round.push_back(k);
+            }
+            // one launch per kernel flavour, one workgroup a stream: as CSCMI_EncodeDeviceChunkBatch queues them
+            for (int parser = 2; parser <= 63 && ok; parser++) {
+                if ((parser & 3) < 2) continue;
+                uint32_t c = 0;
+                EncState **sp = (EncState **)h_batch;
+                const RunDesc **rl = (const RunDesc **)(h_batch + kMaxBatch);
+                uint32_t *cnt = (uint32_t *)(h_batch + 2 * kMaxBatch);
+                uint32_t *rst = (uint32_t *)(h_batch + 3 * kMaxBatch);
+                for (size_t k : in_round) {
+                    const Slot &s = grp[k];
+                    if (s.e->parser != parser) continue;
+                    const CSCMIDevEncode &job = jobs[s.job];
+                    const uint64_t raw = job.props.raw_blocksize, off = r * raw;
+                    sp[c] = s.e->d_state; rl[c] = nullptr; rst[c] = 1u;
+                    cnt[c] = kSelfSegment | (uint32_t)(job.src_size - off < raw ? job.src_size - off : raw);
+                    c++;
+                }
+                if (!c) continue;
+                ok = hipMemcpyAsync(d_batch, h_batch, sizeof(void *) * 4 * kMaxBatch, hipMemcpyHostToDevice, st) == hipSuccess
+                  && hipEventRecord(ev[0], st) == hipSuccess;
+                if (ok) {
+                    launch_encode_runs_multi(parser, c, (EncState *const *)d_batch, (const RunDesc *const *)(d_batch + kMaxBatch),
+                                             (const uint32_t *)(d_batch + 2 * kMaxBatch), (const uint32_t *)(d_batch + 3 * kMaxBatch), st);
+                    ok = hipGetLastError() == hipSuccess && hipEventRecord(ev[1], st) == hipSuccess
+                      && hipStreamSynchronize(st) == hipSuccess;          // (the pointer tables are reused by the next flavour)
+                }
+                float ms = 0;
+                if (ok && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) all_ms += ms;
+                launches++;
+            }
+            ok = ok && frame_round();
+            rounds++;
+        }
+        if (ok) {                                              // CSCEnc_Encode_Flush for every stream that still lives
+            in_round.clear();
+            ok = hipEventRecord(ev[2], st) == hipSuccess;      // one event pair around all the flush kernels: they run back to back on `st`
+            for (size_t k = 0; k < m && ok; k++) {
+                if (!grp[k].live) continue;
+                launch_encode_eof(grp[k].e->d_state, st);
+                launches++;
+                in_round.push_back(k);
+            }
+            ok = ok && hipGetLastError() == hipSuccess && hipEventRecord(ev[3], st) == hipSuccess && frame_round();
+            float ms = 0;
+            if (ok && !in_round.empty() && hipEventElapsedTime(&ms, ev[2], ev[3]) == hipSuccess) all_ms += ms;   // (frame_round has waited for the stream)
+            rounds++;
+            if (ok) for (size_t k : in_round) if (grp[k].live) jobs[grp[k].job].rc = 0;
+        }
+        if (!ok) dev_rc = CSCMI_DEVICE_ERROR;
+        (void)hipStreamSynchronize(st);
+        if (d_mem) (void)hipFree(d_mem);
+        if (h_mem) (void)hipHostFree(h_mem);
+        for (const Slot &s : grp) CSCEnc_Destroy(s.e);
+    }
+    for (hipEvent_t x : ev) (void)hipEventDestroy(x);
+    pooled_stream_release(device, st);
+    if (stats) { stats->launches = launches; stats->rounds = rounds; stats->readback_bytes = readback; stats->kernel_ms = all_ms; }
+    if (trace) fprintf(stderr, "encode-device trace: %d jobs, %llu rounds, %llu launches, kernels %.3f ms of which framing %.3f ms, read back %llu bytes\n",
+                       n, (unsigned long long)rounds, (unsigned long long)launches, all_ms, frame_ms, (unsigned long long)readback);
+    return dev_rc;
 }
 
 void CSCMI_GetStats(CSCEncHandle p, CSCMIStats *out)

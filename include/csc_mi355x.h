@@ -145,6 +145,46 @@ typedef struct {
 typedef struct { uint64_t launch_bytes; } CSCMIDevDecodeOpts;   /* output per stream after which a launch returns; 0 = the library's default (4 MiB) */
 typedef struct { uint64_t launches, rounds; double kernel_ms; } CSCMIDevDecodeStats;   /* kernel launches, host rounds, HIP-event time of the launches */
 int CSCMI_DecodeDeviceBatch(int n, CSCMIDevDecode *jobs, const CSCMIDevDecodeOpts *opts, CSCMIDevDecodeStats *stats);
+/* Device-resident encode, the mirror image of CSCMI_DecodeDeviceBatch: n whole inputs that lie in device memory, encoded into
+ * streams that lie in device memory.  The finished coder blocks are framed into dst by a kernel of their own (k_frame_blocks):
+ * no block crosses the bus and no callback is made.  One-shot: per-stream state comes from the encoder's resource caches,
+ * initialised exactly as CSCEnc_Create initialises it, and goes back to them; any n >= 0, in groups sized to the free device
+ * memory and to 2048 streams; launches go to the library's pooled stream, the call returns when all jobs have their answer, and
+ * it is safe from several threads at once.
+ *
+ * jobs[i].rc and dst[0 .. produced) are exactly what CSCEnc_Create + CSCEnc_Encode + CSCEnc_Encode_Flush write over an
+ * ISeqInStream that serves src[0 .. src_size) with full-size reads (chunks of raw_blocksize bytes, the last one ragged) and an
+ * ISeqOutStream that accepts a Write only while the total stays <= dst_cap.  The 10 property bytes are the caller's
+ * (CSCEnc_WriteProperties), as with the reference; src_size == 0 gives the stream CSCEnc_Encode_Flush alone writes.
+ *   rc        0, or WRITE_ERROR where dst_cap is too small; CSCMI_NO_ENCODER where CSCEnc_Create would have returned NULL for
+ *             these props; CSCMI_DEVICE_ERROR if this job could not get its device memory or its kernel reported an error
+ *             (output arena exhausted, watchdog).  The last two do not stop the other jobs of the call.
+ *   dst       the first Write that does not fit ends the stream with WRITE_ERROR: produced is the bytes of all EARLIER Write
+ *             calls and nothing after it is written, not even a later flag byte that would fit.  The granularity is
+ *             MemIO::WriteBlock's (csc_memio.cpp:83-108): the flag byte, then the 3 size bytes when the block is not exactly
+ *             csc_blocksize long, then the payload -- each all or nothing, in the order the blocks were finished.
+ *             Nothing outside [src, src + src_size) is loaded, nothing outside [dst, dst + dst_cap) is stored, and the bytes
+ *             of dst at and beyond produced are untouched.
+ * Returns 0, or CSCMI_DEVICE_ERROR if the GPU side failed or no device is visible; without a visible device no field of any
+ * job is touched.  stats may be NULL.  A round is one chunk of every stream that still has one (the last round is the flush of
+ * all): stats->rounds is the most chunks any job of a group has, plus one, summed over the groups.  Per round the host reads
+ * back ONE status array, 16 bytes {error, rc, produced} per stream of the round, and nothing else: stats->readback_bytes, which
+ * counts every device-to-host byte of the call, is at most 16 * n * rounds.  stats->launches counts the encode launches (one per
+ * kernel flavour and round), the flush kernels (one per stream) and the framing launches (one per round); stats->kernel_ms is the
+ * HIP-event time of exactly those.  The analyzer launches and the device-to-device copies of the chunks are neither counted nor
+ * timed. */
+#define CSCMI_NO_ENCODER (-91)   /* where CSCEnc_Create would have returned NULL for these props */
+typedef struct {
+    CSCProps props;          /* in: as CSCEncProps_Init gives them, or custom (host memory) */
+    const void *src;         /* in: device pointer to the raw bytes; any alignment */
+    size_t src_size;         /* may be 0 */
+    void *dst;               /* in: device pointer; receives the stream AFTER its 10 property bytes; any alignment; must not overlap src */
+    size_t dst_cap;
+    size_t produced;         /* out: bytes written to dst */
+    int rc;                  /* out */
+} CSCMIDevEncode;
+typedef struct { uint64_t launches, rounds, readback_bytes; double kernel_ms; } CSCMIDevEncodeStats;   /* encode, flush and framing launches; host rounds; device-to-host bytes; HIP-event time of those launches */
+int CSCMI_EncodeDeviceBatch(int n, CSCMIDevEncode *jobs, CSCMIDevEncodeStats *stats);
 /* Host-memory variant used by CSCEnc_Encode itself. */
 int CSCMI_EncodeHostChunk(CSCEncHandle p, const void *host_ptr, size_t size);
 void CSCMI_GetStats(CSCEncHandle p, CSCMIStats *out);
