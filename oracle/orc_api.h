@@ -11,6 +11,11 @@
  *   ICompressProgress    /root/reference/src/libcsc/Types.h:220-225
  *   ISzAlloc             /root/reference/src/libcsc/Types.h:227-231
  *   error codes          /root/reference/src/libcsc/csc_common.h:13-17
+ *
+ * Beside the boundary, oracle-only probes (none of them in the product):
+ *   orc_analyze_block .. orc_tables   single stages, for intermediate goldens
+ *   orc_trace_*                       the chunk walk's and TestFind's decisions during an encode (tests/walk_cases.py)
+ *   orc_synth                         a script of packets -> a stream body
  */
 #ifndef ORC_API_H_
 #define ORC_API_H_
@@ -79,6 +84,22 @@ void orc_inverse_delta(uint8_t *buf, uint32_t size, uint32_t chn);
 /* the two float-built tables */
 void orc_tables(uint32_t p2bits[512], uint32_t logtab[513]);
 
+/* ---- walk trace: what CSCEncoder::Compress and MatchFinder::TestFind decided while a stream was encoded.  Off unless a
+ * trace is attached to the handle right after CSCEnc_Create; rows are plain uint32 words, widths below.
+ *   ORC_TRACE_BLOCK  per 8 KiB block: chunk, block, offset, size, analyzer type, bpb in force, GetDltBpb x 5 (1, 2, 3, 4, 8
+ *                    channels), the GetDltBpb figure the 0.95 rule used (0xFFFFFFFF: rule not reached), type after DT_SKIP
+ *                    inheritance, after the filter switches, after the 0.95 rule, final type, duplicate verdict (2: not asked)
+ *   ORC_TRACE_CAND   per candidate TestFind looked at: chunk, block, offset i in the block, table (0: HT6 slot 0, 1: BT head),
+ *                    dist, vld_rge, cmp_pos, limit, wnd_size - cmp_pos, equal bytes (counted on past the window's end into its
+ *                    eight bytes of slack, up to min(limit, 64); all three 0 where dist > wnd_size), hit
+ *   ORC_TRACE_RUN    per run handed to compress_block: chunk, type, offset, size, tail (EncodeInt after it) */
+enum { ORC_TRACE_BLOCK = 0, ORC_TRACE_CAND = 1, ORC_TRACE_RUN = 2 };
+enum { ORC_TRACE_BLOCK_W = 17, ORC_TRACE_CAND_W = 11, ORC_TRACE_RUN_W = 5 };
+struct OrcTrace;
+struct OrcTrace *orc_trace_new(void);
+void orc_trace_attach(CSCEncHandle h, struct OrcTrace *t);
+const uint32_t *orc_trace_rows(const struct OrcTrace *t, int kind, size_t *count);
+void orc_trace_free(struct OrcTrace *t);
 
 /* ---- stream synthesizer (orc_synth.c): a script of packets -> a stream body, through the oracle's coder and model ---- */
 enum {

@@ -100,6 +100,9 @@ typedef struct OrcEnc {
     uint32_t swap_size;
     uint32_t x0, x1, ei, ek;
     uint8_t ecs;
+
+    /* ---- walk trace (orc_trace_*; NULL unless a test attached one) ---- */
+    struct OrcTrace *trace;
 } OrcEnc;
 
 ORC_INT int write_block(OrcEnc *e, uint8_t *buf, uint32_t size, int rc1bc0);

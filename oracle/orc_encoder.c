@@ -11,6 +11,12 @@
  * from its own sources by oracle/Makefile) is compared byte-for-byte with this
  * restatement by tools/make_golden.py and tests/test_oracle_vs_ref.py, and the
  * resulting vectors are committed under tests/golden/.
+ *
+ * Probes beside the boundary (orc_api.h), all oracle-only:
+ *   orc_debug_set_pos / get_pos    start the match finder's position counter elsewhere (renormalisation)
+ *   orc_analyze_block .. orc_tables   single stages for intermediate goldens
+ *   orc_trace_*                    what enc_compress (the chunk walk) and mf_test_find decided during an encode:
+ *                                  rows per block, per candidate, per run; off unless a trace is attached to the handle
  */
 #include <math.h>
 #include <setjmp.h>
@@ -751,6 +757,47 @@ static MFUnit mf_find_best(OrcEnc *e, const uint32_t *rep_dist, uint32_t wnd_pos
     return e->mfcand[best];
 }
 
+/* ---- walk trace (orc_api.h): growing arrays of uint32 rows, written only while a trace is attached ---- */
+struct OrcTrace {
+    uint32_t *rows[3];
+    size_t count[3], cap[3];
+    uint32_t chunk, block, at;    /* where the walk stands: chunk of the stream, block of the chunk, offset in the block */
+};
+static const uint32_t kTraceWidth[3] = {ORC_TRACE_BLOCK_W, ORC_TRACE_CAND_W, ORC_TRACE_RUN_W};
+static uint32_t *trace_row(struct OrcTrace *t, int kind)
+{
+    if (t->count[kind] == t->cap[kind]) {
+        t->cap[kind] = t->cap[kind] ? t->cap[kind] * 2 : 256;
+        t->rows[kind] = (uint32_t *)realloc(t->rows[kind], t->cap[kind] * kTraceWidth[kind] * sizeof(uint32_t));
+        if (!t->rows[kind]) abort();
+    }
+    return t->rows[kind] + t->count[kind]++ * kTraceWidth[kind];
+}
+struct OrcTrace *orc_trace_new(void) { return (struct OrcTrace *)calloc(1, sizeof(struct OrcTrace)); }
+void orc_trace_attach(CSCEncHandle h, struct OrcTrace *t) { ((OrcEnc *)h)->trace = t; }
+const uint32_t *orc_trace_rows(const struct OrcTrace *t, int kind, size_t *count)
+{
+    *count = t->count[kind];
+    return t->rows[kind];
+}
+void orc_trace_free(struct OrcTrace *t)
+{
+    if (!t) return;
+    for (int k = 0; k < 3; k++) free(t->rows[k]);
+    free(t);
+}
+static void trace_cand(OrcEnc *e, uint32_t table, uint32_t dist, uint32_t wpos, uint32_t limit, const uint8_t *src, int hit)
+{
+    struct OrcTrace *t = e->trace;
+    uint32_t *r = trace_row(t, ORC_TRACE_CAND), eq = 0, cmp_pos = 0;
+    int in_range = dist <= e->wnd_size;       /* (not the reference's test: where a window position can be named at all) */
+    if (in_range) cmp_pos = wrap_back(e, wpos, dist);
+    if (in_range)
+        while (eq < limit && eq < 64 && cmp_pos + eq < e->wnd_size + 8 && src[eq] == e->wnd[cmp_pos + eq]) eq++;
+    r[0] = t->chunk; r[1] = t->block; r[2] = t->at; r[3] = table; r[4] = dist; r[5] = e->vld_rge;
+    r[6] = cmp_pos; r[7] = limit; r[8] = in_range ? e->wnd_size - cmp_pos : 0; r[9] = eq; r[10] = (uint32_t)hit;
+}
+
 /* MatchFinder::TestFind, csc_mf.cpp:526-568 (bucket index lacks +i) */
 static int mf_test_find(OrcEnc *e, uint32_t wpos, const uint8_t *src, uint32_t limit)
 {
@@ -769,10 +816,16 @@ static int mf_test_find(OrcEnc *e, uint32_t wpos, const uint8_t *src, uint32_t l
     }
     for (uint32_t i = 0; i < depth; i++) {
         uint32_t dist = dists[i];
-        if (dist >= e->vld_rge) continue;
+        uint32_t table = (e->bt_head && i == depth - 1) ? 1 : 0;
+        if (dist >= e->vld_rge) {
+            if (e->trace) trace_cand(e, table, dist, wpos, limit, src, 0);
+            continue;
+        }
         uint32_t cmp_pos = wrap_back(e, wpos, dist);
         uint32_t climit = UMIN(limit, e->wnd_size - cmp_pos);
-        if (prefix_len(src, e->wnd + cmp_pos, climit) > 18) return 1;
+        int hit = prefix_len(src, e->wnd + cmp_pos, climit) > 18;
+        if (e->trace) trace_cand(e, table, dist, wpos, limit, src, hit);
+        if (hit) return 1;
     }
     return 0;
 }
@@ -1022,8 +1075,10 @@ static void lz_encode_normal(OrcEnc *e, const uint8_t *src, uint32_t size, uint3
 /* LZ::IsDuplicateBlock, csc_lz.cpp:102-112 */
 static int lz_is_duplicate_block(OrcEnc *e, const uint8_t *src, uint32_t size)
 {
-    for (uint32_t i = 0; i < size; i++)
+    for (uint32_t i = 0; i < size; i++) {
+        if (e->trace) e->trace->at = i;
         if (mf_test_find(e, e->wnd_curpos, src + i, size - i)) return 1;
+    }
     return 0;
 }
 
@@ -1325,25 +1380,51 @@ static void enc_compress_block(OrcEnc *e, uint8_t *src, uint32_t size, uint32_t 
 }
 
 /* CSCEncoder::Compress, csc_encoder_main.cpp:85-147 */
+static void trace_run(OrcEnc *e, uint32_t type, uint32_t off, uint32_t size, uint32_t tail)
+{
+    uint32_t *r = trace_row(e->trace, ORC_TRACE_RUN);
+    r[0] = e->trace->chunk; r[1] = type; r[2] = off; r[3] = size; r[4] = tail;
+}
 static void enc_compress(OrcEnc *e, uint8_t *src, uint32_t size)
 {
     uint32_t last_type = DT_NORMAL, this_type, last_begin = 0, last_size = 0, bpb = 0;
     int use_filters = (e->props.DLTFilter + e->props.EXEFilter + e->props.TXTFilter) != 0;
+    struct OrcTrace *t = e->trace;
+    uint32_t *tr = NULL;
+    if (t) t->block = 0;
     for (uint32_t i = 0; i < size;) {
         uint32_t cur = UMIN(MIN_BLOCK, size - i);
         this_type = use_filters ? an_analyze(e->log_table, src + i, cur, &bpb) : DT_NORMAL;
+        if (t) {
+            static const uint32_t chn[5] = {1, 2, 3, 4, 8};
+            tr = trace_row(t, ORC_TRACE_BLOCK);
+            tr[0] = t->chunk; tr[1] = t->block; tr[2] = i; tr[3] = cur; tr[4] = this_type; tr[5] = bpb;
+            for (int k = 0; k < 5; k++) tr[6 + k] = an_dlt_bpb(e->log_table, src + i, cur, chn[k]);
+            tr[11] = 0xFFFFFFFFu; tr[16] = 2;
+        }
         if (this_type == DT_SKIP) this_type = last_type;
+        if (t) tr[12] = this_type;
         if (this_type != DT_NORMAL) {
             if (this_type == DT_EXE && e->props.EXEFilter == 0) this_type = DT_NORMAL;
             else if (this_type == DT_ENGTXT && e->props.TXTFilter == 0) this_type = DT_NORMAL;
             else if (this_type >= DT_DLT && e->props.DLTFilter == 0) this_type = DT_NORMAL;
         }
-        if (this_type >= DT_DLT
-            && an_dlt_bpb(e->log_table, src + i, cur, kDltIndex[this_type - DT_DLT]) >= bpb * 0.95)
-            this_type = DT_NORMAL;
-        if (this_type >= DT_NO_LZ && lz_is_duplicate_block(e, src + i, cur)) this_type = DT_NORMAL;
+        if (t) tr[13] = this_type;
+        if (this_type >= DT_DLT) {
+            uint32_t d = an_dlt_bpb(e->log_table, src + i, cur, kDltIndex[this_type - DT_DLT]);
+            if (t) tr[11] = d;
+            if (d >= bpb * 0.95) this_type = DT_NORMAL;
+        }
+        if (t) tr[14] = this_type;
+        if (this_type >= DT_NO_LZ) {
+            int dup = lz_is_duplicate_block(e, src + i, cur);
+            if (t) { tr = t->rows[ORC_TRACE_BLOCK] + (t->count[ORC_TRACE_BLOCK] - 1) * ORC_TRACE_BLOCK_W; tr[16] = (uint32_t)dup; }
+            if (dup) this_type = DT_NORMAL;
+        }
+        if (t) { tr[15] = this_type; t->block++; }
         if (last_type != this_type || last_size + cur > e->props.raw_blocksize) {
             if (last_size) {
+                if (t) trace_run(e, last_type, last_begin, last_size, 0);
                 enc_compress_block(e, src + last_begin, last_size, last_type);
                 encode_int(e, 0);
             }
@@ -1355,10 +1436,12 @@ static void enc_compress(OrcEnc *e, uint8_t *src, uint32_t size)
         i += cur;
     }
     if (last_size) {
+        if (t) trace_run(e, last_type, last_begin, last_size, 1);
         enc_compress_block(e, src + last_begin, last_size, last_type);
         encode_int(e, 1);
         coder_flush(e);
     }
+    if (t) t->chunk++;
 }
 
 /* ===================================================================== */

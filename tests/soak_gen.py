@@ -321,11 +321,13 @@ def bind_batch(L):
 def encode_batch(prod, props, datas, chunk=CHUNK, stats=None):
     """Every stream through the batch entry points: one handle each, inputs resident in device memory, one
     CSCMI_EncodeDeviceChunkBatch per chunk round over the streams that still have bytes, then one CSCMI_FlushBatch.
-    Returns (streams, chunk rounds).  `stats`, a list, receives the lead handle's CSCMIStats before the flush."""
+    Returns (streams, chunk rounds).  `stats`, a list, receives the lead handle's CSCMIStats before the flush.  `chunk` may be
+    a list, one chunk size a stream (streams whose props carry their own raw_blocksize)."""
     import torch
     from csc_amd.capi import BytesWriter
     L = bind_batch(prod.lib)
     S = len(datas)
+    chunks = list(chunk) if isinstance(chunk, (list, tuple)) else [chunk] * S
     hs, ws, devs = [], [], []
     try:
         for p, d in zip(props, datas):
@@ -338,12 +340,12 @@ def encode_batch(prod, props, datas, chunk=CHUNK, stats=None):
         torch.cuda.synchronize()
         k = 0
         while True:
-            Z = [max(0, min(chunk, len(d) - k * chunk)) for d in datas]
+            Z = [max(0, min(c, len(d) - k * c)) for c, d in zip(chunks, datas)]
             live = [i for i in range(S) if Z[i] > 0]
             if not live:
                 break
             H = (C.c_void_p * len(live))(*[hs[i] for i in live])
-            P = (C.c_void_p * len(live))(*[devs[i].data_ptr() + k * chunk for i in live])
+            P = (C.c_void_p * len(live))(*[devs[i].data_ptr() + k * chunks[i] for i in live])
             rc = L.CSCMI_EncodeDeviceChunkBatch(len(live), H, P, (C.c_size_t * len(live))(*[Z[i] for i in live]))
             assert rc == 0, f"CSCMI_EncodeDeviceChunkBatch round {k}: {rc}"
             k += 1
