@@ -213,15 +213,21 @@ class CscLib:
         return (rc if rc < 0 else rc2), bytes(w.out)
 
     def decode(self, stream: bytes, *, alloc=None, writer: Optional[BytesWriter] = None,
-               max_read: Optional[int] = None):
+               max_read: Optional[int] = None, progress: Optional[Callable[[int, int], None]] = None):
         """caller reads the 10-byte header -> ReadProperties -> Create -> Decode -> Destroy
-        (csa_worker.cpp:75-83).  Returns (rc, raw_bytes); rc None if Create failed."""
+        (csa_worker.cpp:75-83).  Returns (rc, raw_bytes); rc None if Create failed.
+        `progress(consumed, produced)` sees every Progress call (csc_dec.cpp:761-762)."""
         props = self.read_properties(stream[:CSC_PROP_SIZE])
         r = BytesReader(stream[CSC_PROP_SIZE:], max_read=max_read)
         w = writer or BytesWriter()
         h = self.lib.CSCDec_Create(C.byref(props), C.cast(r.ptr(), C.c_void_p), alloc)
         if not h:
             return None, b""
-        rc = self.lib.CSCDec_Decode(h, C.cast(w.ptr(), C.c_void_p), None)
+        prog = None
+        pfn = None
+        if progress is not None:
+            pfn = PROGRESS_FN(lambda p, a, b: (progress(a, b), 0)[1])
+            prog = ICompressProgress(pfn)
+        rc = self.lib.CSCDec_Decode(h, C.cast(w.ptr(), C.c_void_p), C.byref(prog) if prog else None)
         self.lib.CSCDec_Destroy(h)
         return rc, bytes(w.out)

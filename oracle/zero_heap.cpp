@@ -1,4 +1,5 @@
-/* oracle/zero_heap.cpp -- TEST INFRASTRUCTURE, linked only into oracle/_ref/csarc_ref.
+/* oracle/zero_heap.cpp -- TEST INFRASTRUCTURE, linked only into the reference's programs under oracle/_ref
+ * (csarc_ref, csc_ref, csarc_on_product).
  *
  * The reference archiver compresses two kinds of uninitialised memory:
  *   - libcsc's tables come from malloc() through csc_default_alloc.cpp:5-8 when the caller passes

@@ -236,12 +236,18 @@ def test_device_resident_chunks_equal_host_path(prod):
     assert bytes(w.out) == prod.encode(data, 3, len(data))[1]
 
 
-def test_callbacks_and_error_codes(prod):
+def test_callbacks_and_error_codes(prod, orc, zalloc):
     from csc_amd.capi import BytesWriter, BytesReader
     data = cases.build([["text", 3, 0, 300000]])
     seen = []
     rc, s = prod.encode(data, 2, 1 << 20, progress=lambda a, b: seen.append((a, b)))
     assert rc == 0 and seen and seen[-1][0] == len(data) and 0 < seen[-1][1] < len(s)
+    # every (in, out) pair is the checker's: GetCompressedSize after each chunk (csc_enc.cpp:180-181), the decoder's after each run (csc_dec.cpp:761-762)
+    want = []
+    assert orc.encode(data, 2, 1 << 20, alloc=zalloc, progress=lambda a, b: want.append((a, b))) == (0, s) and seen == want
+    seen_d, want_d = [], []
+    assert prod.decode(s, progress=lambda a, b: seen_d.append((a, b))) == (0, data)
+    assert orc.decode(s, alloc=zalloc, progress=lambda a, b: want_d.append((a, b))) == (0, data) and seen_d == want_d and len(want_d) >= 2
     assert prod.encode(data, 2, 1 << 20, writer=BytesWriter(fail_after=5000))[0] == -97       # WRITE_ERROR
     assert prod.encode(data, 2, 1 << 20, reader=BytesReader(data, max_read=100000, fail_at=200000))[0] == -98   # READ_ERROR
     r = BytesReader(data)
