@@ -36,15 +36,33 @@ class CSAFrag(C.Structure):
                 ("size", C.c_uint64), ("posfile", C.c_uint64)]
 
 
+class CSADevFile(C.Structure):
+    """CSADevFile of include/csa_mi355x.h.  `name` is kept as an address: CSAMI_PlanDeviceLayout's names are not NUL-terminated."""
+    _fields_ = [("name", C.c_void_p), ("esize", C.c_int64), ("edate", C.c_int64), ("eattr", C.c_int64),
+                ("offset", C.c_uint64), ("size", C.c_uint64), ("nfrags", C.c_uint32), ("failed_frags", C.c_uint32)]
+
+
+class CSADevReadStats(C.Structure):
+    _fields_ = [("tasks", C.c_uint64), ("frags", C.c_uint64), ("waves", C.c_uint64), ("launches", C.c_uint64),
+                ("decode_launches", C.c_uint64), ("readback_bytes", C.c_uint64), ("raw_bytes", C.c_uint64),
+                ("verify_failures", C.c_uint32), ("reserved", C.c_uint32), ("kernel_ms", C.c_double), ("seconds_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
 LIST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(CSAFrag))
 
 SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", "CSA_ReadIndex",
            "CSA_Adler32", "CSAMI_Adler32Device", "CSA_DecimalTime", "CSA_UnixTime",
-           "CSAMI_AddShardEncode", "CSAMI_FreeBlob", "CSAMI_AddShardAssemble", "CSAMI_PlanInfo", "CSAMI_PlanShards", "CSA_IndexRoundTrip"]
+           "CSAMI_AddShardEncode", "CSAMI_FreeBlob", "CSAMI_AddShardAssemble", "CSAMI_PlanInfo", "CSAMI_PlanShards", "CSA_IndexRoundTrip",
+           "CSAMI_DeviceOpen", "CSAMI_DevicePlan", "CSAMI_DeviceRead", "CSAMI_DeviceClose", "CSAMI_PlanDeviceLayout", "CSAMI_DeviceKernelMs"]
 
 CSA_MAX_FRAGMENTS = 127
 CSA_TOO_MANY_FRAGMENTS = -94
 CSA_UNSAFE_NAME = -93
+CSCMI_DEVICE_ERROR = -95
+WRITE_ERROR = -97
 
 _lib = None
 
@@ -84,6 +102,21 @@ def lib():
         L.CSAMI_PlanInfo.restype = C.c_int
         L.CSA_IndexRoundTrip.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
         L.CSA_IndexRoundTrip.restype = C.c_int64
+        files = C.POINTER(CSADevFile)
+        L.CSAMI_DeviceOpen.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]
+        L.CSAMI_DeviceOpen.restype = C.c_int
+        L.CSAMI_DevicePlan.argtypes = [C.c_void_p, names, C.c_int, files, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]
+        L.CSAMI_DevicePlan.restype = C.c_int
+        L.CSAMI_DeviceRead.argtypes = [C.c_void_p, names, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(CSAOptions), files, C.c_uint32,
+                                       C.POINTER(CSADevReadStats)]
+        L.CSAMI_DeviceRead.restype = C.c_int
+        L.CSAMI_DeviceKernelMs.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+        L.CSAMI_DeviceKernelMs.restype = None
+        L.CSAMI_DeviceClose.argtypes = [C.c_void_p]
+        L.CSAMI_DeviceClose.restype = None
+        L.CSAMI_PlanDeviceLayout.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, names, C.c_int, files, C.c_uint32, C.POINTER(C.c_uint32),
+                                             C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]
+        L.CSAMI_PlanDeviceLayout.restype = C.c_int
         _lib = L
     return _lib
 
@@ -224,3 +257,113 @@ def adler32_device(device_ptr: int, nbytes: int, adler: int = 0) -> int:
     if rc != 0:
         raise RuntimeError(f"CSAMI_Adler32Device failed: {rc}")
     return int(out.value)
+
+
+# ---- device-resident read ----------------------------------------------------------------------------------------------
+
+def _file_dict(f: CSADevFile, name: str) -> dict:
+    return {"name": name, "esize": f.esize, "edate": f.edate, "eattr": f.eattr, "offset": f.offset, "size": f.size,
+            "nfrags": f.nfrags, "failed_frags": f.failed_frags}
+
+
+def plan_device_layout(raw_index: bytes, arc_size: int, names: Sequence[str] = ()):
+    """CSAMI_PlanDeviceLayout (host only): the layout DeviceArchive.extract gives these raw index bytes ->
+    (rc, [file dicts], dst_bytes, [raw size of every task that would be decoded, in decode order])"""
+    buf = (C.c_uint8 * max(len(raw_index), 1)).from_buffer_copy(raw_index or b"\0")
+    arr, n = _names(names)
+    nf, nt, total = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    rc = lib().CSAMI_PlanDeviceLayout(buf, len(raw_index), arc_size, arr, n, None, 0, C.byref(nf), C.byref(total), None, 0, C.byref(nt))
+    if rc != 0:
+        return rc, [], 0, []
+    files, tasks = (CSADevFile * max(nf.value, 1))(), (C.c_uint64 * max(nt.value, 1))()
+    rc = lib().CSAMI_PlanDeviceLayout(buf, len(raw_index), arc_size, arr, n, files, nf.value, C.byref(nf), C.byref(total), tasks, nt.value, C.byref(nt))
+    out = []
+    for f in files[:nf.value]:
+        ln = int.from_bytes(C.string_at(f.name - 4, 4), "little")          # the name lies in `buf`, its length in front of it
+        out.append(_file_dict(f, C.string_at(f.name, ln).decode("latin-1")))
+    return rc, out, int(total.value), list(tasks[:nt.value])
+
+
+class DeviceArchive:
+    """A `.csa` that lies in device memory (CSAMI_DeviceOpen ... CSAMI_DeviceClose): `csarc x` / `csarc t` without the archive,
+    the decoded tasks or the files crossing the bus.  torch is the plumbing: it owns the buffers and hands out views."""
+
+    def __init__(self, handle, tensor):
+        self._h, self._arc = handle, tensor           # the archive tensor must outlive the handle
+
+    @classmethod
+    def open(cls, tensor) -> "DeviceArchive":
+        """tensor: 1-d contiguous torch.uint8 CUDA tensor of any alignment.  Raises ValueError(rc) where CSAMI_DeviceOpen refuses it."""
+        import torch
+        if not (isinstance(tensor, torch.Tensor) and tensor.dtype == torch.uint8 and tensor.is_cuda and tensor.is_contiguous()
+                and tensor.dim() == 1):
+            raise TypeError("a contiguous 1-d torch.uint8 CUDA tensor")
+        torch.cuda.synchronize()                       # the tensor was filled on torch's stream, the library launches on its own
+        h = C.c_void_p()
+        rc = lib().CSAMI_DeviceOpen(C.c_void_p(tensor.data_ptr()), int(tensor.numel()), C.byref(h))
+        if rc != 0:
+            err = ValueError(f"CSAMI_DeviceOpen: {rc}")
+            err.rc = rc
+            raise err
+        return cls(h, tensor)
+
+    def _plan(self, names):
+        arr, n = _names(names)
+        nf, total = C.c_uint32(), C.c_uint64()
+        rc = lib().CSAMI_DevicePlan(self._h, arr, n, None, 0, C.byref(nf), C.byref(total))
+        if rc != 0:
+            raise ValueError(f"CSAMI_DevicePlan: {rc}")
+        return arr, n, int(nf.value), int(total.value)
+
+    def plan(self, names: Sequence[str] = ()):
+        """-> ([file dicts in index order], dst_bytes)"""
+        arr, n, nf, total = self._plan(names)
+        files = (CSADevFile * max(nf, 1))()
+        lib().CSAMI_DevicePlan(self._h, arr, n, files, nf, None, None)
+        return [_file_dict(f, C.string_at(f.name).decode("latin-1")) for f in files[:nf]], total
+
+    def _read(self, names, dst, opts):
+        import torch
+        arr, n, nf, total = self._plan(names)
+        files, st, o = (CSADevFile * max(nf, 1))(), CSADevReadStats(), options(**opts)
+        torch.cuda.synchronize()
+        rc = lib().CSAMI_DeviceRead(self._h, arr, n, C.c_void_p(dst.data_ptr()) if dst is not None else None,
+                                    int(dst.numel()) if dst is not None else 0, C.byref(o), files, nf, C.byref(st))
+        return rc, [_file_dict(f, C.string_at(f.name).decode("latin-1")) for f in files[:nf]], st.as_dict()
+
+    def extract(self, names: Sequence[str] = (), dst=None, **opts):
+        """`csarc x` -> (rc, {name: uint8 CUDA view of dst}, stats dict).  dst: a 1-d contiguous torch.uint8 CUDA tensor of any
+        alignment with at least plan(names)[1] bytes (allocated here when None); stats["files"] is the files table."""
+        import torch
+        if dst is None:
+            dst = torch.empty(max(self._plan(names)[3], 1), dtype=torch.uint8, device=self._arc.device)
+        elif not (isinstance(dst, torch.Tensor) and dst.dtype == torch.uint8 and dst.is_cuda and dst.is_contiguous() and dst.dim() == 1):
+            raise TypeError("dst: a contiguous 1-d torch.uint8 CUDA tensor")
+        rc, files, st = self._read(names, dst, opts)
+        st["files"] = files
+        views = {} if rc == WRITE_ERROR else {f["name"]: dst[f["offset"]:f["offset"] + f["size"]] for f in files}
+        return rc, views, st
+
+    def test(self, names: Sequence[str] = (), **opts):
+        """`csarc t` -> (rc, stats dict)"""
+        rc, files, st = self._read(names, None, opts)
+        st["files"] = files
+        return rc, st
+
+    def kernel_ms(self):
+        """HIP-event milliseconds of the last extract / test by kernel: (k_gather_extents, k_frag_pieces, k_frag_fold)"""
+        ms = (C.c_double * 3)()
+        lib().CSAMI_DeviceKernelMs(self._h, ms)
+        return tuple(ms)
+
+    def close(self):
+        if self._h:
+            lib().CSAMI_DeviceClose(self._h)
+            self._h = None
+        self._arc = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

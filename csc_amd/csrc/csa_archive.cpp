@@ -1543,3 +1543,416 @@ int64_t CSA_ReadIndex(const char *arcname, uint8_t *buf, uint64_t cap)
 }
 
 }   // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// device-resident read: CSAMI_DeviceOpen / Plan / Read / Close, CSAMI_PlanDeviceLayout (include/csa_mi355x.h).
+// Host side: the index, the layout of dst, the validation of everything the index says, the piece tables.  The bytes move in
+// csa_dev_kernels.hip (tables and copy: csa_dev_read.h) and in CSCMI_DecodeDeviceBatch.
+// ---------------------------------------------------------------------------------------------
+#include "csa_dev_read.h"
+
+void launch_gather_extents(const void *pieces, uint32_t npieces, hipStream_t st);
+void launch_frag_pieces(const void *pieces, void *sums, uint32_t npieces, bool store, hipStream_t st);
+void launch_frag_fold(const void *frags, const void *sums, void *out, uint32_t nfrags, hipStream_t st);
+
+struct CSADevArchive {
+    const uint8_t *arc = nullptr;
+    uint64_t arc_size = 0;
+    Index index;
+    BlockIndex abindex;
+    std::map<uint64_t, uint64_t> task_raw;     // bid -> raw size
+    uint64_t open_readback = 0;
+    double kernel_ms[3] = {0, 0, 0};
+};
+
+namespace {
+
+bool add_ok(uint64_t a, uint64_t b, uint64_t *out) { return !__builtin_add_overflow(a, b, out); }
+
+struct DevFilePlan { Index::const_iterator it; uint64_t offset, size; };
+struct DevFrag { uint32_t file; uint32_t checksum; uint64_t posblock, size, posfile; };
+struct DevTask { uint64_t bid = 0, total = 0, raw = 0; std::vector<DevFrag> frags; };
+struct DevLayout {
+    std::vector<DevFilePlan> files;
+    std::vector<DevTask> tasks;                // decode order
+    uint64_t dst_bytes = 0;
+};
+
+// A task's raw size: max(posblock + size) over ALL fragments of its bid.  false if any sum of the index wraps.
+bool dev_task_sizes(const Index &index, std::map<uint64_t, uint64_t> &raw)
+{
+    raw.clear();
+    for (const auto &kv : index)
+        for (const CSAFrag &f : kv.second.frags) {
+            uint64_t end, fend;
+            if (!add_ok(f.posblock, f.size, &end) || !add_ok(f.posfile, f.size, &fend)) return false;
+            uint64_t &r = raw[f.bid];
+            r = std::max(r, end);
+        }
+    return true;
+}
+
+// The layout of dst and the tasks to decode for a selection.  false if the sum wraps.
+bool dev_layout(const Index &index, const std::map<uint64_t, uint64_t> &raw, const Selection &sel, DevLayout &L)
+{
+    std::map<uint64_t, size_t> idmap;
+    uint64_t off = 0;
+    for (Index::const_iterator it = index.begin(); it != index.end(); ++it) {
+        if (!sel.has(it->first.c_str())) continue;
+        uint64_t size = 0;
+        const uint32_t fi = (uint32_t)L.files.size();
+        for (const CSAFrag &f : it->second.frags) {
+            size = std::max(size, f.posfile + f.size);                     // (checked by dev_task_sizes)
+            if (!f.size) continue;
+            auto m = idmap.find(f.bid);
+            if (m == idmap.end()) {
+                m = idmap.insert(std::make_pair((uint64_t)f.bid, L.tasks.size())).first;
+                L.tasks.push_back(DevTask());
+                L.tasks.back().bid = f.bid;
+                L.tasks.back().raw = raw.at(f.bid);
+            }
+            DevTask &t = L.tasks[m->second];
+            t.frags.push_back(DevFrag{fi, f.checksum, f.posblock, f.size, f.posfile});
+            if (!add_ok(t.total, f.size, &t.total)) return false;
+        }
+        L.files.push_back(DevFilePlan{it, off, size});
+        uint64_t r;
+        if (!add_ok(size, 15, &r) || !add_ok(off, r & ~15ull, &off)) return false;
+    }
+    L.dst_bytes = off;
+    std::sort(L.tasks.begin(), L.tasks.end(), [](const DevTask &a, const DevTask &b) {                        // csarc.cpp:430
+        return a.total != b.total ? a.total > b.total : a.bid < b.bid;
+    });
+    return true;
+}
+
+void dev_fill_files(const DevLayout &L, CSADevFile *files, uint32_t cap)
+{
+    for (size_t i = 0; files && i < L.files.size() && i < cap; i++) {
+        const DevFilePlan &p = L.files[i];
+        CSADevFile &f = files[i];
+        f.name = p.it->first.c_str();
+        f.esize = p.it->second.esize; f.edate = p.it->second.edate; f.eattr = p.it->second.eattr;
+        f.offset = p.offset; f.size = p.size;
+        f.nfrags = (uint32_t)p.it->second.frags.size(); f.failed_frags = 0;
+    }
+}
+
+// AsyncArchiveReader (csa_io.h:466-542) over a buffer: the task's archive blocks, each clipped to the archive; the first one
+// that is cut short ends the stream (ExtentSource: a short read is end of file).  false if the total wraps.
+bool dev_stream_extents(const std::vector<Extent> &in, uint64_t arc_size, std::vector<Extent> &out, uint64_t &total)
+{
+    out.clear();
+    total = 0;
+    for (const Extent &x : in) {
+        const uint64_t avail = x.off < arc_size ? std::min<uint64_t>(x.size, arc_size - x.off) : 0;
+        if (avail) {
+            out.push_back(Extent{x.off, avail});
+            if (!add_ok(total, avail, &total)) return false;
+        }
+        if (avail < x.size) break;
+    }
+    return true;
+}
+
+struct DevBuf {                                // device memory released at scope end
+    void *p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    bool alloc(uint64_t n) { return n <= (uint64_t)SIZE_MAX && HIP_OK(hipMalloc(&p, (size_t)std::max<uint64_t>(n, 16))); }
+    bool upload(const void *src, uint64_t n) { return alloc(n) && (!n || HIP_OK(hipMemcpy(p, src, (size_t)n, hipMemcpyHostToDevice))); }
+};
+
+struct DevTimer {                              // HIP-event time of this layer's three launches, by kernel
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    hipStream_t st = nullptr;
+    bool ok = false;
+    DevTimer() { ok = HIP_OK(hipEventCreate(&ev[0])) && HIP_OK(hipEventCreate(&ev[1])); }
+    ~DevTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    void begin() { (void)hipEventRecord(ev[0], st); }
+    bool end(double *ms)                       // waits for the launch
+    {
+        float f = 0;
+        if (!HIP_OK(hipGetLastError()) || !HIP_OK(hipEventRecord(ev[1], st)) || !HIP_OK(hipEventSynchronize(ev[1]))) return false;
+        if (HIP_OK(hipEventElapsedTime(&f, ev[0], ev[1]))) *ms += f;
+        return true;
+    }
+};
+
+// One wave: tasks [first, first + count) of L.  Returns 0, -1 (a stream failed) or CSCMI_DEVICE_ERROR.
+int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t count, uint8_t *dst, std::vector<uint32_t> &failed,
+                  CSADevReadStats &S, DevTimer &tm)
+{
+    using namespace csadev;
+    static const std::vector<Extent> kNoBlocks;
+    int worst = 0;
+    // 1. the streams: where each task's coded bytes lie, what has to be gathered, where its decoded bytes go
+    std::vector<std::vector<Extent>> ext(count);
+    std::vector<uint64_t> total(count, 0), gat_off(count, 0), raw_off(count, 0);
+    uint64_t gat_bytes = 0, raw_bytes = 0;
+    for (size_t k = 0; k < count; k++) {
+        const DevTask &t = L.tasks[first + k];
+        auto ab = A.abindex.find(t.bid);
+        if (!dev_stream_extents(ab == A.abindex.end() ? kNoBlocks : ab->second, A.arc_size, ext[k], total[k])) return CSCMI_DEVICE_ERROR;
+        uint64_t r;
+        if (total[k] > CSC_PROP_SIZE && ext[k].size() > 1) {
+            gat_off[k] = gat_bytes;
+            if (!add_ok(total[k] - CSC_PROP_SIZE, 255, &r) || !add_ok(gat_bytes, r & ~255ull, &gat_bytes)) return CSCMI_DEVICE_ERROR;
+        }
+        raw_off[k] = raw_bytes;
+        if (!add_ok(t.raw, 255, &r) || !add_ok(raw_bytes, r & ~255ull, &raw_bytes)) return CSCMI_DEVICE_ERROR;
+    }
+    DevBuf d_gat, d_raw, d_props;
+    if (!d_gat.alloc(gat_bytes) || !d_raw.alloc(raw_bytes) || !d_props.alloc(16 * count)) return CSCMI_DEVICE_ERROR;
+
+    // 2. gather: the property bytes of every task (they may span blocks) and the streams of more than one block
+    std::vector<CopyPiece> gp;
+    for (size_t k = 0; k < count; k++) {
+        uint64_t pos = 0;                                                    // position in the task's stream
+        for (const Extent &x : ext[k]) {
+            const uint8_t *src = A.arc + x.off;
+            uint64_t n = x.size;
+            if (pos < CSC_PROP_SIZE) {
+                const uint64_t h = std::min<uint64_t>(CSC_PROP_SIZE - pos, n);
+                gp.push_back(CopyPiece{src, (uint8_t *)d_props.p + 16 * k + pos, (uint32_t)h, 0});
+                src += h; n -= h; pos += h;
+            }
+            if (ext[k].size() > 1 && n)
+                piece_split(src, (uint8_t *)d_gat.p + gat_off[k] + (pos - CSC_PROP_SIZE), n, kGatherPiece,
+                            [&](uint64_t, const CopyPiece &p) { gp.push_back(p); });
+            pos += n;
+        }
+    }
+    if (gp.size() > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
+    std::vector<uint8_t> props(16 * count, 0);
+    {
+        DevBuf d_gp;
+        if (!d_gp.upload(gp.data(), gp.size() * sizeof(CopyPiece))) return CSCMI_DEVICE_ERROR;
+        tm.begin();
+        launch_gather_extents(d_gp.p, (uint32_t)gp.size(), tm.st);
+        S.launches++;
+        if (!tm.end(&A.kernel_ms[0])) return CSCMI_DEVICE_ERROR;
+        if (!HIP_OK(hipMemcpy(props.data(), d_props.p, props.size(), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+        S.readback_bytes += props.size();
+    }
+
+    // 3. decode: csa_worker.cpp:59-90 for every task of the wave at once
+    std::vector<CSCMIDevDecode> jobs;
+    std::vector<size_t> job_task;
+    std::vector<uint64_t> produced(count, 0);
+    for (size_t k = 0; k < count; k++) {
+        if (total[k] < CSC_PROP_SIZE) { worst = -1; continue; }               // csa_worker.cpp:77-80: no property bytes, no decoder
+        CSCMIDevDecode j;
+        memset(&j, 0, sizeof(j));
+        CSCDec_ReadProperties(&j.props, props.data() + 16 * k);
+        j.src = ext[k].size() > 1 ? (const uint8_t *)d_gat.p + gat_off[k] : A.arc + ext[k][0].off + CSC_PROP_SIZE;
+        j.src_size = (size_t)(total[k] - CSC_PROP_SIZE);
+        j.dst = (uint8_t *)d_raw.p + raw_off[k];
+        j.dst_cap = (size_t)L.tasks[first + k].raw;
+        jobs.push_back(j);
+        job_task.push_back(k);
+    }
+    if (!jobs.empty()) {
+        CSCMIDevDecodeStats ds;
+        memset(&ds, 0, sizeof(ds));
+        if (CSCMI_DecodeDeviceBatch((int)jobs.size(), jobs.data(), NULL, &ds) != 0) return CSCMI_DEVICE_ERROR;
+        S.decode_launches += ds.launches;
+        for (size_t i = 0; i < jobs.size(); i++) {
+            if (jobs[i].rc == CSCMI_DEVICE_ERROR) return CSCMI_DEVICE_ERROR;
+            if (jobs[i].rc != 0) worst = -1;                                   // (WRITE_ERROR: more than the raw size -- a decode error here)
+            produced[job_task[i]] = std::min<uint64_t>(jobs[i].produced, jobs[i].dst_cap);   // a failed stream still delivered this much
+        }
+    }
+
+    // 4. scatter and verify: the fragments at least one byte of which was delivered, clipped to what was delivered
+    std::vector<CopyPiece> fp;
+    std::vector<FragFold> ff;
+    std::vector<uint32_t> ff_file;
+    for (size_t k = 0; k < count; k++) {
+        const DevTask &t = L.tasks[first + k];
+        for (const DevFrag &f : t.frags) {
+            if (f.posblock >= produced[k]) continue;
+            const uint64_t n = std::min<uint64_t>(f.size, produced[k] - f.posblock);
+            const uint64_t np = piece_count(n, kFragPiece);
+            if (fp.size() + np > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
+            ff.push_back(FragFold{n, (uint32_t)fp.size(), (uint32_t)np, f.checksum, 0});
+            ff_file.push_back(f.file);
+            piece_split((const uint8_t *)d_raw.p + raw_off[k] + f.posblock, dst ? dst + L.files[f.file].offset + f.posfile : nullptr, n, kFragPiece,
+                        [&](uint64_t, const CopyPiece &p) { fp.push_back(p); });
+        }
+    }
+    DevBuf d_fp, d_ff, d_sums, d_res;
+    if (!d_fp.upload(fp.data(), fp.size() * sizeof(CopyPiece)) || !d_ff.upload(ff.data(), ff.size() * sizeof(FragFold))
+        || !d_sums.alloc(fp.size() * sizeof(PieceSums)) || !d_res.alloc(ff.size() * sizeof(FragResult))) return CSCMI_DEVICE_ERROR;
+    tm.begin();
+    launch_frag_pieces(d_fp.p, d_sums.p, (uint32_t)fp.size(), dst != nullptr, tm.st);
+    S.launches++;
+    if (!tm.end(&A.kernel_ms[1])) return CSCMI_DEVICE_ERROR;
+    tm.begin();
+    launch_frag_fold(d_ff.p, d_sums.p, d_res.p, (uint32_t)ff.size(), tm.st);
+    S.launches++;
+    if (!tm.end(&A.kernel_ms[2])) return CSCMI_DEVICE_ERROR;
+    std::vector<FragResult> res(ff.size());
+    if (!res.empty() && !HIP_OK(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(FragResult), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+    S.readback_bytes += res.size() * sizeof(FragResult);
+    for (size_t i = 0; i < res.size(); i++)
+        if (!res[i].ok) {
+            fprintf(stderr, "******** %s extraction/verify failed\n", L.files[ff_file[i]].it->first.c_str());   // csa_io.h:332,398
+            failed[ff_file[i]]++;
+            S.verify_failures++;
+        }
+    return worst;
+}
+
+}   // namespace
+
+extern "C" {
+
+int CSAMI_DeviceOpen(const void *arc_dev, uint64_t arc_size, CSADevArchive **out)
+{
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
+    const uint8_t *arc = (const uint8_t *)arc_dev;
+    uint8_t hdr[kHeaderSize];
+    if (!arc || arc_size < kHeaderSize) { fprintf(stderr, "Invalid csarc file\n"); return 1; }
+    if (!HIP_OK(hipMemcpy(hdr, arc, kHeaderSize, hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+    if (!header_ok(hdr)) { fprintf(stderr, "Invalid csarc file\n"); return 1; }
+    const uint64_t index_pos = load_le(hdr + 8, 8);
+    const uint32_t csize = (uint32_t)load_le(hdr + 16, 4), rsize = (uint32_t)load_le(hdr + 20, 4);
+    if (index_pos > arc_size || csize > arc_size - index_pos || csize < CSC_PROP_SIZE) { fprintf(stderr, "Invalid csarc file\n"); return -1; }
+    uint8_t ph[CSC_PROP_SIZE];
+    if (!HIP_OK(hipMemcpy(ph, arc + index_pos, CSC_PROP_SIZE, hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+    std::vector<uint8_t> raw(rsize);
+    {
+        DevBuf d_raw;
+        if (!d_raw.alloc(rsize)) return CSCMI_DEVICE_ERROR;
+        CSCMIDevDecode j;
+        memset(&j, 0, sizeof(j));
+        CSCDec_ReadProperties(&j.props, ph);
+        j.src = arc + index_pos + CSC_PROP_SIZE;
+        j.src_size = csize - CSC_PROP_SIZE;
+        j.dst = d_raw.p;
+        j.dst_cap = rsize;
+        if (CSCMI_DecodeDeviceBatch(1, &j, NULL, NULL) != 0 || j.rc == CSCMI_DEVICE_ERROR) return CSCMI_DEVICE_ERROR;
+        if (j.rc != 0 || j.produced != rsize) { fprintf(stderr, "Invalid csarc file (index)\n"); return -1; }
+        if (rsize && !HIP_OK(hipMemcpy(raw.data(), d_raw.p, rsize, hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+    }
+    CSADevArchive *A = new CSADevArchive();
+    A->arc = arc;
+    A->arc_size = arc_size;
+    A->open_readback = kHeaderSize + CSC_PROP_SIZE + rsize;
+    if (!unpack_index(A->index, A->abindex, raw.data(), rsize) || !dev_task_sizes(A->index, A->task_raw)) {
+        fprintf(stderr, "Invalid csarc file (index)\n");
+        delete A;
+        return -1;
+    }
+    *out = A;
+    return 0;
+}
+
+int CSAMI_DevicePlan(CSADevArchive *a, const char *const *names, int nnames,
+                     CSADevFile *files, uint32_t cap, uint32_t *n_files, uint64_t *dst_bytes)
+{
+    DevLayout L;
+    if (!a || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L)) return -1;
+    dev_fill_files(L, files, cap);
+    if (n_files) *n_files = (uint32_t)L.files.size();
+    if (dst_bytes) *dst_bytes = L.dst_bytes;
+    return 0;
+}
+
+int CSAMI_DeviceRead(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
+                     const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st)
+{
+    const double t0 = now_s();
+    CSADevReadStats S;
+    memset(&S, 0, sizeof(S));
+    if (st) *st = S;
+    DevLayout L;
+    if (!a || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L)) return -1;
+    dev_fill_files(L, files, cap);
+    if (dst && dst_cap < L.dst_bytes) return WRITE_ERROR;
+    CSAOptions o;
+    if (opt) o = *opt; else CSA_OptionsInit(&o);
+    a->kernel_ms[0] = a->kernel_ms[1] = a->kernel_ms[2] = 0;
+
+    size_t mem_free = 0, mem_total = 0;
+    if (!HIP_OK(hipMemGetInfo(&mem_free, &mem_total))) return CSCMI_DEVICE_ERROR;
+    const uint64_t budget = o.hbm_budget ? o.hbm_budget : (uint64_t)mem_free / 4 * 3;
+    const size_t width = o.device_streams > 0 ? (size_t)o.device_streams : L.tasks.size();
+    DevTimer tm;
+    if (!tm.ok) return CSCMI_DEVICE_ERROR;
+    std::vector<uint32_t> failed(L.files.size(), 0);
+    int worst = 0;
+    S.readback_bytes = a->open_readback;
+    for (size_t first = 0; first < L.tasks.size() && worst != CSCMI_DEVICE_ERROR;) {
+        size_t count = 0;
+        uint64_t mem = 0;
+        while (first + count < L.tasks.size() && count < width) {
+            // the task's decoded bytes and (at most) a copy of its stream, plus what its decoder holds: the dictionary (bounded by
+            // the raw size and by 1 GiB) and ~24 MiB of rings and buffers, as read_archive reckons
+            const uint64_t raw = L.tasks[first + count].raw;
+            uint64_t need = std::min<uint64_t>(std::max<uint64_t>(raw, 1u << 20), 1ull << 30) + (24ull << 20);
+            if (!add_ok(need, raw, &need) || !add_ok(need, raw, &need)) need = UINT64_MAX;
+            if (count && (mem + need < mem || mem + need > budget)) break;
+            mem += need;
+            count++;
+        }
+        int r = dev_read_wave(*a, L, first, count, (uint8_t *)dst, failed, S, tm);
+        if (r < 0 && worst != CSCMI_DEVICE_ERROR) worst = r;
+        S.waves++;
+        for (size_t k = first; k < first + count; k++) { S.tasks++; S.frags += L.tasks[k].frags.size(); S.raw_bytes += L.tasks[k].total; }
+        first += count;
+    }
+    for (size_t i = 0; files && i < L.files.size() && i < cap; i++) files[i].failed_frags = failed[i];
+    S.kernel_ms = a->kernel_ms[0] + a->kernel_ms[1] + a->kernel_ms[2];
+    S.seconds_total = now_s() - t0;
+    if (st) *st = S;
+    if (worst == CSCMI_DEVICE_ERROR) return CSCMI_DEVICE_ERROR;
+    if (worst < 0) {
+        fprintf(stderr, "Extraction error, archive corrupted\n");           // csarc.cpp:464-467
+        return -1;
+    }
+    return 0;
+}
+
+void CSAMI_DeviceKernelMs(const CSADevArchive *a, double ms[3])
+{
+    for (int i = 0; i < 3; i++) ms[i] = a ? a->kernel_ms[i] : 0;
+}
+
+void CSAMI_DeviceClose(CSADevArchive *a) { delete a; }
+
+int CSAMI_PlanDeviceLayout(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
+                           CSADevFile *files, uint32_t cap, uint32_t *n_files, uint64_t *dst_bytes,
+                           uint64_t *task_raw_sizes, uint32_t task_cap, uint32_t *n_tasks)
+{
+    Index index;
+    BlockIndex abindex;
+    std::map<uint64_t, uint64_t> raw;
+    DevLayout L;
+    if (!raw_index || !unpack_index(index, abindex, raw_index, raw_size) || !dev_task_sizes(index, raw)) return -1;
+    for (const auto &kv : abindex)
+        for (const Extent &x : kv.second) {
+            uint64_t end;
+            if (!add_ok(x.off, x.size, &end) || end > arc_size) return -1;
+        }
+    if (!dev_layout(index, raw, make_selection(names, nnames), L)) return -1;
+    dev_fill_files(L, files, cap);
+    // the names: inside raw_index, where the parse above found them (the first entry of a name wins, as in the map)
+    std::map<std::string, const char *> where;
+    uint64_t pos = 4;
+    for (uint32_t i = 0, n = (uint32_t)load_le(raw_index, 4); i < n; i++) {
+        const uint32_t ln = (uint32_t)load_le(raw_index + pos, 4);
+        const char *p = (const char *)raw_index + pos + 4;
+        where.insert(std::make_pair(std::string(p, ln), p));
+        const int nfr = (int8_t)raw_index[pos + 4 + ln + 24];
+        pos += 4 + (uint64_t)ln + 25 + 32ull * (uint64_t)nfr;
+    }
+    for (size_t i = 0; files && i < L.files.size() && i < cap; i++) files[i].name = where[L.files[i].it->first];
+    if (n_files) *n_files = (uint32_t)L.files.size();
+    if (dst_bytes) *dst_bytes = L.dst_bytes;
+    for (size_t i = 0; task_raw_sizes && i < L.tasks.size() && i < task_cap; i++) task_raw_sizes[i] = L.tasks[i].raw;
+    if (n_tasks) *n_tasks = (uint32_t)L.tasks.size();
+    return 0;
+}
+
+}   // extern "C"

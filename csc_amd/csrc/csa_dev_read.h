@@ -1,0 +1,162 @@
+// csa_dev_read.h -- the device-resident archive read (CSAMI_DeviceRead, include/csa_mi355x.h) below the host planner: the piece
+// tables its three kernels walk, the copy between two byte ranges of ANY alignment, the adler32 sums taken in the same pass, and
+// the fold of a fragment's pieces.  Compiles for the host (plain C++: tests/test_archive_device_host.py runs
+// tests/model/csa_dev_model.cpp with g++ and the sanitizers) and for the device (csa_dev_kernels.hip), so the model runs the text
+// the kernels run.
+//
+// What the reference does with these bytes: AsyncArchiveReader (csa_io.h:466-542) serves a task's archive blocks back to back --
+// here k_gather_extents copies them into one range; AsyncFileWriter (csa_io.h:274-408) cuts the decoded task into its fragments,
+// writes each at its file offset and folds adler32 (csa_adler32.cpp:63-129) over it -- here k_frag_pieces and k_frag_fold.
+//
+// adler32 piecewise, as csa_kernels.hip: a piece of `len` bytes gives A = sum(b_i) and B = sum((len - i) * b_i) as plain integers,
+// and consecutive pieces fold as b' = b + len * a + B, a' = a + A (mod 65521), seed 0.
+//
+// The template parameter PLANT switches one deliberate mistake on (0: none).  The product instantiates 0 only; the model runs each
+// of the others and has to see it caught by a named case.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define CSADEV_FHD __host__ __device__ inline
+#else
+#define CSADEV_FHD inline
+#endif
+
+namespace csadev {
+
+constexpr uint32_t kThreads = 256;              // workgroup of k_gather_extents and k_frag_pieces
+constexpr uint32_t kGatherPiece = 65536;        // bytes of an extent one workgroup copies
+constexpr uint32_t kFragPiece = 16384;          // bytes of a fragment one workgroup sums (and stores)
+constexpr uint32_t kAdlerBase = 65521;
+
+enum Plant { kPlantNone = 0, kPlantTailDropped = 1, kPlantWeightOffByOne = 2, kPlantFoldLastLen = 3, kPlantHeadWrongPointer = 4 };
+
+struct CopyPiece {         // one workgroup of k_gather_extents / k_frag_pieces
+    const uint8_t *src;
+    uint8_t *dst;          // k_frag_pieces<false>: unused
+    uint32_t len;          // <= kGatherPiece / kFragPiece
+    uint32_t pad;
+};
+struct PieceSums { uint64_t a, b; };
+struct FragFold {          // one lane of k_frag_fold
+    uint64_t size;         // the fragment's bytes that were delivered (clipped to its task's `produced`)
+    uint32_t first;        // its first piece; the pieces of a fragment are consecutive
+    uint32_t npieces;
+    uint32_t checksum;     // the index's
+    uint32_t pad;
+};
+struct FragResult { uint32_t adler, ok; };      // all the host reads back of a fragment
+
+CSADEV_FHD uint64_t piece_count(uint64_t size, uint32_t piece) { return (size + piece - 1) / piece; }
+
+// src[0, size) -> dst[0, size) in pieces of at most `piece` bytes: put(k, CopyPiece) for k = 0 .. piece_count - 1.  dst may be NULL.
+template <class Put>
+CSADEV_FHD uint64_t piece_split(const uint8_t *src, uint8_t *dst, uint64_t size, uint32_t piece, Put put)
+{
+    uint64_t k = 0;
+    for (uint64_t off = 0; off < size; off += piece, k++) {
+        CopyPiece p;
+        p.src = src + off;
+        p.dst = dst ? dst + off : nullptr;
+        p.len = (uint32_t)(size - off < piece ? size - off : piece);
+        p.pad = 0;
+        put(k, p);
+    }
+    return k;
+}
+
+struct alignas(16) Vec16 { uint32_t w[4]; };
+
+// the four bytes of w sit at piece positions i0 .. i0 + 3 (little endian), all inside [0, len); wl = len (the weight of byte 0)
+CSADEV_FHD void sum_word(uint32_t w, uint32_t i0, uint32_t wl, uint64_t &a, uint64_t &b)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t s = __builtin_amdgcn_sad_u8(w, 0u, 0u);                      // b0+b1+b2+b3
+    const uint32_t t = __builtin_amdgcn_udot4(w, 0x03020100u, 0u, false);       // 0*b0+1*b1+2*b2+3*b3
+#else
+    const uint32_t b0 = w & 255u, b1 = (w >> 8) & 255u, b2 = (w >> 16) & 255u, b3 = w >> 24;
+    const uint32_t s = b0 + b1 + b2 + b3, t = b1 + 2 * b2 + 3 * b3;
+#endif
+    a += s;
+    b += (uint64_t)(wl - i0) * s - t;
+}
+
+// Thread `tid` of `nthreads`: its share of src[0, n) -- copied to dst[0, n) (STORE) and/or summed into a, b as one piece of n bytes
+// (SUM; the caller adds the threads' a and b up).  n <= 65536.  src and dst have any alignment.  Nothing outside src[0, n) is
+// loaded, not even by an aligned 16-byte window, and nothing outside dst[0, n) is stored.
+//
+// Up to 15 head bytes bring the anchor (dst with STORE, else src) to a 16-byte line and up to 15 tail bytes end the range: those
+// are byte accesses.  Between them every unit is one 16-byte store of source words funnel-shifted into place, from two aligned
+// 16-byte loads; a unit whose load window would begin before src or end behind src + n (the first and the last, at most) takes
+// its 16 bytes one by one.
+template <bool STORE, bool SUM, int PLANT = kPlantNone>
+CSADEV_FHD void copy_sum(uint8_t *dst, const uint8_t *src, uint32_t n, uint32_t tid, uint32_t nthreads, uint64_t &a, uint64_t &b)
+{
+    const uint8_t *anchor = STORE && PLANT != kPlantHeadWrongPointer ? (const uint8_t *)dst : src;
+    uint32_t head = (0u - (uint32_t)(uintptr_t)anchor) & 15u;
+    if (head > n) head = n;
+    const uint32_t units = (n - head) >> 4, tail = PLANT == kPlantTailDropped ? 0u : (n - head) & 15u;
+    const uint32_t wl = PLANT == kPlantWeightOffByOne ? n - 1 : n;
+    if (tid < head) {
+        const uint32_t v = src[tid];
+        if (STORE) dst[tid] = (uint8_t)v;
+        if (SUM) { a += v; b += (uint64_t)(wl - tid) * v; }
+    }
+    // (the tail from the far end of the workgroup: the head's lanes are busy)
+    if (nthreads - 1 - tid < tail) {
+        const uint32_t k = head + 16 * units + (nthreads - 1 - tid);
+        const uint32_t v = src[k];
+        if (STORE) dst[k] = (uint8_t)v;
+        if (SUM) { a += v; b += (uint64_t)(wl - k) * v; }
+    }
+    const uint8_t *s0 = src + head;                                   // unit i is source bytes [s0 + 16 i, s0 + 16 i + 16)
+    const uint32_t m = (uint32_t)(uintptr_t)s0 & 15u;
+    const uintptr_t base = (uintptr_t)s0 - m;                         // aligned; vector i of it covers source bytes [16 i - m, 16 i - m + 16) of s0
+    const uint32_t sw = m >> 2, sb = 8 * (m & 3u);
+    for (uint32_t i = tid; i < units; i += nthreads) {
+        Vec16 o;
+        if (m == 0) {
+            o = *(const Vec16 *)(base + 16ull * i);
+        } else if (head + 16 * i >= m && head + 16 * i + 32 <= n + m) {       // the window [16 i - m, 16 i - m + 32) of s0 lies in src[0, n)
+            const Vec16 x = *(const Vec16 *)(base + 16ull * i), y = *(const Vec16 *)(base + 16ull * i + 16);
+            const uint32_t t0 = (sw & 2u) ? x.w[2] : x.w[0], t1 = (sw & 2u) ? x.w[3] : x.w[1], t2 = (sw & 2u) ? y.w[0] : x.w[2],
+                           t3 = (sw & 2u) ? y.w[1] : x.w[3], t4 = (sw & 2u) ? y.w[2] : y.w[0], t5 = (sw & 2u) ? y.w[3] : y.w[1];
+            const uint32_t u0 = (sw & 1u) ? t1 : t0, u1 = (sw & 1u) ? t2 : t1, u2 = (sw & 1u) ? t3 : t2, u3 = (sw & 1u) ? t4 : t3,
+                           u4 = (sw & 1u) ? t5 : t4;
+            o.w[0] = (uint32_t)((((uint64_t)u1 << 32) | u0) >> sb);
+            o.w[1] = (uint32_t)((((uint64_t)u2 << 32) | u1) >> sb);
+            o.w[2] = (uint32_t)((((uint64_t)u3 << 32) | u2) >> sb);
+            o.w[3] = (uint32_t)((((uint64_t)u4 << 32) | u3) >> sb);
+        } else {
+            const uint8_t *p = s0 + 16 * i;
+            for (uint32_t k = 0; k < 4; k++)
+                o.w[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
+        }
+        if (STORE) *(Vec16 *)(dst + head + 16 * i) = o;
+        if (SUM) {
+            const uint32_t i0 = head + 16 * i;
+            sum_word(o.w[0], i0, wl, a, b);
+            sum_word(o.w[1], i0 + 4, wl, a, b);
+            sum_word(o.w[2], i0 + 8, wl, a, b);
+            sum_word(o.w[3], i0 + 12, wl, a, b);
+        }
+    }
+}
+
+// adler32 (seed 0) of a fragment of `size` bytes from the sums of its piece_count(size, kFragPiece) consecutive pieces; sums(k)
+// returns piece k's PieceSums
+template <int PLANT = kPlantNone, class Sums>
+CSADEV_FHD uint32_t fold_pieces(Sums sums, uint32_t npieces, uint64_t size)
+{
+    uint64_t a = 0, b = 0;
+    for (uint32_t k = 0; k < npieces; k++) {
+        uint64_t left = size - (uint64_t)(PLANT == kPlantFoldLastLen ? npieces - 1 : k) * kFragPiece;
+        const uint64_t len = left < kFragPiece ? left : kFragPiece;
+        const PieceSums s = sums(k);
+        b = (b + len * a + s.b % kAdlerBase) % kAdlerBase;
+        a = (a + s.a % kAdlerBase) % kAdlerBase;
+    }
+    return (uint32_t)(a | (b << 16));
+}
+
+}  // namespace csadev

@@ -150,6 +150,92 @@ int64_t CSA_ReadIndex(const char *arcname, uint8_t *buf, uint64_t cap);
 uint32_t CSA_Adler32(uint32_t adler, const uint8_t *buf, uint64_t len);
 int CSAMI_Adler32Device(uint32_t adler, const void *device_ptr, uint64_t len, uint32_t *out);
 
+/* ---- device-resident archive read: a .csa that lies in device memory to file bytes in device memory; not in the reference ----
+ *
+ * `csarc x` / `csarc t` (CSArc::Extract csarc.cpp:600-650, CSArc::Test :667-700, decompress_mt :411-470) for an archive the
+ * caller already holds in HBM.  No archive block, no decoded run and no file byte crosses the bus: the task streams are decoded
+ * where they lie by CSCMI_DecodeDeviceBatch, and what the reference's reader and writer threads do around the decoder is three
+ * kernels of this layer per wave of tasks:
+ *   k_gather_extents   AsyncArchiveReader (csa_io.h:466-542): a task's archive blocks back to back.  A task whose stream is ONE
+ *                      block is decoded in place from the archive and not copied.
+ *   k_frag_pieces      AsyncFileWriter (csa_io.h:274-408): each fragment from its task's decoded bytes to its place in dst, and
+ *                      adler32's partial sums (csa_adler32.cpp:63-129) in the same pass; without dst (csarc t) the sums alone
+ *   k_frag_fold        the sums of a fragment folded and compared with the index's checksum (csa_io.h:331-332,397-399)
+ * The host reads back the 24 header bytes, the index, the 10 property bytes of every task and 8 bytes per fragment.
+ *
+ * The layout of dst, shared by CSAMI_DevicePlan, CSAMI_DeviceRead and CSAMI_PlanDeviceLayout: the selected entries in index order
+ * (byte-wise by name, std::map of csa_typedef.h:50), selected by the rule of CSA_List (isselected, csarc.cpp:807-816; no names =
+ * all).  An entry's `size` is max(posfile + size) over its fragments, 0 for directories, empty files and files the index gives no
+ * fragment; its `offset` is the sum of the earlier entries' sizes, each rounded up to 16; dst_bytes is that sum after the last.
+ * The unsafe-name rule of CSA_Extract does NOT apply: no name reaches a file system here, so `..` entries are listed and read.
+ *
+ * A task (archive-blocks id `bid`) is decoded when a selected fragment of non-zero size lies in it.  Its raw size -- the capacity
+ * it is decoded into -- is max(posblock + size) over ALL fragments of the index with that bid, selected or not.  Tasks go largest
+ * first (csarc.cpp:430), in waves sized by o->hbm_budget (0 = 3/4 of the free device memory; o == NULL = defaults) and
+ * o->device_streams (0 = no limit); a wave's buffers are released before the next one's are taken.
+ *
+ * Safety contract.  Every extent, fragment and size of the index is validated on the host, in overflow-checked 64-bit arithmetic,
+ * before the first launch.  Nothing outside [arc, arc + arc_size) is loaded, not even by an aligned 16-byte window, and nothing
+ * outside [dst, dst + dst_bytes) is stored; bytes of dst that no delivered fragment covers (rounding gaps, holes, everything at and
+ * behind dst_bytes) stay untouched.  An archive block that passes arc_size is clipped there and ends its task's stream -- the short
+ * read AsyncArchiveReader turns into end of file -- so the stream fails in the decoder, not in a kernel.  A fragment is clipped to
+ * what its task's decoder produced.  Sizes whose buffers cannot be allocated give CSCMI_DEVICE_ERROR.
+ * The archive buffer must stay valid and unchanged from CSAMI_DeviceOpen until CSAMI_DeviceClose; dst must not overlap it. */
+typedef struct CSADevArchive CSADevArchive;                 /* opaque */
+typedef struct CSADevFile {
+    const char *name;        /* owned by the handle, valid until CSAMI_DeviceClose (CSAMI_PlanDeviceLayout: see there) */
+    int64_t esize, edate, eattr;   /* as CSA_List reports them */
+    uint64_t offset;         /* into dst; a multiple of 16 */
+    uint64_t size;           /* max(posfile + size) over the entry's fragments, 0 without any */
+    uint32_t nfrags, failed_frags;   /* failed_frags: CSAMI_DeviceRead only, else 0 */
+} CSADevFile;
+typedef struct CSADevReadStats {
+    uint64_t tasks, frags, waves;   /* tasks decoded; their selected fragments of non-zero size; waves */
+    uint64_t launches;          /* gather + scatter + fold launches of THIS layer: 3 * waves */
+    uint64_t decode_launches;   /* what CSCMI_DecodeDeviceBatch reports, summed over the waves */
+    uint64_t readback_bytes;    /* device-to-host bytes of this layer: CSAMI_DeviceOpen's 24 + 10 + index raw size, plus at most
+                                   16 * tasks + 8 * frags in this call */
+    uint64_t raw_bytes;         /* sum of the sizes of those fragments */
+    uint32_t verify_failures; uint32_t reserved;
+    double kernel_ms, seconds_total;   /* HIP-event time of this layer's launches (the decoder's is not in it); wall time of the call */
+} CSADevReadStats;
+
+/* decompress_index (csarc.cpp:290-336) on the device: check_header (csarc.cpp:577-598) over the 24 header bytes read back; the
+ * index stream decoded where it lies (its 10 property bytes read back first); its raw bytes read back and parsed by the
+ * bounds-checked UnpackIndex.  Returns 0; 1 for a bad header (as CSA_Extract) or arc_size < 24; -1 for an index that is out of
+ * bounds, undecodable or unparsable, or whose sizes wrap in 64 bits; CSCMI_DEVICE_ERROR without a usable device (*out is
+ * untouched then) or when memory cannot be had.  *out is set only when 0 is returned. */
+int CSAMI_DeviceOpen(const void *arc_dev, uint64_t arc_size, CSADevArchive **out);
+/* The layout for a selection, without reading anything (host only): at most `cap` entries are stored to files (files may be NULL),
+ * *n_files is the number of selected entries, *dst_bytes the bytes CSAMI_DeviceRead needs.  Returns 0, or -1 if the sum wraps. */
+int CSAMI_DevicePlan(CSADevArchive *a, const char *const *names, int nnames,
+                     CSADevFile *files, uint32_t cap, uint32_t *n_files, uint64_t *dst_bytes);
+/* `csarc x` into dst (dst == NULL: `csarc t`, dst_cap ignored).  files / cap as CSAMI_DevicePlan, with failed_frags filled in.
+ * Returns what CSA_Test returns: 0; -1 if any task's stream has no decoder, ends early, fails to decode or holds more than its raw
+ * size (a WRITE_ERROR of a task stream is a decode error); CSCMI_DEVICE_ERROR where memory cannot be had; WRITE_ERROR, with
+ * nothing launched and *st zeroed, if dst != NULL and dst_cap < dst_bytes.
+ * A failed adler32 is counted per file in failed_frags and summed in st->verify_failures and does not change the return value
+ * (csa_io.h:331-332).  A fragment is verified only if at least one of its bytes was delivered (posblock < produced of its task) --
+ * that is when AsyncFileWriter opens it, and only opened fragments are closed and verified (csa_io.h:390-406); fragments wholly
+ * behind the end of a short stream are not counted, the -1 reports them.
+ * Where this differs from CSA_Test on a damaged archive: the callback path stops a task's decoder once its last selected fragment
+ * is complete (CSC_WRITE_ABORT, csa_io.h:176-179), this call decodes every task to its end, so damage BEHIND the last selected
+ * fragment of a task is reported here and not there. */
+int CSAMI_DeviceRead(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
+                     const CSAOptions *o, CSADevFile *files, uint32_t cap, CSADevReadStats *st);
+/* HIP-event milliseconds of the last CSAMI_DeviceRead's launches by kernel: [0] k_gather_extents, [1] k_frag_pieces, [2] k_frag_fold */
+void CSAMI_DeviceKernelMs(const CSADevArchive *a, double ms[3]);
+void CSAMI_DeviceClose(CSADevArchive *a);
+/* host only, no GPU: the same plan from raw (unpacked) index bytes, as CSA_ReadIndex returns them.  files[i].name points at the
+ * entry's name INSIDE raw_index: not NUL-terminated, its 32-bit little-endian length in the four bytes in front of it.
+ * task_raw_sizes receives (at most task_cap; may be NULL) the raw sizes of the tasks CSAMI_DeviceRead would decode for this
+ * selection, in the order it decodes them (largest sum of selected fragment sizes first, equal sums by bid); *n_tasks their number.
+ * This call is the strict one: it returns -1 for an index that does not parse, whose sizes wrap, or with an archive block that
+ * does not lie inside [0, arc_size) -- which the device path would read short. */
+int CSAMI_PlanDeviceLayout(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
+                           CSADevFile *files, uint32_t cap, uint32_t *n_files, uint64_t *dst_bytes,
+                           uint64_t *task_raw_sizes, uint32_t task_cap, uint32_t *n_tasks);
+
 /* YYYYMMDDHHMMSS <-> time_t, csa_common.cpp:3-39 */
 int64_t CSA_DecimalTime(int64_t unix_seconds);
 int64_t CSA_UnixTime(int64_t decimal_date);
