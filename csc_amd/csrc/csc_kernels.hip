@@ -294,6 +294,12 @@ DEV void q_publish(Sc &c)
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
     *(volatile __attribute__((address_space(3))) uint32_t *)&c.Q->pub = c.q_head;
 }
+// the same up to entry `to` only: the entries behind it are not all written yet (d6_room)
+DEV void q_publish_to(Sc &c, uint32_t to)
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup", "local");
+    *(volatile __attribute__((address_space(3))) uint32_t *)&c.Q->pub = to;
+}
 // wait until at most kCoderQ - `need` entries are outstanding; -> entries outstanding.  Bounded: a coder wavefront that has stopped
 // consuming turns into an error code (0x40200000 | ...) instead of a hung kernel
 constexpr uint32_t ERR_QUEUE_STALL = 0x40200000u;

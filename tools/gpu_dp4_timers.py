@@ -73,5 +73,9 @@ if tr[15] and tr[40]:
     print(f"    queue room asked for (d6_room's slow path) {tr[40]} times ({tr[40]/nw:.2f} a window): join {16*tr[41]/tr[40]:.0f} cycles each, publish + wait for the coder wavefront {16*tr[42]/tr[40]:.0f} each ({16*(tr[41]+tr[42])/nw:.0f} a window), room afterwards {16*tr[46]/tr[40]:.0f} entries")
 if tr[15] and tr[40]:
     print(f"    ... of them {tr[47]} with a join under 2048 cycles; tree records still to be coded when the room was asked for: {tr[31]/tr[40]:.1f} a call")
+if tr[15] and tr[40]:
+    print(f"    ... of them {tr[22]} joined and published everything (the oldest uncoded record too far back for the room asked); the publish point lay {tr[23]/tr[40]:.0f} entries behind the head on average")
+if tr[15] and tr[48]:
+    print(f"    tree wavefront: {tr[49]} match / rep records in {tr[48]} passes, {tr[49]/tr[48]:.2f} a pass")
 if tr[15] and tr[44]:
     print(f"    coder wavefront: {tr[44]} queue entries in {tr[45]} batches, {16*tr[43]/tr[44]:.0f} cycles an entry, busy {16*tr[43]/tr[15]:.0f} cycles a window")
