@@ -51,12 +51,24 @@ class CSADevReadStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class CSADevWriteStats(C.Structure):
+    _fields_ = [("tasks", C.c_uint64), ("frags", C.c_uint64), ("waves", C.c_uint64), ("blocks", C.c_uint64), ("launches", C.c_uint64),
+                ("encode_launches", C.c_uint64), ("readback_bytes", C.c_uint64), ("upload_bytes", C.c_uint64), ("raw_bytes", C.c_uint64),
+                ("archive_bytes", C.c_uint64), ("index_raw_size", C.c_uint64), ("index_compressed_size", C.c_uint64),
+                ("n_entries", C.c_uint32), ("retries", C.c_uint32), ("kernel_ms", C.c_double), ("seconds_encode", C.c_double),
+                ("seconds_total", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 LIST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(CSAFrag))
 
 SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", "CSA_ReadIndex",
            "CSA_Adler32", "CSAMI_Adler32Device", "CSA_DecimalTime", "CSA_UnixTime",
            "CSAMI_AddShardEncode", "CSAMI_FreeBlob", "CSAMI_AddShardAssemble", "CSAMI_PlanInfo", "CSAMI_PlanShards", "CSA_IndexRoundTrip",
-           "CSAMI_DeviceOpen", "CSAMI_DevicePlan", "CSAMI_DeviceRead", "CSAMI_DeviceClose", "CSAMI_PlanDeviceLayout", "CSAMI_DeviceKernelMs"]
+           "CSAMI_DeviceOpen", "CSAMI_DevicePlan", "CSAMI_DeviceRead", "CSAMI_DeviceClose", "CSAMI_PlanDeviceLayout", "CSAMI_DeviceKernelMs",
+           "CSAMI_DeviceWritePlan", "CSAMI_DeviceWrite", "CSAMI_DeviceWriteKernelMs"]
 
 CSA_MAX_FRAGMENTS = 127
 CSA_TOO_MANY_FRAGMENTS = -94
@@ -117,6 +129,14 @@ def lib():
         L.CSAMI_PlanDeviceLayout.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, names, C.c_int, files, C.c_uint32, C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint32)]
         L.CSAMI_PlanDeviceLayout.restype = C.c_int
+        L.CSAMI_DeviceWritePlan.argtypes = [files, C.c_uint32, C.c_char_p, C.POINTER(CSAOptions), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                            C.POINTER(C.c_uint64)]
+        L.CSAMI_DeviceWritePlan.restype = C.c_int
+        L.CSAMI_DeviceWrite.argtypes = [C.c_void_p, C.c_uint64, files, C.c_uint32, C.c_char_p, C.c_void_p, C.c_uint64, C.POINTER(CSAOptions),
+                                        C.POINTER(CSADevWriteStats)]
+        L.CSAMI_DeviceWrite.restype = C.c_int
+        L.CSAMI_DeviceWriteKernelMs.argtypes = [C.POINTER(C.c_double)]
+        L.CSAMI_DeviceWriteKernelMs.restype = None
         _lib = L
     return _lib
 
@@ -284,6 +304,33 @@ def plan_device_layout(raw_index: bytes, arc_size: int, names: Sequence[str] = (
     return rc, out, int(total.value), list(tasks[:nt.value])
 
 
+def _write_table(files):
+    """[dicts with name, esize, edate, eattr, offset] -> (CSADevFile array, the name buffers it points into)"""
+    keep = [C.create_string_buffer(f["name"].encode("latin-1") if isinstance(f["name"], str) else bytes(f["name"])) for f in files]
+    arr = (CSADevFile * max(len(keep), 1))()
+    for a, f, k in zip(arr, files, keep):
+        a.name = C.cast(k, C.c_void_p)
+        a.esize, a.edate, a.eattr, a.offset = f["esize"], f["edate"], f["eattr"], f.get("offset", 0)
+    return arr, keep
+
+
+def device_write_plan(files, arcname: str = "out.csa", **opts):
+    """CSAMI_DeviceWritePlan (host only): the plan DeviceArchive.write would execute for this table ->
+    (rc, number of task streams, largest fragment count of any entry, raw bytes of all tasks)"""
+    arr, keep = _write_table(files)
+    o = options(**opts)
+    nt, mf, raw = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    rc = lib().CSAMI_DeviceWritePlan(arr, len(keep), arcname.encode(), C.byref(o), C.byref(nt), C.byref(mf), C.byref(raw))
+    return rc, int(nt.value), int(mf.value), int(raw.value)
+
+
+def device_write_kernel_ms():
+    """HIP-event milliseconds of this thread's last DeviceArchive.write by kernel: (k_frag_pieces, k_frag_fold, k_block_table, k_gather_extents)"""
+    ms = (C.c_double * 4)()
+    lib().CSAMI_DeviceWriteKernelMs(ms)
+    return tuple(ms)
+
+
 class DeviceArchive:
     """A `.csa` that lies in device memory (CSAMI_DeviceOpen ... CSAMI_DeviceClose): `csarc x` / `csarc t` without the archive,
     the decoded tasks or the files crossing the bus.  torch is the plumbing: it owns the buffers and hands out views."""
@@ -349,6 +396,41 @@ class DeviceArchive:
         rc, files, st = self._read(names, None, opts)
         st["files"] = files
         return rc, st
+
+    @staticmethod
+    def write(files, src, arcname: str = "out.csa", arc=None, **opts):
+        """`csarc a -t1` -> (rc, uint8 CUDA view of the archive, stats dict).  files: the dicts plan() and extract() return (name,
+        esize, edate, eattr and offset are read); src: the 1-d contiguous torch.uint8 CUDA tensor they lie in, any alignment; arc: the
+        tensor to write into (allocated here when None, and once more with twice the room on WRITE_ERROR).  stats["files"] is the
+        table as returned: size = esize, nfrags = the fragments the entry got."""
+        import torch
+
+        def ok(t):
+            return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.dim() == 1
+        if not ok(src) or not (arc is None or ok(arc)):
+            raise TypeError("src, arc: contiguous 1-d torch.uint8 CUDA tensors")
+        o = options(**opts)
+        caps = [None]
+        if arc is None:
+            rc, nt, _, raw = device_write_plan(files, arcname, **opts)
+            if rc != 0:
+                return rc, None, {"files": []}
+            cap = 24 + raw + raw // 8 + (64 << 10) * (nt + 1) + (1 << 20)
+            caps = [cap, 2 * cap]
+        for cap in caps:
+            if cap is not None:
+                arc = torch.empty(cap, dtype=torch.uint8, device=src.device)
+            arr, keep = _write_table(files)
+            st = CSADevWriteStats()
+            torch.cuda.synchronize()                   # src was filled on torch's stream, the library launches on its own
+            rc = lib().CSAMI_DeviceWrite(C.c_void_p(src.data_ptr()) if src.numel() else None, int(src.numel()), arr, len(keep),
+                                         arcname.encode(), C.c_void_p(arc.data_ptr()) if arc.numel() else None, int(arc.numel()),
+                                         C.byref(o), C.byref(st))
+            if rc != WRITE_ERROR:
+                break
+        d = st.as_dict()
+        d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
+        return rc, (arc[:st.archive_bytes] if rc == 0 else None), d
 
     def kernel_ms(self):
         """HIP-event milliseconds of the last extract / test by kernel: (k_gather_extents, k_frag_pieces, k_frag_fold)"""

@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstring>
 #include <functional>
+#include <list>
 #include <map>
 #include <mutex>
 #include <string>
@@ -58,6 +59,7 @@ struct Entry {
     int64_t edate = 0, esize = 0, eattr = 0;
     char ext[4] = {0, 0, 0, 0};
     std::vector<CSAFrag> frags;
+    uint32_t row = 0;              // CSAMI_DeviceWrite: the entry's row in the caller's table
 };
 typedef std::map<std::string, Entry> Index;
 
@@ -1185,12 +1187,10 @@ struct AddPlan {
     std::vector<Task> tasks;
 };
 
-int plan_add(AddPlan &P, const char *const *filenames, int nfilenames, const CSAOptions *opt)
+// the tasks of P.index under P.o, whoever filled the index: the directory scan (plan_add) or the caller's table (plan_write)
+int plan_index(AddPlan &P)
 {
-    if (opt) P.o = *opt; else CSA_OptionsInit(&P.o);
     if (P.o.split_count <= 0) P.o.split_count = 1;                           // csarc.cpp:199-200
-    Selection sel = make_selection(filenames, nfilenames);
-    for (const std::string &f : sel.names) scan_path(P.index, sel, f, P.o.recurse != 0);
     P.tasks = plan_tasks(P.index, P.o.split_count);
     if (P.o.task_bytes) P.tasks = cap_tasks(P.tasks, P.o.task_bytes);
     // the index stores a file's fragment count in one signed byte (csa_indexpack.cpp:84,105): more than 127 would write an
@@ -1204,6 +1204,14 @@ int plan_add(AddPlan &P, const char *const *filenames, int nfilenames, const CSA
                 return CSA_TOO_MANY_FRAGMENTS;
             }
     return 0;
+}
+
+int plan_add(AddPlan &P, const char *const *filenames, int nfilenames, const CSAOptions *opt)
+{
+    if (opt) P.o = *opt; else CSA_OptionsInit(&P.o);
+    Selection sel = make_selection(filenames, nfilenames);
+    for (const std::string &f : sel.names) scan_path(P.index, sel, f, P.o.recurse != 0);
+    return plan_index(P);
 }
 
 int open_archive(const char *arcname, const CSAOptions &o, int &fd)
@@ -1953,6 +1961,402 @@ int CSAMI_PlanDeviceLayout(const uint8_t *raw_index, uint64_t raw_size, uint64_t
     for (size_t i = 0; task_raw_sizes && i < L.tasks.size() && i < task_cap; i++) task_raw_sizes[i] = L.tasks[i].raw;
     if (n_tasks) *n_tasks = (uint32_t)L.tasks.size();
     return 0;
+}
+
+}   // extern "C"
+
+// ---------------------------------------------------------------------------------------------
+// device-resident write: CSAMI_DeviceWritePlan / CSAMI_DeviceWrite (include/csa_mi355x.h).
+// Host side: the index from the caller's table, the plan CSA_Add makes (plan_index), the validation of every size, the piece
+// tables, arc_end, the index and the header.  The bytes move in csa_dev_kernels.hip (k_frag_pieces, k_frag_fold, k_block_table,
+// k_gather_extents; tables and walks: csa_dev_read.h, csa_dev_write.h) and in CSCMI_EncodeDeviceBatch.
+// ---------------------------------------------------------------------------------------------
+#include "csa_dev_write.h"
+
+void launch_block_table(const void *jobs, uint32_t njobs, void *scratch, void *res, void *sizes, hipStream_t st);
+
+namespace {
+
+thread_local double g_write_ms[4] = {0, 0, 0, 0};      // CSAMI_DeviceWriteKernelMs
+
+// The caller's table as an index, and its plan.  -1 for a table the host refuses; src_size is checked where check_src.
+int plan_write(AddPlan &P, const CSADevFile *files, uint32_t n_files, const CSAOptions *opt, bool check_src, uint64_t src_size,
+               uint64_t *raw_bytes)
+{
+    if (opt) P.o = *opt; else CSA_OptionsInit(&P.o);
+    if (n_files && !files) return -1;
+    uint64_t sum = 0;
+    for (uint32_t i = 0; i < n_files; i++) {
+        const CSADevFile &f = files[i];
+        if (!f.name || f.esize < 0) return -1;
+        const std::string name(f.name);
+        if (!name.empty() && name[name.size() - 1] == '/' && f.esize != 0) return -1;
+        uint64_t end;
+        if (check_src && (!add_ok(f.offset, (uint64_t)f.esize, &end) || end > src_size)) return -1;
+        if (!add_ok(sum, (uint64_t)f.esize, &sum) || sum > (1ull << 60)) return -1;   // (every later sum of sizes stays far from 2^64)
+        auto ins = P.index.insert(std::make_pair(name, Entry()));
+        if (!ins.second) return -1;
+        Entry &e = ins.first->second;
+        e.edate = f.edate; e.esize = f.esize; e.eattr = f.eattr; e.row = i;
+    }
+    const int rc = plan_index(P);
+    if (raw_bytes) { *raw_bytes = 0; for (const Task &t : P.tasks) *raw_bytes += t.total; }
+    return rc;
+}
+
+struct WriteCtx {
+    const uint8_t *src = nullptr;
+    uint8_t *arc = nullptr;
+    uint64_t arc_cap = 0, arc_end = kHeaderSize;
+    const CSADevFile *files = nullptr;
+    int64_t slack = -1;                        // CSA_DEVWRITE_SLACK, -1: not set
+    CSADevWriteStats S;
+    DevTimer tm;
+    BlockIndex abindex;
+};
+
+uint64_t stream_cap(const WriteCtx &W, uint64_t raw)
+{
+    return W.slack >= 0 ? raw / 4 + (uint64_t)W.slack : raw + raw / 8 + 65536;
+}
+
+bool dev_upload(WriteCtx &W, DevBuf &b, const void *p, uint64_t n)
+{
+    W.S.upload_bytes += n;
+    return b.upload(p, n);
+}
+
+// CSCMI_EncodeDeviceBatch over jobs whose dst is scratch of this layer; a job whose scratch was too small once more, alone, into a
+// larger one (kept in `more` until its stream is placed)
+int dev_encode(WriteCtx &W, std::vector<CSCMIDevEncode> &jobs, std::list<DevBuf> &more)
+{
+    const double t0 = now_s();
+    CSCMIDevEncodeStats es;
+    memset(&es, 0, sizeof(es));
+    int rc = CSCMI_EncodeDeviceBatch((int)jobs.size(), jobs.data(), &es) == 0 ? 0 : CSCMI_DEVICE_ERROR;
+    W.S.encode_launches += es.launches; W.S.readback_bytes += es.readback_bytes;
+    for (size_t i = 0; rc == 0 && i < jobs.size(); i++) {
+        CSCMIDevEncode &j = jobs[i];
+        if (j.rc == WRITE_ERROR) {
+            more.emplace_back();
+            const uint64_t cap = 2 * (uint64_t)j.src_size + (1u << 20);
+            if (!more.back().alloc(cap)) { rc = CSCMI_DEVICE_ERROR; break; }
+            j.dst = more.back().p; j.dst_cap = (size_t)cap; j.produced = 0; j.rc = 0;
+            W.S.retries++;
+            memset(&es, 0, sizeof(es));
+            if (CSCMI_EncodeDeviceBatch(1, &j, &es) != 0) rc = CSCMI_DEVICE_ERROR;
+            W.S.encode_launches += es.launches; W.S.readback_bytes += es.readback_bytes;
+        }
+        if (j.rc != 0) rc = CSCMI_DEVICE_ERROR;
+    }
+    W.S.seconds_encode += now_s() - t0;
+    return rc;
+}
+
+// The property bytes and the stream of every job to arc + arc_end, in order, with one launch; `hdr` (NULL, or the 24 header bytes)
+// goes to arc + 0 with it.  WRITE_ERROR, with nothing launched, if it would pass arc_cap.
+int dev_place(WriteCtx &W, const std::vector<CSCMIDevEncode> &jobs, const uint8_t *hdr)
+{
+    using namespace csadev;
+    const uint64_t lead = hdr ? kHeaderSize : 0;
+    uint64_t end = W.arc_end;
+    for (const CSCMIDevEncode &j : jobs)
+        if (!add_ok(end, CSC_PROP_SIZE + (uint64_t)j.produced, &end)) return WRITE_ERROR;
+    if (end > W.arc_cap) return WRITE_ERROR;
+    // the bytes that come from the host: [the header] and the property bytes of every job
+    std::vector<uint8_t> host(hdr, hdr + lead);
+    for (const CSCMIDevEncode &j : jobs) {
+        uint8_t props[CSC_PROP_SIZE];
+        CSCEnc_WriteProperties(&j.props, props, 0);                          // csa_worker.cpp:38-42
+        host.insert(host.end(), props, props + CSC_PROP_SIZE);
+    }
+    DevBuf d_host, d_gp;
+    if (!dev_upload(W, d_host, host.data(), host.size())) return CSCMI_DEVICE_ERROR;
+    std::vector<CopyPiece> gp;
+    if (hdr) gp.push_back(CopyPiece{(const uint8_t *)d_host.p, W.arc, (uint32_t)kHeaderSize, 0});
+    uint64_t pos = W.arc_end;
+    for (size_t k = 0; k < jobs.size(); k++) {
+        gp.push_back(CopyPiece{(const uint8_t *)d_host.p + lead + CSC_PROP_SIZE * k, W.arc + pos, CSC_PROP_SIZE, 0});
+        piece_split((const uint8_t *)jobs[k].dst, W.arc + pos + CSC_PROP_SIZE, jobs[k].produced, kGatherPiece,
+                    [&](uint64_t, const CopyPiece &p) { gp.push_back(p); });
+        pos += CSC_PROP_SIZE + jobs[k].produced;
+    }
+    if (gp.size() > 0x7FFFFFFFull || !dev_upload(W, d_gp, gp.data(), gp.size() * sizeof(CopyPiece))) return CSCMI_DEVICE_ERROR;
+    W.tm.begin();
+    launch_gather_extents(d_gp.p, (uint32_t)gp.size(), W.tm.st);
+    W.S.launches++;
+    if (!W.tm.end(&g_write_ms[3])) return CSCMI_DEVICE_ERROR;
+    W.arc_end = pos;
+    return 0;
+}
+
+// One wave: tasks [first, first + count) of the plan.  0, WRITE_ERROR or CSCMI_DEVICE_ERROR.
+int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
+{
+    using namespace csadev;
+    // 1. where each task's raw bytes lie: one range of one entry is encoded where it is, anything else is gathered
+    std::vector<const uint8_t *> in(count, nullptr);
+    std::vector<uint64_t> gat_off(count, 0);
+    std::vector<uint8_t> gathered(count, 0);
+    uint64_t gat_bytes = 0, npieces = 0;
+    for (size_t k = 0; k < count; k++) {
+        Task &t = P.tasks[first + k];
+        uint64_t cum = 0;
+        size_t nonempty = 0;
+        for (FilePiece &f : t.files) {
+            f.posblock = cum;                                                // csa_io.h:239
+            cum += f.size;
+            if (f.size) { nonempty++; in[k] = W.src + W.files[f.it->second.row].offset + f.off; }
+            npieces += piece_count(f.size, kFragPiece);
+        }
+        if (nonempty > 1) {
+            gathered[k] = 1;
+            gat_off[k] = gat_bytes;
+            gat_bytes += (t.total + 255) & ~255ull;
+        }
+    }
+    if (npieces > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
+    DevBuf d_gat;
+    if (gat_bytes && !d_gat.alloc(gat_bytes)) return CSCMI_DEVICE_ERROR;
+
+    // 2. gather and sum in one pass: the pieces that are stored first, then the ones that are only summed
+    std::vector<CopyPiece> pc[2];                                            // [1]: with the store
+    std::vector<FragFold> ff;
+    std::vector<uint8_t> ff_store;
+    std::vector<FilePiece *> ff_piece;
+    for (size_t k = 0; k < count; k++) {
+        for (FilePiece &f : P.tasks[first + k].files) {
+            f.checksum = 0;
+            if (!f.size) continue;                                           // adler32 of nothing, seed 0
+            std::vector<CopyPiece> &v = pc[gathered[k]];
+            ff.push_back(FragFold{f.size, (uint32_t)v.size(), (uint32_t)piece_count(f.size, kFragPiece), 0, 0});
+            ff_store.push_back(gathered[k]);
+            ff_piece.push_back(&f);
+            piece_split(W.src + W.files[f.it->second.row].offset + f.off,
+                        gathered[k] ? (uint8_t *)d_gat.p + gat_off[k] + f.posblock : nullptr, f.size, kFragPiece,
+                        [&](uint64_t, const CopyPiece &p) { v.push_back(p); });
+        }
+        if (gathered[k]) in[k] = (const uint8_t *)d_gat.p + gat_off[k];
+    }
+    const size_t nstore = pc[1].size();
+    for (size_t i = 0; i < ff.size(); i++) if (!ff_store[i]) ff[i].first += (uint32_t)nstore;
+    pc[1].insert(pc[1].end(), pc[0].begin(), pc[0].end());
+    const std::vector<CopyPiece> &fp = pc[1];
+    if (!ff.empty()) {
+        DevBuf d_fp, d_ff, d_sums, d_res;
+        if (!dev_upload(W, d_fp, fp.data(), fp.size() * sizeof(CopyPiece)) || !dev_upload(W, d_ff, ff.data(), ff.size() * sizeof(FragFold))
+            || !d_sums.alloc(fp.size() * sizeof(PieceSums)) || !d_res.alloc(ff.size() * sizeof(FragResult))) return CSCMI_DEVICE_ERROR;
+        if (nstore) {
+            W.tm.begin();
+            launch_frag_pieces(d_fp.p, d_sums.p, (uint32_t)nstore, true, W.tm.st);
+            W.S.launches++;
+            if (!W.tm.end(&g_write_ms[0])) return CSCMI_DEVICE_ERROR;
+        }
+        if (fp.size() > nstore) {
+            W.tm.begin();
+            launch_frag_pieces((const CopyPiece *)d_fp.p + nstore, (PieceSums *)d_sums.p + nstore, (uint32_t)(fp.size() - nstore), false, W.tm.st);
+            W.S.launches++;
+            if (!W.tm.end(&g_write_ms[0])) return CSCMI_DEVICE_ERROR;
+        }
+        W.tm.begin();
+        launch_frag_fold(d_ff.p, d_sums.p, d_res.p, (uint32_t)ff.size(), W.tm.st);
+        W.S.launches++;
+        if (!W.tm.end(&g_write_ms[1])) return CSCMI_DEVICE_ERROR;
+        std::vector<FragResult> res(ff.size());
+        if (!HIP_OK(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(FragResult), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+        W.S.readback_bytes += res.size() * sizeof(FragResult);
+        for (size_t i = 0; i < res.size(); i++) ff_piece[i]->checksum = res[i].adler;        // csa_io.h:250
+    }
+
+    // 3. encode: csa_worker.cpp:23-56 for every task of the wave at once, into scratch of this layer
+    std::vector<CSCMIDevEncode> jobs(count);
+    uint64_t scr_bytes = 0;
+    std::vector<uint64_t> scr_off(count);
+    for (size_t k = 0; k < count; k++) {
+        scr_off[k] = scr_bytes;
+        scr_bytes += (stream_cap(W, P.tasks[first + k].total) + 255) & ~255ull;
+    }
+    DevBuf d_scr;
+    std::list<DevBuf> more;
+    if (!d_scr.alloc(scr_bytes)) return CSCMI_DEVICE_ERROR;
+    for (size_t k = 0; k < count; k++) {
+        const Task &t = P.tasks[first + k];
+        CSCMIDevEncode &j = jobs[k];
+        memset(&j, 0, sizeof(j));
+        CSCEncProps_Init(&j.props, (uint32_t)std::min<uint64_t>(P.o.dict_size, t.total), P.o.level);   // csa_worker.cpp:35
+        j.src = t.total ? (const void *)in[k] : d_scr.p;                     // (no byte of it is loaded when the task is empty)
+        j.src_size = (size_t)t.total;
+        j.dst = (uint8_t *)d_scr.p + scr_off[k];
+        j.dst_cap = (size_t)stream_cap(W, t.total);
+    }
+    int rc = dev_encode(W, jobs, more);
+    if (rc) return rc;
+
+    // 4. block tables: BlockSink::put over the Write sizes the file path would have seen
+    std::vector<BlockTableJob> bj(count);
+    uint64_t slots = 0;
+    for (size_t k = 0; k < count; k++) {
+        const uint64_t mb = table_bound(jobs[k].produced, jobs[k].props.csc_blocksize);
+        if (mb > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
+        bj[k] = BlockTableJob{(const uint8_t *)jobs[k].dst, (uint64_t)jobs[k].produced, jobs[k].props.csc_blocksize, (uint32_t)mb, slots};
+        slots += mb;
+    }
+    std::vector<BlockTableRes> br(count);
+    std::vector<uint64_t> sizes;
+    {
+        DevBuf d_bj, d_slots, d_res, d_sizes;
+        if (!dev_upload(W, d_bj, bj.data(), bj.size() * sizeof(BlockTableJob)) || !d_slots.alloc(slots * 8) || !d_res.alloc(count * sizeof(BlockTableRes))
+            || !d_sizes.alloc(slots * 8)) return CSCMI_DEVICE_ERROR;
+        W.tm.begin();
+        launch_block_table(d_bj.p, (uint32_t)count, d_slots.p, d_res.p, d_sizes.p, W.tm.st);
+        W.S.launches++;
+        if (!W.tm.end(&g_write_ms[2])) return CSCMI_DEVICE_ERROR;
+        if (!HIP_OK(hipMemcpy(br.data(), d_res.p, count * sizeof(BlockTableRes), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+        W.S.readback_bytes += count * sizeof(BlockTableRes);
+        uint64_t nb = 0;
+        for (size_t k = 0; k < count; k++) {
+            if (br[k].status != kTableOk || br[k].nblocks > bj[k].max_blocks) {
+                fprintf(stderr, "csa-mi355x: task %zu: its stream does not end where its encoder said (block table status %u)\n", first + k, br[k].status);
+                return CSCMI_DEVICE_ERROR;
+            }
+            nb += br[k].nblocks;
+        }
+        sizes.resize(nb);
+        if (nb && !HIP_OK(hipMemcpy(sizes.data(), d_sizes.p, nb * 8, hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+        W.S.readback_bytes += nb * 8;
+        W.S.blocks += nb;
+    }
+
+    // 5. placement, and the tasks' extents (csa_io.h:559-573; id == task index, csarc.cpp:393-394)
+    uint64_t pos = W.arc_end;
+    size_t at = 0;
+    for (size_t k = 0; k < count; k++) {
+        std::vector<Extent> &ext = W.abindex[first + k];
+        const uint64_t begin = pos;
+        for (uint32_t i = 0; i < br[k].nblocks; i++, at++) { ext.push_back(Extent{pos, sizes[at]}); pos += sizes[at]; }
+        if (pos - begin != CSC_PROP_SIZE + (uint64_t)jobs[k].produced) return CSCMI_DEVICE_ERROR;
+    }
+    return dev_place(W, jobs, nullptr);
+}
+
+}   // namespace
+
+extern "C" {
+
+int CSAMI_DeviceWritePlan(const CSADevFile *files, uint32_t n_files, const char *arcname, const CSAOptions *opt,
+                          uint32_t *n_tasks, uint32_t *max_frags, uint64_t *raw_bytes)
+{
+    (void)arcname;
+    AddPlan P;
+    uint64_t raw = 0;
+    const int rc = plan_write(P, files, n_files, opt, false, 0, &raw);
+    if (rc == -1) return -1;
+    std::map<const void *, uint32_t> nfr;
+    uint32_t mx = 0;
+    for (const Task &t : P.tasks)
+        for (const FilePiece &f : t.files) mx = std::max(mx, ++nfr[(const void *)&*f.it]);
+    if (n_tasks) *n_tasks = (uint32_t)P.tasks.size();
+    if (max_frags) *max_frags = mx;
+    if (raw_bytes) *raw_bytes = raw;
+    return rc;
+}
+
+int CSAMI_DeviceWrite(const void *src_dev, uint64_t src_size, CSADevFile *files, uint32_t n_files, const char *arcname,
+                      void *arc_dev, uint64_t arc_cap, const CSAOptions *opt, CSADevWriteStats *st)
+{
+    const double t0 = now_s();
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
+    WriteCtx W;
+    memset(&W.S, 0, sizeof(W.S));
+    if (st) *st = W.S;
+    for (double &m : g_write_ms) m = 0;
+    // ---- everything the host can refuse, before any launch
+    const uintptr_t s0 = (uintptr_t)src_dev, a0 = (uintptr_t)arc_dev;
+    uint64_t s1, a1;
+    if (!arcname || (!src_dev && src_size) || (!arc_dev && arc_cap) || !add_ok(s0, src_size, &s1) || !add_ok(a0, arc_cap, &a1)) return -1;
+    if (src_size && arc_cap && s0 < a1 && a0 < s1) return -1;
+    AddPlan P;
+    int rc = plan_write(P, files, n_files, opt, true, src_size, &W.S.raw_bytes);
+    if (rc) return rc;
+    if (arc_cap < kHeaderSize) return WRITE_ERROR;
+    if (const char *e = getenv("CSA_DEVWRITE_SLACK")) { W.slack = (int64_t)strtoull(e, nullptr, 10); if (W.slack < 0) W.slack = -1; }
+    W.src = (const uint8_t *)src_dev; W.arc = (uint8_t *)arc_dev; W.arc_cap = arc_cap; W.files = files;
+    if (!W.tm.ok) return CSCMI_DEVICE_ERROR;
+
+    // ---- waves of consecutive task ids, largest first (csarc.cpp:355): the plan's order and the archive's
+    size_t mem_free = 0, mem_total = 0;
+    if (!HIP_OK(hipMemGetInfo(&mem_free, &mem_total))) return CSCMI_DEVICE_ERROR;
+    const uint64_t budget = P.o.hbm_budget ? P.o.hbm_budget : (uint64_t)mem_free / 4 * 3;
+    size_t width = P.o.device_streams > 0 ? (size_t)P.o.device_streams : csadev::kTableMaxJobs;
+    width = std::min<size_t>(width, csadev::kTableMaxJobs);
+    for (size_t first = 0; rc == 0 && first < P.tasks.size();) {
+        size_t count = 0;
+        uint64_t mem = 0;
+        while (first + count < P.tasks.size() && count < width) {
+            // what the task's encoder holds (as encode_tasks reckons), a gathered copy of its input (at most) and its scratch stream
+            const Task &t = P.tasks[first + count];
+            CSCProps p;
+            CSCEncProps_Init(&p, (uint32_t)std::min<uint64_t>(P.o.dict_size, t.total), P.o.level);
+            const uint64_t need = CSCEnc_EstMemUsage(&p) + (24ull << 20) + t.total + stream_cap(W, t.total);
+            if (count && mem + need > budget) break;
+            mem += need;
+            count++;
+        }
+        rc = dev_write_wave(W, P, first, count);
+        W.S.waves++;
+        for (size_t k = first; k < first + count; k++) { W.S.tasks++; W.S.frags += P.tasks[k].files.size(); }
+        first += count;
+    }
+
+    // ---- fragments, index stream, header: csarc.cpp:371-386, 219-288
+    if (rc == 0) {
+        for (size_t ti = 0; ti < P.tasks.size(); ti++)
+            for (const FilePiece &f : P.tasks[ti].files)
+                f.it->second.frags.push_back(CSAFrag{(uint32_t)ti, f.checksum, f.posblock, f.size, f.off});
+        const std::vector<uint8_t> raw = pack_index(P.index, W.abindex, arcname);
+        DevBuf d_raw, d_scr;
+        std::list<DevBuf> more;
+        std::vector<CSCMIDevEncode> job(1);
+        memset(&job[0], 0, sizeof(job[0]));
+        CSCEncProps_Init(&job[0].props, 256 * 1024, 2);                      // csarc.cpp:251
+        if (raw.size() > 0xFFFFFFFFull) rc = WRITE_ERROR;                    // (the header has 32 bits for it)
+        else if (!dev_upload(W, d_raw, raw.data(), raw.size()) || !d_scr.alloc(stream_cap(W, raw.size()))) rc = CSCMI_DEVICE_ERROR;
+        if (rc == 0) {
+            job[0].src = d_raw.p; job[0].src_size = raw.size();
+            job[0].dst = d_scr.p; job[0].dst_cap = (size_t)stream_cap(W, raw.size());
+            rc = dev_encode(W, job, more);
+        }
+        const uint64_t csize = CSC_PROP_SIZE + (uint64_t)job[0].produced;
+        if (rc == 0 && csize > 0xFFFFFFFFull) rc = WRITE_ERROR;
+        if (rc == 0) {
+            uint8_t hdr[kHeaderSize];                                        // csarc.cpp:268-287
+            hdr[0] = 'C'; hdr[1] = 'S'; hdr[2] = 'A'; hdr[7] = '1';
+            store_le(hdr + 3, kMagicNum, 4);
+            store_le(hdr + 8, W.arc_end, 8);
+            store_le(hdr + 16, csize, 4);
+            store_le(hdr + 20, raw.size(), 4);
+            rc = dev_place(W, job, hdr);
+        }
+        if (rc == 0) {
+            W.S.index_raw_size = raw.size();
+            W.S.index_compressed_size = csize;
+            W.S.archive_bytes = W.arc_end;
+            W.S.n_entries = (uint32_t)P.index.size();
+            for (const auto &kv : P.index) {
+                files[kv.second.row].size = (uint64_t)kv.second.esize;
+                files[kv.second.row].nfrags = (uint32_t)kv.second.frags.size();
+            }
+        }
+    }
+    W.S.kernel_ms = g_write_ms[0] + g_write_ms[1] + g_write_ms[2] + g_write_ms[3];
+    W.S.seconds_total = now_s() - t0;
+    if (st) *st = W.S;
+    return rc;
+}
+
+void CSAMI_DeviceWriteKernelMs(double ms[4])
+{
+    for (int i = 0; i < 4; i++) ms[i] = g_write_ms[i];
 }
 
 }   // extern "C"

@@ -1,6 +1,7 @@
 // csa_dev_kernels.hip -- the three kernels of the device-resident archive read (CSAMI_DeviceRead, csa_archive.cpp): per wave of
 // tasks one launch of each, whatever the number of tasks and fragments.  All three are bandwidth-bound: a byte is loaded once and
-// stored at most once, in 16-byte accesses wherever the two ends allow it (csa_dev_read.h: copy_sum).
+// stored at most once, in 16-byte accesses wherever the two ends allow it (csa_dev_read.h: copy_sum).  The device-resident write
+// (CSAMI_DeviceWrite) runs the same three the other way round -- fragments gathered and summed, streams placed -- and one more:
 //
 //   k_gather_extents      one workgroup per <= 64 KiB piece of an archive block: the blocks of a task, which interleave with other
 //                         tasks' in an archive written by several workers (AsyncArchiveReader, csa_io.h:466-542), go back to back
@@ -8,6 +9,8 @@
 //   k_frag_pieces<STORE>  one workgroup per <= 16 KiB piece of a fragment: adler32's A and B over it, and with STORE the bytes to
 //                         their place in the caller's buffer in the same pass (AsyncFileWriter, csa_io.h:274-408)
 //   k_frag_fold           one lane per fragment: its pieces folded in order and compared with the index's checksum
+//   k_block_table         one lane per task stream of a wave (write only): the archive-block table AsyncWriter would have made of
+//                         the encoder's Write calls (csa_io.h:145-201), read off the stream's framing (csa_dev_write.h)
 //
 // Every address in the tables was validated by the host before the launch; a workgroup touches src[0, len) and dst[0, len) of its
 // piece and nothing else.
@@ -15,6 +18,7 @@
 #include <stdint.h>
 
 #include "csa_dev_read.h"
+#include "csa_dev_write.h"
 
 using namespace csadev;
 
@@ -76,4 +80,40 @@ void launch_frag_fold(const void *frags, const void *sums, void *out, uint32_t n
 {
     hipLaunchKernelGGL(k_frag_fold, dim3(nfrags ? (nfrags + kThreads - 1) / kThreads : 1), dim3(kThreads), 0, st,
                        (const FragFold *)frags, (const PieceSums *)sums, (FragResult *)out, nfrags);
+}
+
+// One workgroup for the wave: lane t walks tasks t, t + 256, ... -- a step is one coder block, a few dependent byte loads, so the
+// longest stream sets the time whatever the width -- into its own slots of `scratch`; then the tables go back to back, in task
+// order, into `sizes`, so that the host reads back the blocks there are and not the slots there might have been.
+__global__ __launch_bounds__(kTableThreads) void k_block_table(const BlockTableJob *jobs, uint32_t njobs, uint64_t *scratch,
+                                                               BlockTableRes *res, uint64_t *sizes)
+{
+    __shared__ uint32_t start[kTableMaxJobs];
+    for (uint32_t k = threadIdx.x; k < njobs; k += kTableThreads) {
+        const BlockTableJob j = jobs[k];
+        const uint8_t *s = j.stream;
+        uint64_t *out = scratch + j.first;
+        BlockTableRes r;
+        r.status = block_table([s](uint64_t i) { return (uint32_t)s[i]; }, j.produced, j.bsize, j.max_blocks,
+                               [out](uint32_t i, uint64_t size) { out[i] = size; }, &r.nblocks);
+        res[k] = r;
+        start[k] = r.nblocks < j.max_blocks ? r.nblocks : j.max_blocks;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t at = 0;
+        for (uint32_t k = 0; k < njobs; k++) { const uint32_t n = start[k]; start[k] = at; at += n; }
+    }
+    __syncthreads();
+    for (uint32_t k = threadIdx.x; k < njobs; k += kTableThreads) {
+        const BlockTableJob j = jobs[k];
+        const uint32_t nb = res[k].nblocks < j.max_blocks ? res[k].nblocks : j.max_blocks;
+        for (uint32_t i = 0; i < nb; i++) sizes[start[k] + i] = scratch[j.first + i];
+    }
+}
+
+void launch_block_table(const void *jobs, uint32_t njobs, void *scratch, void *res, void *sizes, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_block_table, dim3(1), dim3(kTableThreads), 0, st, (const BlockTableJob *)jobs, njobs, (uint64_t *)scratch,
+                       (BlockTableRes *)res, (uint64_t *)sizes);
 }

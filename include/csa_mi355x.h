@@ -236,6 +236,69 @@ int CSAMI_PlanDeviceLayout(const uint8_t *raw_index, uint64_t raw_size, uint64_t
                            CSADevFile *files, uint32_t cap, uint32_t *n_files, uint64_t *dst_bytes,
                            uint64_t *task_raw_sizes, uint32_t task_cap, uint32_t *n_tasks);
 
+/* ---- device-resident archive write: file bytes that lie in device memory to a .csa in device memory; not in the reference ----
+ *
+ * `csarc a -t1` (CSArc::Add csarc.cpp:472-575, compress_mt :338-409, compress_index :219-288) for entries the caller already holds
+ * in HBM: arc[0, archive_bytes) is byte for byte what CSA_Add writes for the same entries and options.  What the reference's
+ * reader and writer threads do around the encoder is, per wave of tasks, at most five launches of this layer whatever the number
+ * of tasks and fragments:
+ *   k_frag_pieces      AsyncFileReader (csa_io.h:215-272): a task's fragments back to back, and adler32's partial sums in the same
+ *                      pass.  A task whose input is ONE range of one entry is encoded where it lies: summed, not copied.
+ *                      (one launch for the pieces that are copied, one for those that are not)
+ *   k_frag_fold        the sums of each fragment folded (csa_io.h:250); the host reads the checksums, 8 bytes a fragment
+ *   CSCMI_EncodeDeviceBatch   every task of the wave at once, into scratch of this layer: raw + raw/8 + 64 KiB a stream; a stream
+ *                      that does not fit is encoded once more, alone, into 2 raw + 1 MiB (st->retries).  CSA_DEVWRITE_SLACK=<bytes>
+ *                      in the environment, read per call, makes the first size raw/4 + <bytes> (for tests of that second try)
+ *   k_block_table      AsyncWriter::Write / flush (csa_io.h:145-201): the task's archive-block table, from the sizes of the Write
+ *                      calls the encoder would have made -- read off the framing of the stream where it lies
+ *   k_gather_extents   the 10 property bytes and the stream of each task to arc, in task-id order (csa_io.h:559-573)
+ * and after the last wave the index (PackIndex, csa_indexpack.cpp:166-189) is uploaded, encoded on the device and placed with the
+ * 24 header bytes by one more launch: st->launches <= 5 * waves + 2.
+ *
+ * Input.  `files` is the table CSAMI_DeviceRead fills, so a read can be fed straight back: name, esize, edate and eattr go into the
+ * index as given; an entry's bytes are src[offset, offset + esize), offset of any alignment; a name that ends in '/' is a directory
+ * and must have esize 0.  size, nfrags and failed_frags are ignored on input; on return (0 only) size = esize and nfrags is the
+ * number of fragments the entry got.  The order of the table does not matter: the index is in byte-wise name order
+ * (csa_typedef.h:50).  No selection and no unsafe-name rule applies -- nothing reaches a file system.  arcname enters through its
+ * length alone (csa_indexpack.cpp:129-134).  Of the options level, dict_size, split_count, task_bytes, device_streams and
+ * hbm_budget mean what they mean for CSA_Add and CSAMI_DeviceRead, the others are ignored; o == NULL gives the defaults.
+ * The plan is CSA_Add's (the same text, over an index built from the table instead of a directory scan); tasks go in waves of
+ * consecutive ids, largest first, sized by hbm_budget and device_streams (at most 2048), a wave's buffers released before the next.
+ *
+ * Returns 0; CSA_TOO_MANY_FRAGMENTS as CSA_Add, nothing launched and nothing stored; -1 for a table the host refuses before any
+ * launch (n_files > 0 with files == NULL, a NULL or duplicate name, esize < 0, a directory with bytes, offset + esize past
+ * src_size or wrapping, sizes that sum past 2^60, [src, src + src_size) overlapping [arc, arc + arc_cap)); WRITE_ERROR when the
+ * archive does not fit in arc_cap (refused before the launch that would pass it); CSCMI_DEVICE_ERROR without a usable device (no
+ * argument touched then), when memory cannot be had, when a task's encode job reports it or fails its second try, or when the
+ * block-table walk finds a stream that does not end at its `produced` (an internal inconsistency, never a fault).
+ *
+ * Safety contract.  Every size is checked on the host, in overflow-checked 64-bit arithmetic, before the first launch.  Nothing
+ * outside [src, src + src_size) is loaded, not even by an aligned 16-byte window, and nothing outside [arc, arc + arc_cap) is stored.
+ * On success the bytes of arc at and behind archive_bytes are untouched; on failure the bytes inside arc_cap are unspecified.
+ *
+ * What crosses the bus.  Host to device: the piece tables (24 bytes per <= 16 KiB piece of a fragment, 24 per fragment, 32 per task,
+ * 24 per <= 64 KiB piece of a placed stream), 10 property bytes a task, the raw index and the 24 header bytes.  Device to host: the
+ * encoder's own 16 bytes a stream a round, 8 bytes a fragment, and per task 8 bytes (block count, status) plus 8 bytes per archive
+ * block.  No file byte and no stream byte crosses in either direction. */
+typedef struct CSADevWriteStats {
+    uint64_t tasks, frags, waves, blocks;     /* task streams; fragments of all entries; waves; archive blocks of all tasks */
+    uint64_t launches;                        /* launches of THIS layer (gather/sum, fold, block table, placement) */
+    uint64_t encode_launches;                 /* what CSCMI_EncodeDeviceBatch reports, summed (index stream included) */
+    uint64_t readback_bytes, upload_bytes;    /* every device-to-host / host-to-device byte of this layer (tables included in upload) */
+    uint64_t raw_bytes, archive_bytes, index_raw_size, index_compressed_size;
+    uint32_t n_entries, retries;              /* retries: task streams re-encoded because the scratch was too small */
+    double kernel_ms, seconds_encode, seconds_total;
+} CSADevWriteStats;
+/* The plan CSAMI_DeviceWrite would execute (host only, no GPU): number of task streams, the largest fragment count of any entry,
+ * the bytes of all tasks.  Returns 0, CSA_TOO_MANY_FRAGMENTS, or -1 for a table refused as above (offsets are not looked at). */
+int CSAMI_DeviceWritePlan(const CSADevFile *files, uint32_t n_files, const char *arcname, const CSAOptions *o,
+                          uint32_t *n_tasks, uint32_t *max_frags, uint64_t *raw_bytes);
+int CSAMI_DeviceWrite(const void *src_dev, uint64_t src_size, CSADevFile *files, uint32_t n_files, const char *arcname,
+                      void *arc_dev, uint64_t arc_cap, const CSAOptions *o, CSADevWriteStats *st);
+/* HIP-event milliseconds of this thread's last CSAMI_DeviceWrite by kernel: [0] k_frag_pieces, [1] k_frag_fold, [2] k_block_table,
+ * [3] k_gather_extents (placement) */
+void CSAMI_DeviceWriteKernelMs(double ms[4]);
+
 /* YYYYMMDDHHMMSS <-> time_t, csa_common.cpp:3-39 */
 int64_t CSA_DecimalTime(int64_t unix_seconds);
 int64_t CSA_UnixTime(int64_t decimal_date);

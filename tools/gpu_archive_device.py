@@ -157,7 +157,7 @@ def main():
               "a streaming kernel can reach on this device.  An archive of several GB was not measured.  k_gather_extents moved the property bytes only: no task stream of these archives exceeds one archive block, so nothing was gathered and its bandwidth was not measured.",
               "- Not measured: the parent commit's library as a separate build (the file path's code is the same text), rocprofv3 "
               "kernel traces, PMC counters, more than one wave at a realistic budget, archives written with `-t4`.",
-              "- Not built: the write half (a `.csa` assembled in HBM), overlap of a wave's gather with the previous wave's decode, "
+              "- Not built: overlap of a wave's gather with the previous wave's decode, "
               "decoding straight into dst where a task is one whole file.", ""]
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
