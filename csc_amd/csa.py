@@ -51,6 +51,13 @@ class CSADevReadStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class CSADevStopStats(C.Structure):
+    _fields_ = [("decoded_bytes", C.c_uint64), ("task_raw_bytes", C.c_uint64), ("scratch_bytes", C.c_uint64), ("stopped_tasks", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class CSADevWriteStats(C.Structure):
     _fields_ = [("tasks", C.c_uint64), ("frags", C.c_uint64), ("waves", C.c_uint64), ("blocks", C.c_uint64), ("launches", C.c_uint64),
                 ("encode_launches", C.c_uint64), ("readback_bytes", C.c_uint64), ("upload_bytes", C.c_uint64), ("raw_bytes", C.c_uint64),
@@ -68,6 +75,7 @@ SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", 
            "CSA_Adler32", "CSAMI_Adler32Device", "CSA_DecimalTime", "CSA_UnixTime",
            "CSAMI_AddShardEncode", "CSAMI_FreeBlob", "CSAMI_AddShardAssemble", "CSAMI_PlanInfo", "CSAMI_PlanShards", "CSA_IndexRoundTrip",
            "CSAMI_DeviceOpen", "CSAMI_DevicePlan", "CSAMI_DeviceRead", "CSAMI_DeviceClose", "CSAMI_PlanDeviceLayout", "CSAMI_DeviceKernelMs",
+           "CSAMI_DeviceReadStop", "CSAMI_PlanDeviceStops",
            "CSAMI_DeviceWritePlan", "CSAMI_DeviceWrite", "CSAMI_DeviceWriteKernelMs"]
 
 CSA_MAX_FRAGMENTS = 127
@@ -122,6 +130,11 @@ def lib():
         L.CSAMI_DeviceRead.argtypes = [C.c_void_p, names, C.c_int, C.c_void_p, C.c_uint64, C.POINTER(CSAOptions), files, C.c_uint32,
                                        C.POINTER(CSADevReadStats)]
         L.CSAMI_DeviceRead.restype = C.c_int
+        L.CSAMI_DeviceReadStop.argtypes = L.CSAMI_DeviceRead.argtypes + [C.POINTER(CSADevStopStats)]
+        L.CSAMI_DeviceReadStop.restype = C.c_int
+        u64s = C.POINTER(C.c_uint64)
+        L.CSAMI_PlanDeviceStops.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, names, C.c_int, u64s, u64s, u64s, C.c_uint32, C.POINTER(C.c_uint32)]
+        L.CSAMI_PlanDeviceStops.restype = C.c_int
         L.CSAMI_DeviceKernelMs.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
         L.CSAMI_DeviceKernelMs.restype = None
         L.CSAMI_DeviceClose.argtypes = [C.c_void_p]
@@ -304,6 +317,21 @@ def plan_device_layout(raw_index: bytes, arc_size: int, names: Sequence[str] = (
     return rc, out, int(total.value), list(tasks[:nt.value])
 
 
+def plan_device_stops(raw_index: bytes, arc_size: int, names: Sequence[str] = ()):
+    """CSAMI_PlanDeviceStops (host only): the tasks DeviceArchive.extract(names, stop_early=True) decodes for these raw index
+    bytes, in decode order -> (rc, [{"bid", "stop", "raw"}])"""
+    buf = (C.c_uint8 * max(len(raw_index), 1)).from_buffer_copy(raw_index or b"\0")
+    arr, n = _names(names)
+    nt = C.c_uint32()
+    rc = lib().CSAMI_PlanDeviceStops(buf, len(raw_index), arc_size, arr, n, None, None, None, 0, C.byref(nt))
+    if rc != 0:
+        return rc, []
+    k = nt.value
+    bids, stops, raws = ((C.c_uint64 * max(k, 1))() for _ in range(3))
+    rc = lib().CSAMI_PlanDeviceStops(buf, len(raw_index), arc_size, arr, n, bids, stops, raws, k, C.byref(nt))
+    return rc, [{"bid": int(b), "stop": int(s), "raw": int(r)} for b, s, r in zip(bids[:k], stops[:k], raws[:k])]
+
+
 def _write_table(files):
     """[dicts with name, esize, edate, eattr, offset] -> (CSADevFile array, the name buffers it points into)"""
     keep = [C.create_string_buffer(f["name"].encode("latin-1") if isinstance(f["name"], str) else bytes(f["name"])) for f in files]
@@ -369,31 +397,41 @@ class DeviceArchive:
         lib().CSAMI_DevicePlan(self._h, arr, n, files, nf, None, None)
         return [_file_dict(f, C.string_at(f.name).decode("latin-1")) for f in files[:nf]], total
 
-    def _read(self, names, dst, opts):
+    def _read(self, names, dst, opts, stop_early=False):
         import torch
         arr, n, nf, total = self._plan(names)
         files, st, o = (CSADevFile * max(nf, 1))(), CSADevReadStats(), options(**opts)
         torch.cuda.synchronize()
-        rc = lib().CSAMI_DeviceRead(self._h, arr, n, C.c_void_p(dst.data_ptr()) if dst is not None else None,
-                                    int(dst.numel()) if dst is not None else 0, C.byref(o), files, nf, C.byref(st))
-        return rc, [_file_dict(f, C.string_at(f.name).decode("latin-1")) for f in files[:nf]], st.as_dict()
+        args = (self._h, arr, n, C.c_void_p(dst.data_ptr()) if dst is not None else None,
+                int(dst.numel()) if dst is not None else 0, C.byref(o), files, nf, C.byref(st))
+        if stop_early:
+            ss = CSADevStopStats()
+            rc = lib().CSAMI_DeviceReadStop(*args, C.byref(ss))
+        else:
+            rc = lib().CSAMI_DeviceRead(*args)
+        out = st.as_dict()
+        if stop_early:
+            out.update(ss.as_dict())
+        return rc, [_file_dict(f, C.string_at(f.name).decode("latin-1")) for f in files[:nf]], out
 
-    def extract(self, names: Sequence[str] = (), dst=None, **opts):
+    def extract(self, names: Sequence[str] = (), dst=None, stop_early=False, **opts):
         """`csarc x` -> (rc, {name: uint8 CUDA view of dst}, stats dict).  dst: a 1-d contiguous torch.uint8 CUDA tensor of any
-        alignment with at least plan(names)[1] bytes (allocated here when None); stats["files"] is the files table."""
+        alignment with at least plan(names)[1] bytes (allocated here when None); stats["files"] is the files table.
+        stop_early: CSAMI_DeviceReadStop -- every task is decoded only up to its last selected byte, and the stats dict also holds
+        decoded_bytes, task_raw_bytes, scratch_bytes and stopped_tasks."""
         import torch
         if dst is None:
             dst = torch.empty(max(self._plan(names)[3], 1), dtype=torch.uint8, device=self._arc.device)
         elif not (isinstance(dst, torch.Tensor) and dst.dtype == torch.uint8 and dst.is_cuda and dst.is_contiguous() and dst.dim() == 1):
             raise TypeError("dst: a contiguous 1-d torch.uint8 CUDA tensor")
-        rc, files, st = self._read(names, dst, opts)
+        rc, files, st = self._read(names, dst, opts, stop_early)
         st["files"] = files
         views = {} if rc == WRITE_ERROR else {f["name"]: dst[f["offset"]:f["offset"] + f["size"]] for f in files}
         return rc, views, st
 
-    def test(self, names: Sequence[str] = (), **opts):
-        """`csarc t` -> (rc, stats dict)"""
-        rc, files, st = self._read(names, None, opts)
+    def test(self, names: Sequence[str] = (), stop_early=False, **opts):
+        """`csarc t` -> (rc, stats dict); stop_early as in extract"""
+        rc, files, st = self._read(names, None, opts, stop_early)
         st["files"] = files
         return rc, st
 

@@ -1555,7 +1555,8 @@ int64_t CSA_ReadIndex(const char *arcname, uint8_t *buf, uint64_t cap)
 // ---------------------------------------------------------------------------------------------
 // device-resident read: CSAMI_DeviceOpen / Plan / Read / Close, CSAMI_PlanDeviceLayout (include/csa_mi355x.h).
 // Host side: the index, the layout of dst, the validation of everything the index says, the piece tables.  The bytes move in
-// csa_dev_kernels.hip (tables and copy: csa_dev_read.h) and in CSCMI_DecodeDeviceBatch.
+// csa_dev_kernels.hip (tables and copy: csa_dev_read.h) and in CSCMI_DecodeDeviceBatch; CSAMI_DeviceReadStop is the same body with
+// every task stopped behind its last selected byte (CSCMI_DecodeDeviceBatchStop).
 // ---------------------------------------------------------------------------------------------
 #include "csa_dev_read.h"
 
@@ -1579,7 +1580,7 @@ bool add_ok(uint64_t a, uint64_t b, uint64_t *out) { return !__builtin_add_overf
 
 struct DevFilePlan { Index::const_iterator it; uint64_t offset, size; };
 struct DevFrag { uint32_t file; uint32_t checksum; uint64_t posblock, size, posfile; };
-struct DevTask { uint64_t bid = 0, total = 0, raw = 0; std::vector<DevFrag> frags; };
+struct DevTask { uint64_t bid = 0, total = 0, raw = 0, stop = 0; std::vector<DevFrag> frags; };   // stop: max(posblock + size) over `frags`, <= raw
 struct DevLayout {
     std::vector<DevFilePlan> files;
     std::vector<DevTask> tasks;                // decode order
@@ -1622,6 +1623,7 @@ bool dev_layout(const Index &index, const std::map<uint64_t, uint64_t> &raw, con
             DevTask &t = L.tasks[m->second];
             t.frags.push_back(DevFrag{fi, f.checksum, f.posblock, f.size, f.posfile});
             if (!add_ok(t.total, f.size, &t.total)) return false;
+            t.stop = std::max(t.stop, f.posblock + f.size);               // (checked by dev_task_sizes)
         }
         L.files.push_back(DevFilePlan{it, off, size});
         uint64_t r;
@@ -1687,8 +1689,11 @@ struct DevTimer {                              // HIP-event time of this layer's
 };
 
 // One wave: tasks [first, first + count) of L.  Returns 0, -1 (a stream failed) or CSCMI_DEVICE_ERROR.
+// SS != nullptr (CSAMI_DeviceReadStop): a task is decoded only up to its `stop` -- capacity, scratch and stop position are that --
+// and SS is added to.  The coded stream of a task of several archive blocks is still gathered whole: how many coded bytes a
+// prefix of the raw bytes needs is not known before it is decoded.
 int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t count, uint8_t *dst, std::vector<uint32_t> &failed,
-                  CSADevReadStats &S, DevTimer &tm)
+                  CSADevReadStats &S, DevTimer &tm, CSADevStopStats *SS)
 {
     using namespace csadev;
     static const std::vector<Extent> kNoBlocks;
@@ -1707,7 +1712,7 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
             if (!add_ok(total[k] - CSC_PROP_SIZE, 255, &r) || !add_ok(gat_bytes, r & ~255ull, &gat_bytes)) return CSCMI_DEVICE_ERROR;
         }
         raw_off[k] = raw_bytes;
-        if (!add_ok(t.raw, 255, &r) || !add_ok(raw_bytes, r & ~255ull, &raw_bytes)) return CSCMI_DEVICE_ERROR;
+        if (!add_ok(SS ? t.stop : t.raw, 255, &r) || !add_ok(raw_bytes, r & ~255ull, &raw_bytes)) return CSCMI_DEVICE_ERROR;
     }
     DevBuf d_gat, d_raw, d_props;
     if (!d_gat.alloc(gat_bytes) || !d_raw.alloc(raw_bytes) || !d_props.alloc(16 * count)) return CSCMI_DEVICE_ERROR;
@@ -1746,6 +1751,7 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
     // 3. decode: csa_worker.cpp:59-90 for every task of the wave at once
     std::vector<CSCMIDevDecode> jobs;
     std::vector<size_t> job_task;
+    std::vector<uint64_t> stops;
     std::vector<uint64_t> produced(count, 0);
     for (size_t k = 0; k < count; k++) {
         if (total[k] < CSC_PROP_SIZE) { worst = -1; continue; }               // csa_worker.cpp:77-80: no property bytes, no decoder
@@ -1755,17 +1761,28 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
         j.src = ext[k].size() > 1 ? (const uint8_t *)d_gat.p + gat_off[k] : A.arc + ext[k][0].off + CSC_PROP_SIZE;
         j.src_size = (size_t)(total[k] - CSC_PROP_SIZE);
         j.dst = (uint8_t *)d_raw.p + raw_off[k];
-        j.dst_cap = (size_t)L.tasks[first + k].raw;
+        j.dst_cap = (size_t)(SS ? L.tasks[first + k].stop : L.tasks[first + k].raw);
         jobs.push_back(j);
         job_task.push_back(k);
+        stops.push_back(j.dst_cap);
+    }
+    if (SS) {
+        SS->scratch_bytes += raw_bytes;
+        for (size_t k = 0; k < count; k++) {
+            const DevTask &t = L.tasks[first + k];
+            SS->task_raw_bytes += t.raw;
+            if (t.stop < t.raw) SS->stopped_tasks++;
+        }
     }
     if (!jobs.empty()) {
         CSCMIDevDecodeStats ds;
         memset(&ds, 0, sizeof(ds));
-        if (CSCMI_DecodeDeviceBatch((int)jobs.size(), jobs.data(), NULL, &ds) != 0) return CSCMI_DEVICE_ERROR;
+        if ((SS ? CSCMI_DecodeDeviceBatchStop((int)jobs.size(), jobs.data(), stops.data(), NULL, &ds)
+                : CSCMI_DecodeDeviceBatch((int)jobs.size(), jobs.data(), NULL, &ds)) != 0) return CSCMI_DEVICE_ERROR;
         S.decode_launches += ds.launches;
         for (size_t i = 0; i < jobs.size(); i++) {
             if (jobs[i].rc == CSCMI_DEVICE_ERROR) return CSCMI_DEVICE_ERROR;
+            if (SS) SS->decoded_bytes += jobs[i].produced;
             if (jobs[i].rc != 0) worst = -1;                                   // (WRITE_ERROR: more than the raw size -- a decode error here)
             produced[job_task[i]] = std::min<uint64_t>(jobs[i].produced, jobs[i].dst_cap);   // a failed stream still delivered this much
         }
@@ -1867,8 +1884,13 @@ int CSAMI_DevicePlan(CSADevArchive *a, const char *const *names, int nnames,
     return 0;
 }
 
-int CSAMI_DeviceRead(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
-                     const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st)
+}   // extern "C"
+
+namespace {
+
+// CSAMI_DeviceRead (ss == nullptr) and CSAMI_DeviceReadStop (ss: its stop statistics, never null there)
+int dev_read(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
+             const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st, CSADevStopStats *ss)
 {
     const double t0 = now_s();
     CSADevReadStats S;
@@ -1897,14 +1919,15 @@ int CSAMI_DeviceRead(CSADevArchive *a, const char *const *names, int nnames, voi
         while (first + count < L.tasks.size() && count < width) {
             // the task's decoded bytes and (at most) a copy of its stream, plus what its decoder holds: the dictionary (bounded by
             // the raw size and by 1 GiB) and ~24 MiB of rings and buffers, as read_archive reckons
-            const uint64_t raw = L.tasks[first + count].raw;
+            // (stopped early: the decoded bytes are `stop`; the dictionary and the stream's copy are what they were)
+            const uint64_t raw = L.tasks[first + count].raw, out = ss ? L.tasks[first + count].stop : raw;
             uint64_t need = std::min<uint64_t>(std::max<uint64_t>(raw, 1u << 20), 1ull << 30) + (24ull << 20);
-            if (!add_ok(need, raw, &need) || !add_ok(need, raw, &need)) need = UINT64_MAX;
+            if (!add_ok(need, out, &need) || !add_ok(need, raw, &need)) need = UINT64_MAX;
             if (count && (mem + need < mem || mem + need > budget)) break;
             mem += need;
             count++;
         }
-        int r = dev_read_wave(*a, L, first, count, (uint8_t *)dst, failed, S, tm);
+        int r = dev_read_wave(*a, L, first, count, (uint8_t *)dst, failed, S, tm, ss);
         if (r < 0 && worst != CSCMI_DEVICE_ERROR) worst = r;
         S.waves++;
         for (size_t k = first; k < first + count; k++) { S.tasks++; S.frags += L.tasks[k].frags.size(); S.raw_bytes += L.tasks[k].total; }
@@ -1922,6 +1945,28 @@ int CSAMI_DeviceRead(CSADevArchive *a, const char *const *names, int nnames, voi
     return 0;
 }
 
+}   // namespace
+
+extern "C" {
+
+int CSAMI_DeviceRead(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
+                     const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st)
+{
+    return dev_read(a, names, nnames, dst, dst_cap, opt, files, cap, st, nullptr);
+}
+
+int CSAMI_DeviceReadStop(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
+                         const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st, CSADevStopStats *stop_stats)
+{
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;               // (before anything of the caller's is touched)
+    CSADevStopStats SS;
+    memset(&SS, 0, sizeof(SS));
+    if (stop_stats) *stop_stats = SS;
+    const int rc = dev_read(a, names, nnames, dst, dst_cap, opt, files, cap, st, &SS);
+    if (stop_stats) *stop_stats = SS;
+    return rc;
+}
+
 void CSAMI_DeviceKernelMs(const CSADevArchive *a, double ms[3])
 {
     for (int i = 0; i < 3; i++) ms[i] = a ? a->kernel_ms[i] : 0;
@@ -1929,21 +1974,37 @@ void CSAMI_DeviceKernelMs(const CSADevArchive *a, double ms[3])
 
 void CSAMI_DeviceClose(CSADevArchive *a) { delete a; }
 
+}   // extern "C"
+
+namespace {
+
+// the strict host-only plan of CSAMI_PlanDeviceLayout / CSAMI_PlanDeviceStops: false for an index that does not parse, whose sizes
+// wrap, or with an archive block outside [0, arc_size).  L.files point into `index`.
+bool dev_plan_strict(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
+                     Index &index, DevLayout &L)
+{
+    BlockIndex abindex;
+    std::map<uint64_t, uint64_t> raw;
+    if (!raw_index || !unpack_index(index, abindex, raw_index, raw_size) || !dev_task_sizes(index, raw)) return false;
+    for (const auto &kv : abindex)
+        for (const Extent &x : kv.second) {
+            uint64_t end;
+            if (!add_ok(x.off, x.size, &end) || end > arc_size) return false;
+        }
+    return dev_layout(index, raw, make_selection(names, nnames), L);
+}
+
+}   // namespace
+
+extern "C" {
+
 int CSAMI_PlanDeviceLayout(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
                            CSADevFile *files, uint32_t cap, uint32_t *n_files, uint64_t *dst_bytes,
                            uint64_t *task_raw_sizes, uint32_t task_cap, uint32_t *n_tasks)
 {
     Index index;
-    BlockIndex abindex;
-    std::map<uint64_t, uint64_t> raw;
     DevLayout L;
-    if (!raw_index || !unpack_index(index, abindex, raw_index, raw_size) || !dev_task_sizes(index, raw)) return -1;
-    for (const auto &kv : abindex)
-        for (const Extent &x : kv.second) {
-            uint64_t end;
-            if (!add_ok(x.off, x.size, &end) || end > arc_size) return -1;
-        }
-    if (!dev_layout(index, raw, make_selection(names, nnames), L)) return -1;
+    if (!dev_plan_strict(raw_index, raw_size, arc_size, names, nnames, index, L)) return -1;
     dev_fill_files(L, files, cap);
     // the names: inside raw_index, where the parse above found them (the first entry of a name wins, as in the map)
     std::map<std::string, const char *> where;
@@ -1959,6 +2020,23 @@ int CSAMI_PlanDeviceLayout(const uint8_t *raw_index, uint64_t raw_size, uint64_t
     if (n_files) *n_files = (uint32_t)L.files.size();
     if (dst_bytes) *dst_bytes = L.dst_bytes;
     for (size_t i = 0; task_raw_sizes && i < L.tasks.size() && i < task_cap; i++) task_raw_sizes[i] = L.tasks[i].raw;
+    if (n_tasks) *n_tasks = (uint32_t)L.tasks.size();
+    return 0;
+}
+
+int CSAMI_PlanDeviceStops(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
+                          uint64_t *bids, uint64_t *stops, uint64_t *raws, uint32_t cap, uint32_t *n_tasks)
+{
+    Index index;
+    DevLayout L;
+    if (!dev_plan_strict(raw_index, raw_size, arc_size, names, nnames, index, L)) return -1;
+    for (const DevTask &t : L.tasks)
+        if (t.stop == 0 || t.stop > t.raw) return -1;                       // (a selected fragment past its task: cannot be, by construction)
+    for (size_t i = 0; i < L.tasks.size() && i < cap; i++) {
+        if (bids) bids[i] = L.tasks[i].bid;
+        if (stops) stops[i] = L.tasks[i].stop;
+        if (raws) raws[i] = L.tasks[i].raw;
+    }
     if (n_tasks) *n_tasks = (uint32_t)L.tasks.size();
     return 0;
 }

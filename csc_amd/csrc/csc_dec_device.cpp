@@ -11,6 +11,7 @@
 //     of the resumable kernel; the decoded run is copied back and handed to ISeqOutStream::Write.
 //   * CSCMI_DecodeDeviceBatch is the path without callbacks: streams that lie in device memory, raw bytes that stay
 //     there; block reader and run delivery are in the kernel (k_decode_dev*), the host only relaunches live streams.
+//     CSCMI_DecodeDeviceBatchStop is the same call with a stop position per stream (DecState::stop_at, DEC_STOPPED).
 // No CPU decoding path exists in this library.
 #include <hip/hip_runtime.h>
 
@@ -436,9 +437,20 @@ int CSCMI_DecodeBatch(int n, CSCDecHandle *hs, ISeqOutStream *const *oss, int *r
 // that refuses the run which would pass dst_cap (include/csc_mi355x.h).
 int CSCMI_DecodeDeviceBatch(int n, CSCMIDevDecode *jobs, const CSCMIDevDecodeOpts *opts, CSCMIDevDecodeStats *stats)
 {
+    if (stats) { stats->launches = stats->rounds = 0; stats->kernel_ms = 0; }   // (this call zeroes them even where no device is visible)
+    return CSCMI_DecodeDeviceBatchStop(n, jobs, NULL, opts, stats);
+}
+
+// The same with a stop position per stream (stop_at == NULL, or UINT64_MAX for a stream: none): the writer wants the first
+// stop_at[i] bytes and answers CSC_WRITE_ABORT once it has them.  The rule is the kernel's (decode_stream<true>): the run that
+// crosses the position is delivered clipped to it, and no run -- nor the end-of-stream signal -- is decoded behind it; a stopped
+// stream leaves the live list like one that has ended, so it is not launched again.
+int CSCMI_DecodeDeviceBatchStop(int n, CSCMIDevDecode *jobs, const uint64_t *stop_at, const CSCMIDevDecodeOpts *opts,
+                                CSCMIDevDecodeStats *stats)
+{
+    if (n > 0 && CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;           // nothing of the caller's is touched
     if (stats) { stats->launches = stats->rounds = 0; stats->kernel_ms = 0; }
     if (n <= 0) return 0;
-    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
     int device = 0;
     if (hipGetDevice(&device) != hipSuccess) return CSCMI_DEVICE_ERROR;
     uint64_t budget64 = opts && opts->launch_bytes ? opts->launch_bytes : kDevLaunchBytes;
@@ -478,6 +490,7 @@ int CSCMI_DecodeDeviceBatch(int n, CSCMIDevDecode *jobs, const CSCMIDevDecodeOpt
             dec_place(h, D, l);
             h.src = (const uint8_t *)job.src; h.src_size = job.src_size; h.src_pos = 0;
             h.dst = (uint8_t *)job.dst; h.dst_cap = job.dst_cap; h.produced = 0;
+            h.stop_at = stop_at ? stop_at[next] : UINT64_MAX;
             h.launch_budget = launch_budget;
             Slot s = {next, r, (DecState *)(D + l.o_state), (DecState *)(r->hslab + l.p_read)};
             *s.h_read = h;                                     // (pinned: the upload below reads it when the stream gets there)
@@ -525,6 +538,7 @@ int CSCMI_DecodeDeviceBatch(int n, CSCMIDevDecode *jobs, const CSCMIDevDecodeOpt
                 switch (r.status) {
                 case DEC_DONE: keep.push_back(k); break;                  // the launch budget: more to come
                 case DEC_END: job.rc = 0; break;
+                case DEC_STOPPED: job.rc = 0; break;                      // the caller has the bytes it asked for
                 case DEC_ERR_MINUS1: job.rc = -1; break;
                 case DEC_ERR_READ: job.rc = READ_ERROR; break;
                 case DEC_ERR_WRITE: job.rc = WRITE_ERROR; break;

@@ -1004,7 +1004,8 @@ DNOINL void d_deliver(dgu8 *dst, const dgu8 *src, uint32_t n)
 // DEV = false: one Decompress call, left with DEC_NEED_RC / DEC_NEED_BC whenever a block is wanted that the host has not uploaded
 // (k_decode_run*).  DEV = true (k_decode_dev*): the same machine, but where it would leave for a block -- rolled back to its
 // checkpoint, `need` set -- d_read_block fetches it from DecState::src and the machine goes on; a completed call's run is copied to
-// DecState::dst and the next call starts, until the stream ends or this launch has delivered launch_budget bytes.
+// DecState::dst and the next call starts, until the stream ends, `produced` reaches DecState::stop_at (DEC_STOPPED: the run that
+// crosses it is delivered clipped, no call is made behind it) or this launch has delivered launch_budget bytes.
 template <bool DEV>
 DDEV void decode_stream(gDecState *D, DecLds &lds)
 {
@@ -1051,18 +1052,22 @@ DDEV void decode_stream(gDecState *D, DecLds &lds)
     const uint32_t max = DUNI(D->raw_blocksize);
     Ck k;
     bool done = false;
-    uint64_t produced = 0, dst_cap = 0;
+    uint64_t produced = 0, dst_cap = 0, stop_at = 0;
     uint32_t launch_out = 0, launch_budget = 0;
     dgu8 *dst = nullptr;
     if (DEV) {
-        produced = U64(D->produced); dst_cap = U64(D->dst_cap); dst = (dgu8 *)U64((uint64_t)D->dst);
+        produced = U64(D->produced); dst_cap = U64(D->dst_cap); stop_at = U64(D->stop_at); dst = (dgu8 *)U64((uint64_t)D->dst);
         launch_budget = DUNI(D->launch_budget);
     }
     for (;;) {
     while (!done && !c.need && c.status == DEC_RUNNING) {
         switch (c.phase) {
         case DEC_PH_PRIME0:
-            if (dprime(c)) c.phase = DEC_PH_TYPE;
+            if (dprime(c)) {
+                c.phase = DEC_PH_TYPE;
+                // CSCDec_Create has succeeded (both first blocks are there); a stream that is wanted no byte of decodes no run
+                if (DEV && produced >= stop_at) c.status = DEC_STOPPED;
+            }
             break;
         case DEC_PH_TYPE: {
             ck_take(c, k);
@@ -1159,10 +1164,15 @@ DDEV void decode_stream(gDecState *D, DecLds &lds)
     c.woff[0] = c.woff[1] = 64;          // (a re-prime has moved on to new blocks: the byte windows are refetched, as at a launch's start)
     const uint32_t size = c.out_size;
     if (size == 0) { c.status = DEC_END; break; }
-    if (size > dst_cap - produced) { c.status = DEC_ERR_WRITE; break; }
-    d_deliver(dst + produced, c.out, size);
-    produced += size;
-    launch_out += size;
+    // the writer wants the first stop_at bytes (produced < stop_at here): the run clipped to them, whole or not at all, and
+    // CSC_WRITE_ABORT once it has them -- the next run, or the end-of-stream signal, is not decoded
+    const uint64_t want = stop_at - produced;
+    const uint32_t n = DUNI(size < want ? size : (uint32_t)want);
+    if (n > dst_cap - produced) { c.status = DEC_ERR_WRITE; break; }
+    d_deliver(dst + produced, c.out, n);
+    produced += n;
+    launch_out += n;
+    if (produced >= stop_at) { c.status = DEC_STOPPED; break; }
     if (launch_out >= launch_budget) break;
     }
     // store the stream state

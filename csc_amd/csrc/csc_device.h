@@ -121,7 +121,8 @@ struct EncState {
 constexpr uint32_t kDecUndoCap = 32768;   // probability updates journalled per packet (RLE run lengths can take ~14.6 K long-length bits)
 enum : uint32_t { DEC_RUNNING = 0, DEC_DONE = 1, DEC_NEED_RC = 2, DEC_NEED_BC = 3, DEC_ERR_DECODE = 4, DEC_ERR_MINUS1 = 5,
                   // k_decode_dev* only (the block reader and the run delivery are in the kernel; DEC_DONE there = launch budget used up, relaunch):
-                  DEC_ERR_READ = 6, DEC_ERR_WRITE = 7, DEC_NO_DECODER = 8, DEC_END = 9 };
+                  DEC_ERR_READ = 6, DEC_ERR_WRITE = 7, DEC_NO_DECODER = 8, DEC_END = 9,
+                  DEC_STOPPED = 10 };   // `produced` has reached DecState::stop_at: the stream ends here with rc 0, nothing behind it is decoded
 enum : uint32_t { DEC_PH_PRIME0 = 0, DEC_PH_TYPE, DEC_PH_SIZE, DEC_PH_LZ, DEC_PH_RAW, DEC_PH_POST, DEC_PH_TAIL, DEC_PH_PRIME };
 
 struct DecState {
@@ -148,6 +149,7 @@ struct DecState {
     const uint8_t *src;        // the stream behind its property bytes, any alignment
     uint8_t *dst;              // any alignment
     uint64_t src_size, src_pos, dst_cap, produced;
+    uint64_t stop_at;          // the stream stops once `produced` has reached it (a run is delivered clipped to it); UINT64_MAX = never
     uint32_t launch_budget, launch_out;   // launch_out: bytes the last launch delivered
     uint32_t probs[P_COUNT + 4];
     uint64_t dbg[16];          // development-only section timers (-DCSCMI_TIMERS builds); zero otherwise

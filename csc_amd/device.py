@@ -1,4 +1,4 @@
-"""Device-resident decode and encode: ctypes mirrors of CSCMI_DecodeDeviceBatch / CSCMI_EncodeDeviceBatch
+"""Device-resident decode and encode: ctypes mirrors of CSCMI_DecodeDeviceBatch(Stop) / CSCMI_EncodeDeviceBatch
 (include/csc_mi355x.h) and a torch front end for each.
 
 The streams lie in device memory and the raw bytes stay there: torch is the plumbing (allocation, upload of `bytes`
@@ -36,14 +36,27 @@ def bind(lib: CscLib):
     return fn
 
 
+def bind_stop(lib: CscLib):
+    fn = lib.lib.CSCMI_DecodeDeviceBatchStop
+    fn.argtypes = [C.c_int, C.POINTER(CSCMIDevDecode), C.POINTER(C.c_uint64), C.POINTER(CSCMIDevDecodeOpts),
+                   C.POINTER(CSCMIDevDecodeStats)]
+    fn.restype = C.c_int
+    return fn
+
+
+NO_STOP = (1 << 64) - 1     # stop_at[i] of a stream that is decoded to its end
+
+
 def default_cap(stream_len: int) -> int:
     """the destination size decode_device gives a stream when the caller names none: 64 bytes per stream byte, 1 MiB at least"""
     return max(1 << 20, 64 * stream_len)
 
 
 def decode_device(lib: CscLib, streams: Sequence, *, caps: Union[None, int, Sequence[int]] = None, launch_bytes: int = 0,
-                  dsts: Optional[Sequence] = None) -> Tuple[List[tuple], CSCMIDevDecodeStats]:
-    """Decode whole streams (each with its 10 property bytes) on the current device, all in ONE CSCMI_DecodeDeviceBatch call.
+                  dsts: Optional[Sequence] = None,
+                  stop_at: Union[None, int, Sequence[Optional[int]]] = None) -> Tuple[List[tuple], CSCMIDevDecodeStats]:
+    """Decode whole streams (each with its 10 property bytes) on the current device, all in ONE CSCMI_DecodeDeviceBatch call
+    (CSCMI_DecodeDeviceBatchStop where stop_at is given).
 
     streams       a list of `bytes` (uploaded here, in one copy) or of contiguous torch.uint8 CUDA tensors (used in place)
     caps          destination bytes per stream: one int for all, or one per stream.  A stream does not say how long its raw
@@ -52,17 +65,31 @@ def decode_device(lib: CscLib, streams: Sequence, *, caps: Union[None, int, Sequ
                   with WRITE_ERROR and the runs that fitted -- call again with a larger cap.
     dsts          instead of caps: the torch.uint8 CUDA tensors to decode into (cap = their size); any alignment
     launch_bytes  output per stream after which a launch returns (0 = the library's default)
+    stop_at       raw bytes wanted per stream: one int for all, or one per stream (None: to its end).  The decoder stops once
+                  they are delivered -- rc 0, the view is dst[:produced], nothing behind the position is decoded, `consumed` is
+                  informative.  With caps=None a stopped stream's destination is min(default_cap(len(stream)), its stop).
 
     Returns ([(rc, tensor_view_of_the_produced_bytes, consumed)], stats); rc is CSCDec_Decode's code for that stream, or
     CSCMI_NO_DECODER where CSCDec_Create would have refused it.  Raises RuntimeError if the call itself fails."""
     import torch
-    fn = bind(lib)
     n = len(streams)
+    stops = None
+    if stop_at is not None:
+        stop_at = [stop_at] * n if isinstance(stop_at, int) else list(stop_at)
+        if len(stop_at) != n:
+            raise ValueError("one stop per stream")
+        stops = (C.c_uint64 * max(n, 1))(*[NO_STOP if s is None else int(s) for s in stop_at])
+        call, what = bind_stop(lib), "CSCMI_DecodeDeviceBatchStop"
+
+        def fn(k, jobs, opts, st):
+            return call(k, jobs, stops, opts, st)
+    else:
+        fn, what = bind(lib), "CSCMI_DecodeDeviceBatch"
     stats = CSCMIDevDecodeStats()
     if n == 0:
         rc = fn(0, None, None, C.byref(stats))
         if rc != 0:
-            raise RuntimeError(f"CSCMI_DecodeDeviceBatch: {rc}")
+            raise RuntimeError(f"{what}: {rc}")
         return [], stats
     dev = torch.device("cuda", torch.cuda.current_device())
     lens = [len(s) if isinstance(s, (bytes, bytearray, memoryview)) else int(s.numel()) for s in streams]
@@ -84,6 +111,8 @@ def decode_device(lib: CscLib, streams: Sequence, *, caps: Union[None, int, Sequ
     if dsts is None:
         if caps is None:
             caps = [default_cap(ln) for ln in lens]
+            if stops is not None:
+                caps = [min(c, int(s)) for c, s in zip(caps, stops)]
         elif isinstance(caps, int):
             caps = [caps] * n
         dsts = [torch.empty(max(int(c), 1), dtype=torch.uint8, device=dev)[:int(c)] for c in caps]
@@ -102,7 +131,7 @@ def decode_device(lib: CscLib, streams: Sequence, *, caps: Union[None, int, Sequ
     opts = CSCMIDevDecodeOpts(int(launch_bytes))
     rc = fn(n, jobs, C.byref(opts), C.byref(stats))
     if rc != 0:
-        raise RuntimeError(f"CSCMI_DecodeDeviceBatch: {rc}")
+        raise RuntimeError(f"{what}: {rc}")
     del keep
     return [(int(j.rc), d[:int(j.produced)], int(j.consumed)) for j, d in zip(jobs, dsts)], stats
 

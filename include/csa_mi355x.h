@@ -187,7 +187,7 @@ typedef struct CSADevFile {
     int64_t esize, edate, eattr;   /* as CSA_List reports them */
     uint64_t offset;         /* into dst; a multiple of 16 */
     uint64_t size;           /* max(posfile + size) over the entry's fragments, 0 without any */
-    uint32_t nfrags, failed_frags;   /* failed_frags: CSAMI_DeviceRead only, else 0 */
+    uint32_t nfrags, failed_frags;   /* failed_frags: CSAMI_DeviceRead / CSAMI_DeviceReadStop only, else 0 */
 } CSADevFile;
 typedef struct CSADevReadStats {
     uint64_t tasks, frags, waves;   /* tasks decoded; their selected fragments of non-zero size; waves */
@@ -223,6 +223,31 @@ int CSAMI_DevicePlan(CSADevArchive *a, const char *const *names, int nnames,
  * fragment of a task is reported here and not there. */
 int CSAMI_DeviceRead(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
                      const CSAOptions *o, CSADevFile *files, uint32_t cap, CSADevReadStats *st);
+/* CSAMI_DeviceRead that costs what it selects: every decoded task stops behind its last selected byte.  Arguments, the layout of
+ * dst, files and *st are those of CSAMI_DeviceRead; stop_stats may be NULL.  It differs in four places only:
+ *   - a decoded task gets stop = max(posblock + size) over its SELECTED fragments of non-zero size (<= its raw size) and is decoded
+ *     by CSCMI_DecodeDeviceBatchStop (csc_mi355x.h) with stop_at = dst_cap = stop: the decoder delivers the run that reaches `stop`
+ *     clipped to it and decodes nothing behind it -- the callback path (CSA_Extract / CSA_Test) decodes one run more, the
+ *     reference an amount that depends on its writer thread's timing;
+ *   - the task's scratch is `stop` bytes (rounded up to 256) instead of its raw size;
+ *   - wave sizing reckons the decoded bytes at `stop`; the dictionary term (bounded by the raw size) and the room for a copy of
+ *     the coded stream stay as they are;
+ *   - the return value: as CSAMI_DeviceRead, except that damage wholly behind the run that reaches a task's `stop` is not seen,
+ *     nor a stream that holds more than its raw size -- which is what CSA_Test answers for damage behind the run after that one.
+ * Unchanged: a fragment is clipped to what was produced and verified only if a byte of it was delivered; st->launches ==
+ * 3 * st->waves; the read-back bound; and the gather: a task stream of more than one archive block is still copied WHOLE, because
+ * how many coded bytes a prefix of the raw bytes needs is not known before it is decoded.
+ * Out of scope: stopping inside a run (the granularity is one run, at most raw_blocksize = 2 MiB by default), byte ranges inside
+ * an entry, gathering part of a multi-block stream, and the host paths (CSA_Extract / CSA_Test), which stop as they did.
+ * Without a visible device CSCMI_DEVICE_ERROR is returned and nothing of the caller's is touched. */
+typedef struct CSADevStopStats {
+    uint64_t decoded_bytes;     /* sum of the decode jobs' `produced`: the sum of the tasks' stops where every stream is intact */
+    uint64_t task_raw_bytes;    /* sum of the decoded tasks' raw sizes: the capacities CSAMI_DeviceRead would have decoded into */
+    uint64_t scratch_bytes;     /* device bytes taken for decoded bytes: per wave, the sum of its tasks' stops each rounded up to 256 */
+    uint64_t stopped_tasks;     /* tasks with stop < raw size */
+} CSADevStopStats;
+int CSAMI_DeviceReadStop(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
+                         const CSAOptions *o, CSADevFile *files, uint32_t cap, CSADevReadStats *st, CSADevStopStats *stop_stats);
 /* HIP-event milliseconds of the last CSAMI_DeviceRead's launches by kernel: [0] k_gather_extents, [1] k_frag_pieces, [2] k_frag_fold */
 void CSAMI_DeviceKernelMs(const CSADevArchive *a, double ms[3]);
 void CSAMI_DeviceClose(CSADevArchive *a);
@@ -235,6 +260,12 @@ void CSAMI_DeviceClose(CSADevArchive *a);
 int CSAMI_PlanDeviceLayout(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
                            CSADevFile *files, uint32_t cap, uint32_t *n_files, uint64_t *dst_bytes,
                            uint64_t *task_raw_sizes, uint32_t task_cap, uint32_t *n_tasks);
+/* host only, no GPU: the tasks CSAMI_DeviceReadStop would decode for this selection, in the order it decodes them, from raw index
+ * bytes and with the strictness of CSAMI_PlanDeviceLayout (-1 for what that call refuses).  bids / stops / raws (each may be NULL)
+ * receive at most `cap` entries: the task's archive-blocks id, its stop position and its raw size (stop <= raw); *n_tasks their
+ * number.  No task is listed for a selection of directories and empty files only. */
+int CSAMI_PlanDeviceStops(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
+                          uint64_t *bids, uint64_t *stops, uint64_t *raws, uint32_t cap, uint32_t *n_tasks);
 
 /* ---- device-resident archive write: file bytes that lie in device memory to a .csa in device memory; not in the reference ----
  *

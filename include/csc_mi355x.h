@@ -145,6 +145,29 @@ typedef struct {
 typedef struct { uint64_t launch_bytes; } CSCMIDevDecodeOpts;   /* output per stream after which a launch returns; 0 = the library's default (4 MiB) */
 typedef struct { uint64_t launches, rounds; double kernel_ms; } CSCMIDevDecodeStats;   /* kernel launches, host rounds, HIP-event time of the launches */
 int CSCMI_DecodeDeviceBatch(int n, CSCMIDevDecode *jobs, const CSCMIDevDecodeOpts *opts, CSCMIDevDecodeStats *stats);
+/* CSCMI_DecodeDeviceBatch with a stop position per stream: job i is wanted only the first stop_at[i] raw bytes of, and its
+ * decoder stops once they are delivered.  stop_at == NULL, or stop_at[i] == UINT64_MAX, means no stop: rc, produced, consumed and
+ * dst of that job are then exactly what CSCMI_DecodeDeviceBatch gives (which is this call with NULL).
+ *
+ * jobs[i] is the answer of CSCDec_Create + CSCDec_Decode over an ISeqOutStream that wants the first stop_at[i] bytes and answers
+ * CSC_WRITE_ABORT (csc_dec.cpp:768-769) once it has them.  Per completed run of `size` bytes: n = min(size, stop_at - produced);
+ * if n > dst_cap - produced the stream ends with WRITE_ERROR and nothing of this run is delivered; otherwise n bytes are
+ * delivered, and once produced has reached stop_at the stream ends with rc = 0.  So
+ *   produced  min(stop_at, the stream's raw size) where rc == 0; with stop_at > dst_cap the call behaves as the plain one
+ *   consumed  the bytes the block reader had taken when the stream stopped, <= src_size: informative for a stopped stream (the
+ *             reader takes whole coder blocks, ahead of the decoder)
+ *   dst       bytes at and behind produced stay untouched, nothing outside [dst, dst + dst_cap) is stored
+ * No run is decoded once produced >= stop_at: not the run right behind one that ended exactly at stop_at, not the end-of-stream
+ * signal, and with stop_at == 0 no run at all -- the answers of CSCDec_Create still hold then (CSCMI_NO_DECODER for illegal
+ * props or a first block that is missing or cut).  Damage of the stream wholly behind the run that reaches stop_at is therefore
+ * not seen.  The position holds across launches (opts->launch_bytes): a stopped stream is not launched again.
+ * Where this differs from the reference: there `finished_` is set by the writer thread, asynchronously, with up to 8 MiB queued
+ * (csa_io.h:300-375), so how far the reference decodes behind the last wanted byte depends on timing; this library's callback
+ * path (CSA_Extract / CSA_Test) decodes exactly one run more than is wanted; this call decodes none.
+ * Out of scope: stopping INSIDE a run -- filtered runs are inverse-filtered whole, so the granularity of the work saved is one
+ * run (at most raw_blocksize, 2 MiB by default); the run that crosses stop_at is decoded whole and delivered clipped. */
+int CSCMI_DecodeDeviceBatchStop(int n, CSCMIDevDecode *jobs, const uint64_t *stop_at, const CSCMIDevDecodeOpts *opts,
+                                CSCMIDevDecodeStats *stats);
 /* Device-resident encode, the mirror image of CSCMI_DecodeDeviceBatch: n whole inputs that lie in device memory, encoded into
  * streams that lie in device memory.  The finished coder blocks are framed into dst by a kernel of their own (k_frame_blocks):
  * no block crosses the bus and no callback is made.  One-shot: per-stream state comes from the encoder's resource caches,

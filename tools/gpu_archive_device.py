@@ -12,6 +12,14 @@ the bytes each moved (gather: the bytes of streams of more than one archive bloc
 and stored again by extract).  Writes profiles/archive_device.md.
 
     python tools/gpu_archive_device.py [--repeats 5] [--out profiles/archive_device.md]
+    python tools/gpu_archive_device.py --stop-early [--select NAME...] [--repeats 5] [--out FILE]
+
+--stop-early measures something else: a SELECTION read by DeviceArchive.extract with and without stop_early (CSAMI_DeviceRead against
+CSAMI_DeviceReadStop, same handle, same session, alternating), on three archives: `one_ext` (24 files of 1 MiB with one extension:
+one large task), `tree_small`, and `split4` (one 16 MiB file written with split_count=4).  The selection is --select, or else the
+file that lies first in the archive's largest task.  Per archive: wall seconds per call of either, decoded_bytes / task_raw_bytes
+and the scratch bytes; the bytes delivered are compared.  Prints the section (and writes it to --out if given); it is the first
+part of profiles/archive_device_stop.md.
 
 Needs a GPU; there is no fallback.  The upload of the archive is outside the timed region (the caller of the device path holds
 it in HBM already -- that is the case the path is for); the file path's page cache is warm (tmpfs)."""
@@ -66,14 +74,102 @@ def spread(ts):
     return statistics.median(ts), min(ts), max(ts)
 
 
+def main_stop(args):
+    """--stop-early: a selection, with and without the stop"""
+    import torch
+    import cases
+    from csc_amd import csa, treegen
+    csa.lib()
+    shm = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None
+    root = tempfile.mkdtemp(prefix="csa_stop_", dir=shm)
+    lines = ["## A selection with and without the stop", "",
+             f"`tools/gpu_archive_device.py --stop-early --repeats {args.repeats}` on {torch.cuda.get_device_name(0)}: `DeviceArchive.extract(names)` "
+             "(CSAMI_DeviceRead, the parent commit's text) against `extract(names, stop_early=True)` (CSAMI_DeviceReadStop) on the same handle, "
+             "alternating, after one warm-up each.  Wall seconds per call: median (min .. max).", "",
+             "| archive | selection | tasks | full read s | stopped read s | decoded / task raw bytes | scratch bytes: full, stopped | decode launches: full, stopped |",
+             "|---|---|---|---|---|---|---|---|"]
+    cwd = os.getcwd()
+    try:
+        trees = {}
+        d = os.path.join(root, "one_ext")
+        os.makedirs(os.path.join(d, "data"))
+        for i in range(24):
+            with open(os.path.join(d, "data", f"a{i:04d}.npy"), "wb") as f:
+                f.write(cases.build([[("text", "exe", "delta")[i % 3], 300 + i, 0, 1 << 20]]))
+        trees["one_ext"] = (d, ["data"], dict(level=2, dict_size=32 << 20, recurse=True))
+        d = os.path.join(root, "tree_small")
+        os.makedirs(d)
+        treegen.materialize(d, "tree_small")
+        trees["tree_small"] = (d, ["t"], dict(level=3, dict_size=64 << 20, recurse=True))
+        d = os.path.join(root, "split4")
+        os.makedirs(d)
+        with open(os.path.join(d, "big.bin"), "wb") as f:
+            f.write(cases.build([["text", 340, 0, 16 << 20]]))
+        trees["split4"] = (d, ["big.bin"], dict(level=2, dict_size=32 << 20, split_count=4))
+        for name, (d, argv, opts) in trees.items():
+            os.chdir(d)
+            rc, _ = csa.add("out.csa", argv, overwrite=True, **opts)
+            if rc != 0:
+                raise SystemExit(f"csa.add {name}: rc={rc}")
+            data = open("out.csa", "rb").read()
+            names = args.select
+            if not names:                                  # the file that lies first in the largest task
+                raw = {}
+                entries = csa.list_entries("out.csa")
+                for e in entries:
+                    for f in e["frags"]:
+                        raw[f["bid"]] = max(raw.get(f["bid"], 0), f["posblock"] + f["size"])
+                big = max(raw, key=lambda b: raw[b])
+                names = [next(e["name"] for e in entries if any(f["bid"] == big and f["posblock"] == 0 and f["size"] for f in e["frags"]))]
+            dev = torch.frombuffer(bytearray(data), dtype=torch.uint8).cuda()
+            with csa.DeviceArchive.open(dev) as a:
+                total = a.plan(names)[1]
+                dsts = [torch.zeros(max(total, 1), dtype=torch.uint8, device="cuda") for _ in range(2)]
+                times, last = ([], []), [None, None]
+                for rep in range(args.repeats + 1):
+                    for k in ((0, 1) if rep % 2 == 0 else (1, 0)):
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        rc, views, st = a.extract(names, dst=dsts[k], stop_early=bool(k))
+                        dt = time.perf_counter() - t0
+                        assert rc == 0 and st["verify_failures"] == 0, (name, rc)
+                        last[k] = st
+                        if rep:
+                            times[k].append(dt)
+                assert bool((dsts[0] == dsts[1]).all()), "the stopped read delivered other bytes"
+                for f in last[1]["files"]:
+                    rel = f["name"]
+                    if os.path.isfile(rel):
+                        assert dsts[1][f["offset"]:f["offset"] + f["size"]].cpu().numpy().tobytes() == open(rel, "rb").read(), rel
+            full, stop = last
+            raw_scratch = csa.plan_device_stops(csa.read_index("out.csa"), len(data), names)[1]
+            fs = "%.4f (%.4f .. %.4f)"
+            lines.append(f"| {name} ({len(data)} bytes) | {' '.join(names)} | {stop['tasks']}, {stop['stopped_tasks']} stopped | {fs % spread(times[0])} | {fs % spread(times[1])} | "
+                         f"{stop['decoded_bytes']} / {stop['task_raw_bytes']} = {stop['decoded_bytes'] / max(stop['task_raw_bytes'], 1):.4f} | "
+                         f"{sum((t['raw'] + 255) // 256 * 256 for t in raw_scratch)}, {stop['scratch_bytes']} | {full['decode_launches']}, {stop['decode_launches']} |")
+    finally:
+        os.chdir(cwd)
+        shutil.rmtree(root, ignore_errors=True)
+    lines.append("")
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write("\n".join(lines))
+    print("\n".join(lines))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=5)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "archive_device.md"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--stop-early", action="store_true")
+    ap.add_argument("--select", nargs="+", default=None)
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("gpu_archive_device.py needs a GPU: a CPU run says nothing about these paths")
+    if args.stop_early or args.select:
+        return main_stop(args)
+    args.out = args.out or os.path.join(ROOT, "profiles", "archive_device.md")
     from csc_amd import csa
     csa.lib()
     shm = "/dev/shm" if os.path.isdir("/dev/shm") and os.access("/dev/shm", os.W_OK) else None

@@ -7,7 +7,11 @@ decode (CSCMI_DecodeDeviceBatch: streams in HBM, raw bytes in HBM) on three sets
 Each path decodes each set three times, in alternating order; every answer is compared with the input.  Prints, per set and
 path, MB/s of raw bytes per repeat, launches and rounds -- the table of profiles/decode_device.md.
 
-    python tools/gpu_decode_device.py [--lib PATH] [--launch-bytes N] [--sets tasks954,8x8MiB,1x16MiB]
+    python tools/gpu_decode_device.py [--lib PATH] [--launch-bytes N] [--sets tasks954,8x8MiB,1x16MiB] [--repeats N]
+                                      [--paths host,device,single] [--stop-at N]
+--stop-at N decodes only the first N raw bytes of every stream on the device path (CSCMI_DecodeDeviceBatchStop; the answer is
+compared with that prefix, MB/s are of the bytes delivered); --paths leaves paths out (the table of profiles/archive_device_stop.md
+is --paths device --repeats 5, with and without --lib).
 --lib names another build of the library (a parent commit's, for the baseline); one without CSCMI_DecodeDeviceBatch is measured on
 the callback paths only.  The development build (csc_amd/csrc/build/dev/libcsc_mi355x_timers.so) prints every launch's time on
 stderr: that is where the longest launch of profiles/decode_device.md comes from.
@@ -84,6 +88,8 @@ def main():
     ap.add_argument("--launch-bytes", type=int, default=0)
     ap.add_argument("--sets", default="tasks954,8x8MiB,1x16MiB")
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--paths", default="host,device,single")
+    ap.add_argument("--stop-at", type=int, default=None)
     a = ap.parse_args()
     import torch
     import csc_amd
@@ -113,7 +119,7 @@ def main():
         info = ""
         for rep in range(a.repeats):
             for path in (("host", "device") if rep % 2 == 0 else ("device", "host")):
-                if path == "device" and not has_dev:
+                if path not in a.paths or (path == "device" and not has_dev):
                     continue
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
@@ -122,14 +128,17 @@ def main():
                     dt = time.perf_counter() - t0
                     assert all(rc == 0 and out == d for (rc, out), d in zip(got, datas)), "callback path: wrong bytes"
                 else:
-                    res, st = decode_device(lib, devs, dsts=dsts, launch_bytes=a.launch_bytes)
+                    res, st = decode_device(lib, devs, dsts=dsts, launch_bytes=a.launch_bytes, stop_at=a.stop_at)
                     torch.cuda.synchronize()
                     dt = time.perf_counter() - t0
                     for (rc, t, consumed), d, s in zip(res, datas, streams):
-                        assert rc == 0 and consumed == len(s) - 10 and bytes(t.cpu().numpy().tobytes()) == d, "device path: wrong bytes"
+                        want = d if a.stop_at is None else d[:a.stop_at]
+                        assert rc == 0 and (consumed == len(s) - 10 or a.stop_at is not None) and bytes(t.cpu().numpy().tobytes()) == want, "device path: wrong bytes"
                     info = f"launches {st.launches} rounds {st.rounds} kernel {st.kernel_ms:.1f} ms"
-                rows[path].append(raw / 1e6 / dt)
-            if len(datas) == 1:
+                    if a.stop_at is not None:
+                        info += f"; stopped at {a.stop_at}: {sum(int(t.numel()) for _, t, _ in res)} bytes delivered in {dt * 1e3:.1f} ms"
+                rows[path].append((raw if path != "device" or a.stop_at is None else sum(min(a.stop_at, len(d)) for d in datas)) / 1e6 / dt)
+            if len(datas) == 1 and "single" in a.paths:
                 t0 = time.perf_counter()
                 rc, out = lib.decode(streams[0])
                 dt = time.perf_counter() - t0
@@ -139,7 +148,7 @@ def main():
                             ("single", "CSCDec_Decode, one stream")):
             if rows[path]:
                 v = rows[path]
-                print(f"{name:9s} {label:42s} MB/s " + " ".join(f"{x:8.2f}" for x in v) + f"   median {sorted(v)[len(v) // 2]:8.2f}  spread {max(v) - min(v):.2f}"
+                print(f"{name:9s} {label:42s} MB/s " + " ".join(f"{x:8.2f}" for x in v) + f"   median {sorted(v)[len(v) // 2]:8.2f}  min..max {min(v):.2f}..{max(v):.2f}"
                       + (f"   {info}" if path == "device" else ""), flush=True)
 
 
