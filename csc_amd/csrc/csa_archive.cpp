@@ -1,7 +1,9 @@
 // csa_archive.cpp -- the `.csa` container around the libcsc streams (C ABI in
 // include/csa_mi355x.h).  Host code, like the reference's src/archiver: directory scan, task split,
 // block table, index, file I/O.  The streams themselves come from the HIP encoder/decoder behind
-// CSCEnc_* / CSCDec_* in this same library, and the per-fragment adler32 from k_adler_pieces.
+// CSCEnc_* / CSCDec_* in this same library, and the per-fragment adler32 from k_frag_pieces
+// (csa_dev_kernels.hip).  The device-resident read and write are csa_dev_archive.cpp; what the two
+// share is csa_internal.h.
 //
 // Layout contract: CSA_Add writes what `csarc a -t1` writes -- tasks in task-id order, each chopped
 // into archive blocks by the 1 MiB coalescing rule of the reference's writer -- while encoding many
@@ -19,77 +21,21 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <functional>
-#include <list>
 #include <map>
-#include <mutex>
 #include <string>
 #include <thread>
 #include <vector>
 
-#include "../../include/csc_mi355x.h"
-#include "../../include/csa_mi355x.h"
+#include "csa_internal.h"
+#include "csa_waves.h"
+#include "csa_dev_read.h"
 
-void launch_adler_pieces(const void *pieces, void *out, uint32_t npieces, hipStream_t st);
+using namespace csa;
 
-namespace {
-
-constexpr uint32_t kMagicNum = 0x20130331u;          // csarc.cpp:283,593
-constexpr uint64_t kHeaderSize = 24;                 // csarc.cpp:561
-constexpr uint64_t kBlockCap = 1048576;              // csa_io.h:158
-constexpr uint32_t kAdlerBase = 65521;
-constexpr uint32_t kAdlerPiece = 16384;              // bytes per k_adler_pieces workgroup
-constexpr int kMaxStreams = 2048;        // = kMaxBatch of csc_host.cpp: one launch takes them all; the GPU starts the next workgroup where one ends
-constexpr int kStageBufs = 8;
-constexpr uint32_t kMaxFrags = CSA_MAX_FRAGMENTS;
-const char *const kDummyName = "****";               // csa_common.h:79
-
-double now_s()
-{
-    return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
-}
-
-// ---------------------------------------------------------------------------------------------
-// index model -- csa_typedef.h:12-90
-// ---------------------------------------------------------------------------------------------
-struct Entry {
-    int64_t edate = 0, esize = 0, eattr = 0;
-    char ext[4] = {0, 0, 0, 0};
-    std::vector<CSAFrag> frags;
-    uint32_t row = 0;              // CSAMI_DeviceWrite: the entry's row in the caller's table
-};
-typedef std::map<std::string, Entry> Index;
-
-struct FilePiece {                 // FileBlock: one file (or slice of it) inside a task
-    std::string path;
-    Index::iterator it;
-    uint32_t checksum = 0;
-    uint64_t off = 0, size = 0, posblock = 0;
-};
-struct Task {
-    uint64_t total = 0;
-    std::vector<FilePiece> files;
-    uint32_t ab_id = 0;
-    void add(const std::string &path, uint64_t off, uint64_t size, uint64_t posblock, uint32_t checksum, Index::iterator it)
-    {
-        FilePiece p;
-        p.path = path; p.off = off; p.size = size; p.posblock = posblock; p.checksum = checksum; p.it = it;
-        files.push_back(p);
-        total += size;
-    }
-};
-struct Extent { uint64_t off, size; };
-typedef std::map<uint64_t, std::vector<Extent>> BlockIndex;
-
-// ---------------------------------------------------------------------------------------------
-// little-endian fields -- csa_indexpack.cpp:5-66
-// ---------------------------------------------------------------------------------------------
-void put_le(std::vector<uint8_t> &v, uint64_t x, int n) { for (int i = 0; i < n; i++) v.push_back((uint8_t)(x >> (8 * i))); }
-void store_le(uint8_t *p, uint64_t x, int n) { for (int i = 0; i < n; i++) p[i] = (uint8_t)(x >> (8 * i)); }
-uint64_t load_le(const uint8_t *p, int n) { uint64_t x = 0; for (int i = n - 1; i >= 0; i--) x = (x << 8) | p[i]; return x; }
+namespace csa {
 
 // PackIndex, csa_indexpack.cpp:166-189.  The reference sizes the buffer with ArchiveBlocksSize (:127-134),
 // which still counts `4 + arcname.size()` per task for a name ArchiveBlocksToBuf (:136-150) stopped writing;
@@ -191,15 +137,9 @@ bool path_match(const char *a, const char *b)
     return *b == 0 || *b == '/';
 }
 
-struct Selection {
-    std::vector<std::string> names;
-    bool has(const char *name) const
-    {
-        if (names.empty()) return true;
-        for (const std::string &f : names) if (path_match(f.c_str(), name)) return true;
-        return false;
-    }
-};
+}   // namespace csa
+
+namespace {
 
 // ---------------------------------------------------------------------------------------------
 // archive-block writer -- csa_io.h:145-201 (AsyncWriter::flush / Write), :596-603 (Finish).
@@ -395,8 +335,10 @@ std::vector<Task> plan_tasks(Index &index, int split_count)
 // ---------------------------------------------------------------------------------------------
 // device side of one Add: chunk staging, adler pieces
 // ---------------------------------------------------------------------------------------------
-struct AdlerPieceH { const uint8_t *ptr; uint32_t len; uint32_t pad; };
-struct AdlerSumsH { uint64_t a, b; };
+using csadev::CopyPiece;
+using csadev::PieceSums;
+using csadev::kAdlerBase;
+using csadev::kFragPiece;                  // bytes per k_frag_pieces workgroup
 
 struct PieceRef { uint32_t slot; uint32_t file; uint32_t len; };     // which fragment a piece belongs to
 
@@ -430,10 +372,10 @@ struct FillLane {
     hipEvent_t stage_ev[kStageBufs] = {nullptr};
     bool stage_used[kStageBufs] = {false};
     int stage_next = 0;
-    std::vector<AdlerPieceH> pieces;
+    std::vector<CopyPiece> pieces;            // k_frag_pieces<false>: summed where they lie
     std::vector<PieceRef> refs;
     void *d_pieces = nullptr, *d_sums = nullptr;
-    AdlerSumsH *h_sums = nullptr;
+    PieceSums *h_sums = nullptr;
     size_t piece_cap = 0;
     uint64_t raw_bytes = 0;
 };
@@ -445,8 +387,6 @@ struct AddJob {
     std::vector<uint8_t *> chunk_groups;          // the slots' device chunks, kChunkGroup slots (x 2 buffers) per allocation
 };
 constexpr size_t kChunkGroup = 64;
-
-#define HIP_OK(x) ((x) == hipSuccess)
 
 // Fill the slot's device chunk with the next <= raw_blocksize bytes of its task (files back to back, what
 // AsyncReader::Read hands CSCEnc_Encode: full chunks until the task ends, csa_io.h:66-96) and queue the
@@ -483,9 +423,9 @@ int64_t fill_chunk(AddJob &J, FillLane &Ln, uint32_t slot_idx, Slot &s, uint8_t 
             fprintf(stderr, "csa-mi355x: %s: short read (file changed while archiving?)\n", f.path.c_str());
             return READ_ERROR;
         }
-        for (uint64_t o = 0; o < got; o += kAdlerPiece) {
-            uint32_t n = (uint32_t)std::min<uint64_t>(kAdlerPiece, got - o);
-            Ln.pieces.push_back(AdlerPieceH{d_dst + filled + o, n, 0});
+        for (uint64_t o = 0; o < got; o += kFragPiece) {
+            uint32_t n = (uint32_t)std::min<uint64_t>(kFragPiece, got - o);
+            Ln.pieces.push_back(CopyPiece{d_dst + filled + o, nullptr, n, 0});
             Ln.refs.push_back(PieceRef{slot_idx, (uint32_t)s.fi, n});
         }
         filled += got; s.fprog += got; s.cum += got;
@@ -509,15 +449,15 @@ int run_adler(AddJob &J, FillLane &Ln, std::vector<Slot> &slots)
         if (Ln.d_sums) (void)hipFree(Ln.d_sums);
         if (Ln.h_sums) (void)hipHostFree(Ln.h_sums);
         Ln.d_pieces = Ln.d_sums = nullptr; Ln.h_sums = nullptr;
-        if (!HIP_OK(hipMalloc(&Ln.d_pieces, cap * sizeof(AdlerPieceH))) || !HIP_OK(hipMalloc(&Ln.d_sums, cap * sizeof(AdlerSumsH)))
-            || !HIP_OK(hipHostMalloc((void **)&Ln.h_sums, cap * sizeof(AdlerSumsH), hipHostMallocDefault)))
+        if (!HIP_OK(hipMalloc(&Ln.d_pieces, cap * sizeof(CopyPiece))) || !HIP_OK(hipMalloc(&Ln.d_sums, cap * sizeof(PieceSums)))
+            || !HIP_OK(hipHostMalloc((void **)&Ln.h_sums, cap * sizeof(PieceSums), hipHostMallocDefault)))
             return CSCMI_DEVICE_ERROR;
         Ln.piece_cap = cap;
     }
-    if (!HIP_OK(hipMemcpyAsync(Ln.d_pieces, Ln.pieces.data(), n * sizeof(AdlerPieceH), hipMemcpyHostToDevice, Ln.st))) return CSCMI_DEVICE_ERROR;
-    launch_adler_pieces(Ln.d_pieces, Ln.d_sums, (uint32_t)n, Ln.st);
+    if (!HIP_OK(hipMemcpyAsync(Ln.d_pieces, Ln.pieces.data(), n * sizeof(CopyPiece), hipMemcpyHostToDevice, Ln.st))) return CSCMI_DEVICE_ERROR;
+    launch_frag_pieces(Ln.d_pieces, Ln.d_sums, (uint32_t)n, /*store=*/false, Ln.st);
     if (!HIP_OK(hipGetLastError())) return CSCMI_DEVICE_ERROR;
-    if (!HIP_OK(hipMemcpyAsync(Ln.h_sums, Ln.d_sums, n * sizeof(AdlerSumsH), hipMemcpyDeviceToHost, Ln.st))) return CSCMI_DEVICE_ERROR;
+    if (!HIP_OK(hipMemcpyAsync(Ln.h_sums, Ln.d_sums, n * sizeof(PieceSums), hipMemcpyDeviceToHost, Ln.st))) return CSCMI_DEVICE_ERROR;
     if (!HIP_OK(hipStreamSynchronize(Ln.st))) return CSCMI_DEVICE_ERROR;
     for (size_t i = 0; i < n; i++) {
         const PieceRef &r = Ln.refs[i];
@@ -579,7 +519,7 @@ int encode_tasks(std::vector<Task> &tasks, const EmitFn &emit, const CSAOptions 
 
     size_t mem_free = 0, mem_total = 0;
     if (!HIP_OK(hipMemGetInfo(&mem_free, &mem_total))) return CSCMI_DEVICE_ERROR;
-    const uint64_t budget = o.hbm_budget ? o.hbm_budget : (uint64_t)mem_free / 4 * 3;
+    const uint64_t budget = hbm_budget(o, mem_free);
     int max_streams = o.device_streams > 0 ? o.device_streams : kMaxStreams;
     if (max_streams > kMaxStreams) max_streams = kMaxStreams;
     uint64_t mem_used = 0;
@@ -761,12 +701,6 @@ int encode_index(const std::vector<uint8_t> &raw, std::vector<uint8_t> &out)
 // ---------------------------------------------------------------------------------------------
 // reading side
 // ---------------------------------------------------------------------------------------------
-// check_header, csarc.cpp:577-598
-bool header_ok(const uint8_t *h)
-{
-    return h[0] == 'C' && h[1] == 'S' && h[2] == 'A' && h[7] == '1' && (uint32_t)load_le(h + 3, 4) == kMagicNum;
-}
-
 // decompress_index, csarc.cpp:290-336.  0 ok, 1 cannot open / bad header, -1 undecodable index.
 int read_index(const char *arcname, Index &index, BlockIndex &abindex, std::vector<uint8_t> *raw_out = nullptr)
 {
@@ -1045,22 +979,17 @@ int read_archive(const char *arcname, const Selection &sel, const CSAOptions &o,
     // waves of tasks, largest first (csarc.cpp:430): as many streams per launch as there are CUs, within the HBM budget
     size_t mem_free = 0, mem_total = 0;
     if (hipMemGetInfo(&mem_free, &mem_total) != hipSuccess) { close(arc_fd); return CSCMI_DEVICE_ERROR; }
-    const uint64_t budget = o.hbm_budget ? o.hbm_budget : (uint64_t)mem_free / 4 * 3;
+    const uint64_t budget = hbm_budget(o, mem_free);
     const size_t width = o.device_streams > 0 ? (size_t)o.device_streams : 256;
     std::atomic<uint32_t> failures(0);
     int worst = 0;
     double t1 = now_s();
     for (size_t first = 0; first < tasks.size();) {
-        size_t count = 0;
-        uint64_t mem = 0;
-        while (first + count < tasks.size() && count < width) {
-            // a decoder holds the dictionary (unknown before its header is read; bounded by the task's raw size
-            // and by 1 GiB) plus ~24 MiB of rings and buffers
-            uint64_t need = std::min<uint64_t>(std::max<uint64_t>(tasks[first + count].total, 1u << 20), 1ull << 30) + (24ull << 20);
-            if (count && mem + need > budget) break;
-            mem += need;
-            count++;
-        }
+        // a decoder holds the dictionary (unknown before its header is read; bounded by the task's raw size
+        // and by 1 GiB) plus ~24 MiB of rings and buffers
+        const size_t count = wave_count(first, tasks.size(), width, budget, [&](size_t t) {
+            return std::min<uint64_t>(std::max<uint64_t>(tasks[t].total, 1u << 20), 1ull << 30) + (24ull << 20);
+        });
         int r = decode_wave(arc_fd, tasks, first, count, abindex, &failures);
         if (r < 0) worst = r;
         first += count;
@@ -1079,13 +1008,6 @@ int read_archive(const char *arcname, const Selection &sel, const CSAOptions &o,
         return -1;
     }
     return unsafe ? CSA_UNSAFE_NAME : 0;
-}
-
-Selection make_selection(const char *const *names, int n)
-{
-    Selection s;
-    for (int i = 0; i < n; i++) s.names.push_back(names[i]);
-    return s;
 }
 
 }   // namespace
@@ -1120,17 +1042,16 @@ uint32_t CSA_Adler32(uint32_t adler, const uint8_t *buf, uint64_t len)
 int CSAMI_Adler32Device(uint32_t adler, const void *device_ptr, uint64_t len, uint32_t *out)
 {
     if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
-    std::vector<AdlerPieceH> pieces;
-    for (uint64_t o = 0; o < len; o += kAdlerPiece)
-        pieces.push_back(AdlerPieceH{(const uint8_t *)device_ptr + o, (uint32_t)std::min<uint64_t>(kAdlerPiece, len - o), 0});
-    std::vector<AdlerSumsH> sums(pieces.size());
+    std::vector<CopyPiece> pieces;
+    csadev::piece_split((const uint8_t *)device_ptr, nullptr, len, kFragPiece, [&](uint64_t, const CopyPiece &p) { pieces.push_back(p); });
+    std::vector<PieceSums> sums(pieces.size());
     if (!pieces.empty()) {
         void *dp = nullptr, *ds = nullptr;
-        bool ok = HIP_OK(hipMalloc(&dp, pieces.size() * sizeof(AdlerPieceH))) && HIP_OK(hipMalloc(&ds, pieces.size() * sizeof(AdlerSumsH)));
-        ok = ok && HIP_OK(hipMemcpy(dp, pieces.data(), pieces.size() * sizeof(AdlerPieceH), hipMemcpyHostToDevice));
+        bool ok = HIP_OK(hipMalloc(&dp, pieces.size() * sizeof(CopyPiece))) && HIP_OK(hipMalloc(&ds, pieces.size() * sizeof(PieceSums)));
+        ok = ok && HIP_OK(hipMemcpy(dp, pieces.data(), pieces.size() * sizeof(CopyPiece), hipMemcpyHostToDevice));
         if (ok) {
-            launch_adler_pieces(dp, ds, (uint32_t)pieces.size(), nullptr);
-            ok = HIP_OK(hipGetLastError()) && HIP_OK(hipMemcpy(sums.data(), ds, pieces.size() * sizeof(AdlerSumsH), hipMemcpyDeviceToHost));
+            launch_frag_pieces(dp, ds, (uint32_t)pieces.size(), /*store=*/false, nullptr);
+            ok = HIP_OK(hipGetLastError()) && HIP_OK(hipMemcpy(sums.data(), ds, pieces.size() * sizeof(PieceSums), hipMemcpyDeviceToHost));
         }
         if (dp) (void)hipFree(dp);
         if (ds) (void)hipFree(ds);
@@ -1179,16 +1100,7 @@ int64_t CSA_UnixTime(int64_t date)
 }   // extern "C"
 
 // ---- pieces of Add shared by the one-process path and the sharded (one process per GPU) path ----
-namespace {
-
-struct AddPlan {
-    CSAOptions o;
-    Index index;
-    std::vector<Task> tasks;
-};
-
-// the tasks of P.index under P.o, whoever filled the index: the directory scan (plan_add) or the caller's table (plan_write)
-int plan_index(AddPlan &P)
+int csa::plan_index(AddPlan &P)
 {
     if (P.o.split_count <= 0) P.o.split_count = 1;                           // csarc.cpp:199-200
     P.tasks = plan_tasks(P.index, P.o.split_count);
@@ -1205,6 +1117,8 @@ int plan_index(AddPlan &P)
             }
     return 0;
 }
+
+namespace {
 
 int plan_add(AddPlan &P, const char *const *filenames, int nfilenames, const CSAOptions *opt)
 {
@@ -1548,893 +1462,6 @@ int64_t CSA_ReadIndex(const char *arcname, uint8_t *buf, uint64_t cap)
     if (read_index(arcname, index, abindex, &raw) != 0) return -1;
     if (buf) memcpy(buf, raw.data(), (size_t)std::min<uint64_t>(cap, raw.size()));
     return (int64_t)raw.size();
-}
-
-}   // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// device-resident read: CSAMI_DeviceOpen / Plan / Read / Close, CSAMI_PlanDeviceLayout (include/csa_mi355x.h).
-// Host side: the index, the layout of dst, the validation of everything the index says, the piece tables.  The bytes move in
-// csa_dev_kernels.hip (tables and copy: csa_dev_read.h) and in CSCMI_DecodeDeviceBatch; CSAMI_DeviceReadStop is the same body with
-// every task stopped behind its last selected byte (CSCMI_DecodeDeviceBatchStop).
-// ---------------------------------------------------------------------------------------------
-#include "csa_dev_read.h"
-
-void launch_gather_extents(const void *pieces, uint32_t npieces, hipStream_t st);
-void launch_frag_pieces(const void *pieces, void *sums, uint32_t npieces, bool store, hipStream_t st);
-void launch_frag_fold(const void *frags, const void *sums, void *out, uint32_t nfrags, hipStream_t st);
-
-struct CSADevArchive {
-    const uint8_t *arc = nullptr;
-    uint64_t arc_size = 0;
-    Index index;
-    BlockIndex abindex;
-    std::map<uint64_t, uint64_t> task_raw;     // bid -> raw size
-    uint64_t open_readback = 0;
-    double kernel_ms[3] = {0, 0, 0};
-};
-
-namespace {
-
-bool add_ok(uint64_t a, uint64_t b, uint64_t *out) { return !__builtin_add_overflow(a, b, out); }
-
-struct DevFilePlan { Index::const_iterator it; uint64_t offset, size; };
-struct DevFrag { uint32_t file; uint32_t checksum; uint64_t posblock, size, posfile; };
-struct DevTask { uint64_t bid = 0, total = 0, raw = 0, stop = 0; std::vector<DevFrag> frags; };   // stop: max(posblock + size) over `frags`, <= raw
-struct DevLayout {
-    std::vector<DevFilePlan> files;
-    std::vector<DevTask> tasks;                // decode order
-    uint64_t dst_bytes = 0;
-};
-
-// A task's raw size: max(posblock + size) over ALL fragments of its bid.  false if any sum of the index wraps.
-bool dev_task_sizes(const Index &index, std::map<uint64_t, uint64_t> &raw)
-{
-    raw.clear();
-    for (const auto &kv : index)
-        for (const CSAFrag &f : kv.second.frags) {
-            uint64_t end, fend;
-            if (!add_ok(f.posblock, f.size, &end) || !add_ok(f.posfile, f.size, &fend)) return false;
-            uint64_t &r = raw[f.bid];
-            r = std::max(r, end);
-        }
-    return true;
-}
-
-// The layout of dst and the tasks to decode for a selection.  false if the sum wraps.
-bool dev_layout(const Index &index, const std::map<uint64_t, uint64_t> &raw, const Selection &sel, DevLayout &L)
-{
-    std::map<uint64_t, size_t> idmap;
-    uint64_t off = 0;
-    for (Index::const_iterator it = index.begin(); it != index.end(); ++it) {
-        if (!sel.has(it->first.c_str())) continue;
-        uint64_t size = 0;
-        const uint32_t fi = (uint32_t)L.files.size();
-        for (const CSAFrag &f : it->second.frags) {
-            size = std::max(size, f.posfile + f.size);                     // (checked by dev_task_sizes)
-            if (!f.size) continue;
-            auto m = idmap.find(f.bid);
-            if (m == idmap.end()) {
-                m = idmap.insert(std::make_pair((uint64_t)f.bid, L.tasks.size())).first;
-                L.tasks.push_back(DevTask());
-                L.tasks.back().bid = f.bid;
-                L.tasks.back().raw = raw.at(f.bid);
-            }
-            DevTask &t = L.tasks[m->second];
-            t.frags.push_back(DevFrag{fi, f.checksum, f.posblock, f.size, f.posfile});
-            if (!add_ok(t.total, f.size, &t.total)) return false;
-            t.stop = std::max(t.stop, f.posblock + f.size);               // (checked by dev_task_sizes)
-        }
-        L.files.push_back(DevFilePlan{it, off, size});
-        uint64_t r;
-        if (!add_ok(size, 15, &r) || !add_ok(off, r & ~15ull, &off)) return false;
-    }
-    L.dst_bytes = off;
-    std::sort(L.tasks.begin(), L.tasks.end(), [](const DevTask &a, const DevTask &b) {                        // csarc.cpp:430
-        return a.total != b.total ? a.total > b.total : a.bid < b.bid;
-    });
-    return true;
-}
-
-void dev_fill_files(const DevLayout &L, CSADevFile *files, uint32_t cap)
-{
-    for (size_t i = 0; files && i < L.files.size() && i < cap; i++) {
-        const DevFilePlan &p = L.files[i];
-        CSADevFile &f = files[i];
-        f.name = p.it->first.c_str();
-        f.esize = p.it->second.esize; f.edate = p.it->second.edate; f.eattr = p.it->second.eattr;
-        f.offset = p.offset; f.size = p.size;
-        f.nfrags = (uint32_t)p.it->second.frags.size(); f.failed_frags = 0;
-    }
-}
-
-// AsyncArchiveReader (csa_io.h:466-542) over a buffer: the task's archive blocks, each clipped to the archive; the first one
-// that is cut short ends the stream (ExtentSource: a short read is end of file).  false if the total wraps.
-bool dev_stream_extents(const std::vector<Extent> &in, uint64_t arc_size, std::vector<Extent> &out, uint64_t &total)
-{
-    out.clear();
-    total = 0;
-    for (const Extent &x : in) {
-        const uint64_t avail = x.off < arc_size ? std::min<uint64_t>(x.size, arc_size - x.off) : 0;
-        if (avail) {
-            out.push_back(Extent{x.off, avail});
-            if (!add_ok(total, avail, &total)) return false;
-        }
-        if (avail < x.size) break;
-    }
-    return true;
-}
-
-struct DevBuf {                                // device memory released at scope end
-    void *p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    bool alloc(uint64_t n) { return n <= (uint64_t)SIZE_MAX && HIP_OK(hipMalloc(&p, (size_t)std::max<uint64_t>(n, 16))); }
-    bool upload(const void *src, uint64_t n) { return alloc(n) && (!n || HIP_OK(hipMemcpy(p, src, (size_t)n, hipMemcpyHostToDevice))); }
-};
-
-struct DevTimer {                              // HIP-event time of this layer's three launches, by kernel
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    hipStream_t st = nullptr;
-    bool ok = false;
-    DevTimer() { ok = HIP_OK(hipEventCreate(&ev[0])) && HIP_OK(hipEventCreate(&ev[1])); }
-    ~DevTimer() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    void begin() { (void)hipEventRecord(ev[0], st); }
-    bool end(double *ms)                       // waits for the launch
-    {
-        float f = 0;
-        if (!HIP_OK(hipGetLastError()) || !HIP_OK(hipEventRecord(ev[1], st)) || !HIP_OK(hipEventSynchronize(ev[1]))) return false;
-        if (HIP_OK(hipEventElapsedTime(&f, ev[0], ev[1]))) *ms += f;
-        return true;
-    }
-};
-
-// One wave: tasks [first, first + count) of L.  Returns 0, -1 (a stream failed) or CSCMI_DEVICE_ERROR.
-// SS != nullptr (CSAMI_DeviceReadStop): a task is decoded only up to its `stop` -- capacity, scratch and stop position are that --
-// and SS is added to.  The coded stream of a task of several archive blocks is still gathered whole: how many coded bytes a
-// prefix of the raw bytes needs is not known before it is decoded.
-int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t count, uint8_t *dst, std::vector<uint32_t> &failed,
-                  CSADevReadStats &S, DevTimer &tm, CSADevStopStats *SS)
-{
-    using namespace csadev;
-    static const std::vector<Extent> kNoBlocks;
-    int worst = 0;
-    // 1. the streams: where each task's coded bytes lie, what has to be gathered, where its decoded bytes go
-    std::vector<std::vector<Extent>> ext(count);
-    std::vector<uint64_t> total(count, 0), gat_off(count, 0), raw_off(count, 0);
-    uint64_t gat_bytes = 0, raw_bytes = 0;
-    for (size_t k = 0; k < count; k++) {
-        const DevTask &t = L.tasks[first + k];
-        auto ab = A.abindex.find(t.bid);
-        if (!dev_stream_extents(ab == A.abindex.end() ? kNoBlocks : ab->second, A.arc_size, ext[k], total[k])) return CSCMI_DEVICE_ERROR;
-        uint64_t r;
-        if (total[k] > CSC_PROP_SIZE && ext[k].size() > 1) {
-            gat_off[k] = gat_bytes;
-            if (!add_ok(total[k] - CSC_PROP_SIZE, 255, &r) || !add_ok(gat_bytes, r & ~255ull, &gat_bytes)) return CSCMI_DEVICE_ERROR;
-        }
-        raw_off[k] = raw_bytes;
-        if (!add_ok(SS ? t.stop : t.raw, 255, &r) || !add_ok(raw_bytes, r & ~255ull, &raw_bytes)) return CSCMI_DEVICE_ERROR;
-    }
-    DevBuf d_gat, d_raw, d_props;
-    if (!d_gat.alloc(gat_bytes) || !d_raw.alloc(raw_bytes) || !d_props.alloc(16 * count)) return CSCMI_DEVICE_ERROR;
-
-    // 2. gather: the property bytes of every task (they may span blocks) and the streams of more than one block
-    std::vector<CopyPiece> gp;
-    for (size_t k = 0; k < count; k++) {
-        uint64_t pos = 0;                                                    // position in the task's stream
-        for (const Extent &x : ext[k]) {
-            const uint8_t *src = A.arc + x.off;
-            uint64_t n = x.size;
-            if (pos < CSC_PROP_SIZE) {
-                const uint64_t h = std::min<uint64_t>(CSC_PROP_SIZE - pos, n);
-                gp.push_back(CopyPiece{src, (uint8_t *)d_props.p + 16 * k + pos, (uint32_t)h, 0});
-                src += h; n -= h; pos += h;
-            }
-            if (ext[k].size() > 1 && n)
-                piece_split(src, (uint8_t *)d_gat.p + gat_off[k] + (pos - CSC_PROP_SIZE), n, kGatherPiece,
-                            [&](uint64_t, const CopyPiece &p) { gp.push_back(p); });
-            pos += n;
-        }
-    }
-    if (gp.size() > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
-    std::vector<uint8_t> props(16 * count, 0);
-    {
-        DevBuf d_gp;
-        if (!d_gp.upload(gp.data(), gp.size() * sizeof(CopyPiece))) return CSCMI_DEVICE_ERROR;
-        tm.begin();
-        launch_gather_extents(d_gp.p, (uint32_t)gp.size(), tm.st);
-        S.launches++;
-        if (!tm.end(&A.kernel_ms[0])) return CSCMI_DEVICE_ERROR;
-        if (!HIP_OK(hipMemcpy(props.data(), d_props.p, props.size(), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-        S.readback_bytes += props.size();
-    }
-
-    // 3. decode: csa_worker.cpp:59-90 for every task of the wave at once
-    std::vector<CSCMIDevDecode> jobs;
-    std::vector<size_t> job_task;
-    std::vector<uint64_t> stops;
-    std::vector<uint64_t> produced(count, 0);
-    for (size_t k = 0; k < count; k++) {
-        if (total[k] < CSC_PROP_SIZE) { worst = -1; continue; }               // csa_worker.cpp:77-80: no property bytes, no decoder
-        CSCMIDevDecode j;
-        memset(&j, 0, sizeof(j));
-        CSCDec_ReadProperties(&j.props, props.data() + 16 * k);
-        j.src = ext[k].size() > 1 ? (const uint8_t *)d_gat.p + gat_off[k] : A.arc + ext[k][0].off + CSC_PROP_SIZE;
-        j.src_size = (size_t)(total[k] - CSC_PROP_SIZE);
-        j.dst = (uint8_t *)d_raw.p + raw_off[k];
-        j.dst_cap = (size_t)(SS ? L.tasks[first + k].stop : L.tasks[first + k].raw);
-        jobs.push_back(j);
-        job_task.push_back(k);
-        stops.push_back(j.dst_cap);
-    }
-    if (SS) {
-        SS->scratch_bytes += raw_bytes;
-        for (size_t k = 0; k < count; k++) {
-            const DevTask &t = L.tasks[first + k];
-            SS->task_raw_bytes += t.raw;
-            if (t.stop < t.raw) SS->stopped_tasks++;
-        }
-    }
-    if (!jobs.empty()) {
-        CSCMIDevDecodeStats ds;
-        memset(&ds, 0, sizeof(ds));
-        if ((SS ? CSCMI_DecodeDeviceBatchStop((int)jobs.size(), jobs.data(), stops.data(), NULL, &ds)
-                : CSCMI_DecodeDeviceBatch((int)jobs.size(), jobs.data(), NULL, &ds)) != 0) return CSCMI_DEVICE_ERROR;
-        S.decode_launches += ds.launches;
-        for (size_t i = 0; i < jobs.size(); i++) {
-            if (jobs[i].rc == CSCMI_DEVICE_ERROR) return CSCMI_DEVICE_ERROR;
-            if (SS) SS->decoded_bytes += jobs[i].produced;
-            if (jobs[i].rc != 0) worst = -1;                                   // (WRITE_ERROR: more than the raw size -- a decode error here)
-            produced[job_task[i]] = std::min<uint64_t>(jobs[i].produced, jobs[i].dst_cap);   // a failed stream still delivered this much
-        }
-    }
-
-    // 4. scatter and verify: the fragments at least one byte of which was delivered, clipped to what was delivered
-    std::vector<CopyPiece> fp;
-    std::vector<FragFold> ff;
-    std::vector<uint32_t> ff_file;
-    for (size_t k = 0; k < count; k++) {
-        const DevTask &t = L.tasks[first + k];
-        for (const DevFrag &f : t.frags) {
-            if (f.posblock >= produced[k]) continue;
-            const uint64_t n = std::min<uint64_t>(f.size, produced[k] - f.posblock);
-            const uint64_t np = piece_count(n, kFragPiece);
-            if (fp.size() + np > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
-            ff.push_back(FragFold{n, (uint32_t)fp.size(), (uint32_t)np, f.checksum, 0});
-            ff_file.push_back(f.file);
-            piece_split((const uint8_t *)d_raw.p + raw_off[k] + f.posblock, dst ? dst + L.files[f.file].offset + f.posfile : nullptr, n, kFragPiece,
-                        [&](uint64_t, const CopyPiece &p) { fp.push_back(p); });
-        }
-    }
-    DevBuf d_fp, d_ff, d_sums, d_res;
-    if (!d_fp.upload(fp.data(), fp.size() * sizeof(CopyPiece)) || !d_ff.upload(ff.data(), ff.size() * sizeof(FragFold))
-        || !d_sums.alloc(fp.size() * sizeof(PieceSums)) || !d_res.alloc(ff.size() * sizeof(FragResult))) return CSCMI_DEVICE_ERROR;
-    tm.begin();
-    launch_frag_pieces(d_fp.p, d_sums.p, (uint32_t)fp.size(), dst != nullptr, tm.st);
-    S.launches++;
-    if (!tm.end(&A.kernel_ms[1])) return CSCMI_DEVICE_ERROR;
-    tm.begin();
-    launch_frag_fold(d_ff.p, d_sums.p, d_res.p, (uint32_t)ff.size(), tm.st);
-    S.launches++;
-    if (!tm.end(&A.kernel_ms[2])) return CSCMI_DEVICE_ERROR;
-    std::vector<FragResult> res(ff.size());
-    if (!res.empty() && !HIP_OK(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(FragResult), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-    S.readback_bytes += res.size() * sizeof(FragResult);
-    for (size_t i = 0; i < res.size(); i++)
-        if (!res[i].ok) {
-            fprintf(stderr, "******** %s extraction/verify failed\n", L.files[ff_file[i]].it->first.c_str());   // csa_io.h:332,398
-            failed[ff_file[i]]++;
-            S.verify_failures++;
-        }
-    return worst;
-}
-
-}   // namespace
-
-extern "C" {
-
-int CSAMI_DeviceOpen(const void *arc_dev, uint64_t arc_size, CSADevArchive **out)
-{
-    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
-    const uint8_t *arc = (const uint8_t *)arc_dev;
-    uint8_t hdr[kHeaderSize];
-    if (!arc || arc_size < kHeaderSize) { fprintf(stderr, "Invalid csarc file\n"); return 1; }
-    if (!HIP_OK(hipMemcpy(hdr, arc, kHeaderSize, hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-    if (!header_ok(hdr)) { fprintf(stderr, "Invalid csarc file\n"); return 1; }
-    const uint64_t index_pos = load_le(hdr + 8, 8);
-    const uint32_t csize = (uint32_t)load_le(hdr + 16, 4), rsize = (uint32_t)load_le(hdr + 20, 4);
-    if (index_pos > arc_size || csize > arc_size - index_pos || csize < CSC_PROP_SIZE) { fprintf(stderr, "Invalid csarc file\n"); return -1; }
-    uint8_t ph[CSC_PROP_SIZE];
-    if (!HIP_OK(hipMemcpy(ph, arc + index_pos, CSC_PROP_SIZE, hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-    std::vector<uint8_t> raw(rsize);
-    {
-        DevBuf d_raw;
-        if (!d_raw.alloc(rsize)) return CSCMI_DEVICE_ERROR;
-        CSCMIDevDecode j;
-        memset(&j, 0, sizeof(j));
-        CSCDec_ReadProperties(&j.props, ph);
-        j.src = arc + index_pos + CSC_PROP_SIZE;
-        j.src_size = csize - CSC_PROP_SIZE;
-        j.dst = d_raw.p;
-        j.dst_cap = rsize;
-        if (CSCMI_DecodeDeviceBatch(1, &j, NULL, NULL) != 0 || j.rc == CSCMI_DEVICE_ERROR) return CSCMI_DEVICE_ERROR;
-        if (j.rc != 0 || j.produced != rsize) { fprintf(stderr, "Invalid csarc file (index)\n"); return -1; }
-        if (rsize && !HIP_OK(hipMemcpy(raw.data(), d_raw.p, rsize, hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-    }
-    CSADevArchive *A = new CSADevArchive();
-    A->arc = arc;
-    A->arc_size = arc_size;
-    A->open_readback = kHeaderSize + CSC_PROP_SIZE + rsize;
-    if (!unpack_index(A->index, A->abindex, raw.data(), rsize) || !dev_task_sizes(A->index, A->task_raw)) {
-        fprintf(stderr, "Invalid csarc file (index)\n");
-        delete A;
-        return -1;
-    }
-    *out = A;
-    return 0;
-}
-
-int CSAMI_DevicePlan(CSADevArchive *a, const char *const *names, int nnames,
-                     CSADevFile *files, uint32_t cap, uint32_t *n_files, uint64_t *dst_bytes)
-{
-    DevLayout L;
-    if (!a || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L)) return -1;
-    dev_fill_files(L, files, cap);
-    if (n_files) *n_files = (uint32_t)L.files.size();
-    if (dst_bytes) *dst_bytes = L.dst_bytes;
-    return 0;
-}
-
-}   // extern "C"
-
-namespace {
-
-// CSAMI_DeviceRead (ss == nullptr) and CSAMI_DeviceReadStop (ss: its stop statistics, never null there)
-int dev_read(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
-             const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st, CSADevStopStats *ss)
-{
-    const double t0 = now_s();
-    CSADevReadStats S;
-    memset(&S, 0, sizeof(S));
-    if (st) *st = S;
-    DevLayout L;
-    if (!a || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L)) return -1;
-    dev_fill_files(L, files, cap);
-    if (dst && dst_cap < L.dst_bytes) return WRITE_ERROR;
-    CSAOptions o;
-    if (opt) o = *opt; else CSA_OptionsInit(&o);
-    a->kernel_ms[0] = a->kernel_ms[1] = a->kernel_ms[2] = 0;
-
-    size_t mem_free = 0, mem_total = 0;
-    if (!HIP_OK(hipMemGetInfo(&mem_free, &mem_total))) return CSCMI_DEVICE_ERROR;
-    const uint64_t budget = o.hbm_budget ? o.hbm_budget : (uint64_t)mem_free / 4 * 3;
-    const size_t width = o.device_streams > 0 ? (size_t)o.device_streams : L.tasks.size();
-    DevTimer tm;
-    if (!tm.ok) return CSCMI_DEVICE_ERROR;
-    std::vector<uint32_t> failed(L.files.size(), 0);
-    int worst = 0;
-    S.readback_bytes = a->open_readback;
-    for (size_t first = 0; first < L.tasks.size() && worst != CSCMI_DEVICE_ERROR;) {
-        size_t count = 0;
-        uint64_t mem = 0;
-        while (first + count < L.tasks.size() && count < width) {
-            // the task's decoded bytes and (at most) a copy of its stream, plus what its decoder holds: the dictionary (bounded by
-            // the raw size and by 1 GiB) and ~24 MiB of rings and buffers, as read_archive reckons
-            // (stopped early: the decoded bytes are `stop`; the dictionary and the stream's copy are what they were)
-            const uint64_t raw = L.tasks[first + count].raw, out = ss ? L.tasks[first + count].stop : raw;
-            uint64_t need = std::min<uint64_t>(std::max<uint64_t>(raw, 1u << 20), 1ull << 30) + (24ull << 20);
-            if (!add_ok(need, out, &need) || !add_ok(need, raw, &need)) need = UINT64_MAX;
-            if (count && (mem + need < mem || mem + need > budget)) break;
-            mem += need;
-            count++;
-        }
-        int r = dev_read_wave(*a, L, first, count, (uint8_t *)dst, failed, S, tm, ss);
-        if (r < 0 && worst != CSCMI_DEVICE_ERROR) worst = r;
-        S.waves++;
-        for (size_t k = first; k < first + count; k++) { S.tasks++; S.frags += L.tasks[k].frags.size(); S.raw_bytes += L.tasks[k].total; }
-        first += count;
-    }
-    for (size_t i = 0; files && i < L.files.size() && i < cap; i++) files[i].failed_frags = failed[i];
-    S.kernel_ms = a->kernel_ms[0] + a->kernel_ms[1] + a->kernel_ms[2];
-    S.seconds_total = now_s() - t0;
-    if (st) *st = S;
-    if (worst == CSCMI_DEVICE_ERROR) return CSCMI_DEVICE_ERROR;
-    if (worst < 0) {
-        fprintf(stderr, "Extraction error, archive corrupted\n");           // csarc.cpp:464-467
-        return -1;
-    }
-    return 0;
-}
-
-}   // namespace
-
-extern "C" {
-
-int CSAMI_DeviceRead(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
-                     const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st)
-{
-    return dev_read(a, names, nnames, dst, dst_cap, opt, files, cap, st, nullptr);
-}
-
-int CSAMI_DeviceReadStop(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
-                         const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st, CSADevStopStats *stop_stats)
-{
-    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;               // (before anything of the caller's is touched)
-    CSADevStopStats SS;
-    memset(&SS, 0, sizeof(SS));
-    if (stop_stats) *stop_stats = SS;
-    const int rc = dev_read(a, names, nnames, dst, dst_cap, opt, files, cap, st, &SS);
-    if (stop_stats) *stop_stats = SS;
-    return rc;
-}
-
-void CSAMI_DeviceKernelMs(const CSADevArchive *a, double ms[3])
-{
-    for (int i = 0; i < 3; i++) ms[i] = a ? a->kernel_ms[i] : 0;
-}
-
-void CSAMI_DeviceClose(CSADevArchive *a) { delete a; }
-
-}   // extern "C"
-
-namespace {
-
-// the strict host-only plan of CSAMI_PlanDeviceLayout / CSAMI_PlanDeviceStops: false for an index that does not parse, whose sizes
-// wrap, or with an archive block outside [0, arc_size).  L.files point into `index`.
-bool dev_plan_strict(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
-                     Index &index, DevLayout &L)
-{
-    BlockIndex abindex;
-    std::map<uint64_t, uint64_t> raw;
-    if (!raw_index || !unpack_index(index, abindex, raw_index, raw_size) || !dev_task_sizes(index, raw)) return false;
-    for (const auto &kv : abindex)
-        for (const Extent &x : kv.second) {
-            uint64_t end;
-            if (!add_ok(x.off, x.size, &end) || end > arc_size) return false;
-        }
-    return dev_layout(index, raw, make_selection(names, nnames), L);
-}
-
-}   // namespace
-
-extern "C" {
-
-int CSAMI_PlanDeviceLayout(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
-                           CSADevFile *files, uint32_t cap, uint32_t *n_files, uint64_t *dst_bytes,
-                           uint64_t *task_raw_sizes, uint32_t task_cap, uint32_t *n_tasks)
-{
-    Index index;
-    DevLayout L;
-    if (!dev_plan_strict(raw_index, raw_size, arc_size, names, nnames, index, L)) return -1;
-    dev_fill_files(L, files, cap);
-    // the names: inside raw_index, where the parse above found them (the first entry of a name wins, as in the map)
-    std::map<std::string, const char *> where;
-    uint64_t pos = 4;
-    for (uint32_t i = 0, n = (uint32_t)load_le(raw_index, 4); i < n; i++) {
-        const uint32_t ln = (uint32_t)load_le(raw_index + pos, 4);
-        const char *p = (const char *)raw_index + pos + 4;
-        where.insert(std::make_pair(std::string(p, ln), p));
-        const int nfr = (int8_t)raw_index[pos + 4 + ln + 24];
-        pos += 4 + (uint64_t)ln + 25 + 32ull * (uint64_t)nfr;
-    }
-    for (size_t i = 0; files && i < L.files.size() && i < cap; i++) files[i].name = where[L.files[i].it->first];
-    if (n_files) *n_files = (uint32_t)L.files.size();
-    if (dst_bytes) *dst_bytes = L.dst_bytes;
-    for (size_t i = 0; task_raw_sizes && i < L.tasks.size() && i < task_cap; i++) task_raw_sizes[i] = L.tasks[i].raw;
-    if (n_tasks) *n_tasks = (uint32_t)L.tasks.size();
-    return 0;
-}
-
-int CSAMI_PlanDeviceStops(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
-                          uint64_t *bids, uint64_t *stops, uint64_t *raws, uint32_t cap, uint32_t *n_tasks)
-{
-    Index index;
-    DevLayout L;
-    if (!dev_plan_strict(raw_index, raw_size, arc_size, names, nnames, index, L)) return -1;
-    for (const DevTask &t : L.tasks)
-        if (t.stop == 0 || t.stop > t.raw) return -1;                       // (a selected fragment past its task: cannot be, by construction)
-    for (size_t i = 0; i < L.tasks.size() && i < cap; i++) {
-        if (bids) bids[i] = L.tasks[i].bid;
-        if (stops) stops[i] = L.tasks[i].stop;
-        if (raws) raws[i] = L.tasks[i].raw;
-    }
-    if (n_tasks) *n_tasks = (uint32_t)L.tasks.size();
-    return 0;
-}
-
-}   // extern "C"
-
-// ---------------------------------------------------------------------------------------------
-// device-resident write: CSAMI_DeviceWritePlan / CSAMI_DeviceWrite (include/csa_mi355x.h).
-// Host side: the index from the caller's table, the plan CSA_Add makes (plan_index), the validation of every size, the piece
-// tables, arc_end, the index and the header.  The bytes move in csa_dev_kernels.hip (k_frag_pieces, k_frag_fold, k_block_table,
-// k_gather_extents; tables and walks: csa_dev_read.h, csa_dev_write.h) and in CSCMI_EncodeDeviceBatch.
-// ---------------------------------------------------------------------------------------------
-#include "csa_dev_write.h"
-
-void launch_block_table(const void *jobs, uint32_t njobs, void *scratch, void *res, void *sizes, hipStream_t st);
-
-namespace {
-
-thread_local double g_write_ms[4] = {0, 0, 0, 0};      // CSAMI_DeviceWriteKernelMs
-
-// The caller's table as an index, and its plan.  -1 for a table the host refuses; src_size is checked where check_src.
-int plan_write(AddPlan &P, const CSADevFile *files, uint32_t n_files, const CSAOptions *opt, bool check_src, uint64_t src_size,
-               uint64_t *raw_bytes)
-{
-    if (opt) P.o = *opt; else CSA_OptionsInit(&P.o);
-    if (n_files && !files) return -1;
-    uint64_t sum = 0;
-    for (uint32_t i = 0; i < n_files; i++) {
-        const CSADevFile &f = files[i];
-        if (!f.name || f.esize < 0) return -1;
-        const std::string name(f.name);
-        if (!name.empty() && name[name.size() - 1] == '/' && f.esize != 0) return -1;
-        uint64_t end;
-        if (check_src && (!add_ok(f.offset, (uint64_t)f.esize, &end) || end > src_size)) return -1;
-        if (!add_ok(sum, (uint64_t)f.esize, &sum) || sum > (1ull << 60)) return -1;   // (every later sum of sizes stays far from 2^64)
-        auto ins = P.index.insert(std::make_pair(name, Entry()));
-        if (!ins.second) return -1;
-        Entry &e = ins.first->second;
-        e.edate = f.edate; e.esize = f.esize; e.eattr = f.eattr; e.row = i;
-    }
-    const int rc = plan_index(P);
-    if (raw_bytes) { *raw_bytes = 0; for (const Task &t : P.tasks) *raw_bytes += t.total; }
-    return rc;
-}
-
-struct WriteCtx {
-    const uint8_t *src = nullptr;
-    uint8_t *arc = nullptr;
-    uint64_t arc_cap = 0, arc_end = kHeaderSize;
-    const CSADevFile *files = nullptr;
-    int64_t slack = -1;                        // CSA_DEVWRITE_SLACK, -1: not set
-    CSADevWriteStats S;
-    DevTimer tm;
-    BlockIndex abindex;
-};
-
-uint64_t stream_cap(const WriteCtx &W, uint64_t raw)
-{
-    return W.slack >= 0 ? raw / 4 + (uint64_t)W.slack : raw + raw / 8 + 65536;
-}
-
-bool dev_upload(WriteCtx &W, DevBuf &b, const void *p, uint64_t n)
-{
-    W.S.upload_bytes += n;
-    return b.upload(p, n);
-}
-
-// CSCMI_EncodeDeviceBatch over jobs whose dst is scratch of this layer; a job whose scratch was too small once more, alone, into a
-// larger one (kept in `more` until its stream is placed)
-int dev_encode(WriteCtx &W, std::vector<CSCMIDevEncode> &jobs, std::list<DevBuf> &more)
-{
-    const double t0 = now_s();
-    CSCMIDevEncodeStats es;
-    memset(&es, 0, sizeof(es));
-    int rc = CSCMI_EncodeDeviceBatch((int)jobs.size(), jobs.data(), &es) == 0 ? 0 : CSCMI_DEVICE_ERROR;
-    W.S.encode_launches += es.launches; W.S.readback_bytes += es.readback_bytes;
-    for (size_t i = 0; rc == 0 && i < jobs.size(); i++) {
-        CSCMIDevEncode &j = jobs[i];
-        if (j.rc == WRITE_ERROR) {
-            more.emplace_back();
-            const uint64_t cap = 2 * (uint64_t)j.src_size + (1u << 20);
-            if (!more.back().alloc(cap)) { rc = CSCMI_DEVICE_ERROR; break; }
-            j.dst = more.back().p; j.dst_cap = (size_t)cap; j.produced = 0; j.rc = 0;
-            W.S.retries++;
-            memset(&es, 0, sizeof(es));
-            if (CSCMI_EncodeDeviceBatch(1, &j, &es) != 0) rc = CSCMI_DEVICE_ERROR;
-            W.S.encode_launches += es.launches; W.S.readback_bytes += es.readback_bytes;
-        }
-        if (j.rc != 0) rc = CSCMI_DEVICE_ERROR;
-    }
-    W.S.seconds_encode += now_s() - t0;
-    return rc;
-}
-
-// The property bytes and the stream of every job to arc + arc_end, in order, with one launch; `hdr` (NULL, or the 24 header bytes)
-// goes to arc + 0 with it.  WRITE_ERROR, with nothing launched, if it would pass arc_cap.
-int dev_place(WriteCtx &W, const std::vector<CSCMIDevEncode> &jobs, const uint8_t *hdr)
-{
-    using namespace csadev;
-    const uint64_t lead = hdr ? kHeaderSize : 0;
-    uint64_t end = W.arc_end;
-    for (const CSCMIDevEncode &j : jobs)
-        if (!add_ok(end, CSC_PROP_SIZE + (uint64_t)j.produced, &end)) return WRITE_ERROR;
-    if (end > W.arc_cap) return WRITE_ERROR;
-    // the bytes that come from the host: [the header] and the property bytes of every job
-    std::vector<uint8_t> host(hdr, hdr + lead);
-    for (const CSCMIDevEncode &j : jobs) {
-        uint8_t props[CSC_PROP_SIZE];
-        CSCEnc_WriteProperties(&j.props, props, 0);                          // csa_worker.cpp:38-42
-        host.insert(host.end(), props, props + CSC_PROP_SIZE);
-    }
-    DevBuf d_host, d_gp;
-    if (!dev_upload(W, d_host, host.data(), host.size())) return CSCMI_DEVICE_ERROR;
-    std::vector<CopyPiece> gp;
-    if (hdr) gp.push_back(CopyPiece{(const uint8_t *)d_host.p, W.arc, (uint32_t)kHeaderSize, 0});
-    uint64_t pos = W.arc_end;
-    for (size_t k = 0; k < jobs.size(); k++) {
-        gp.push_back(CopyPiece{(const uint8_t *)d_host.p + lead + CSC_PROP_SIZE * k, W.arc + pos, CSC_PROP_SIZE, 0});
-        piece_split((const uint8_t *)jobs[k].dst, W.arc + pos + CSC_PROP_SIZE, jobs[k].produced, kGatherPiece,
-                    [&](uint64_t, const CopyPiece &p) { gp.push_back(p); });
-        pos += CSC_PROP_SIZE + jobs[k].produced;
-    }
-    if (gp.size() > 0x7FFFFFFFull || !dev_upload(W, d_gp, gp.data(), gp.size() * sizeof(CopyPiece))) return CSCMI_DEVICE_ERROR;
-    W.tm.begin();
-    launch_gather_extents(d_gp.p, (uint32_t)gp.size(), W.tm.st);
-    W.S.launches++;
-    if (!W.tm.end(&g_write_ms[3])) return CSCMI_DEVICE_ERROR;
-    W.arc_end = pos;
-    return 0;
-}
-
-// One wave: tasks [first, first + count) of the plan.  0, WRITE_ERROR or CSCMI_DEVICE_ERROR.
-int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
-{
-    using namespace csadev;
-    // 1. where each task's raw bytes lie: one range of one entry is encoded where it is, anything else is gathered
-    std::vector<const uint8_t *> in(count, nullptr);
-    std::vector<uint64_t> gat_off(count, 0);
-    std::vector<uint8_t> gathered(count, 0);
-    uint64_t gat_bytes = 0, npieces = 0;
-    for (size_t k = 0; k < count; k++) {
-        Task &t = P.tasks[first + k];
-        uint64_t cum = 0;
-        size_t nonempty = 0;
-        for (FilePiece &f : t.files) {
-            f.posblock = cum;                                                // csa_io.h:239
-            cum += f.size;
-            if (f.size) { nonempty++; in[k] = W.src + W.files[f.it->second.row].offset + f.off; }
-            npieces += piece_count(f.size, kFragPiece);
-        }
-        if (nonempty > 1) {
-            gathered[k] = 1;
-            gat_off[k] = gat_bytes;
-            gat_bytes += (t.total + 255) & ~255ull;
-        }
-    }
-    if (npieces > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
-    DevBuf d_gat;
-    if (gat_bytes && !d_gat.alloc(gat_bytes)) return CSCMI_DEVICE_ERROR;
-
-    // 2. gather and sum in one pass: the pieces that are stored first, then the ones that are only summed
-    std::vector<CopyPiece> pc[2];                                            // [1]: with the store
-    std::vector<FragFold> ff;
-    std::vector<uint8_t> ff_store;
-    std::vector<FilePiece *> ff_piece;
-    for (size_t k = 0; k < count; k++) {
-        for (FilePiece &f : P.tasks[first + k].files) {
-            f.checksum = 0;
-            if (!f.size) continue;                                           // adler32 of nothing, seed 0
-            std::vector<CopyPiece> &v = pc[gathered[k]];
-            ff.push_back(FragFold{f.size, (uint32_t)v.size(), (uint32_t)piece_count(f.size, kFragPiece), 0, 0});
-            ff_store.push_back(gathered[k]);
-            ff_piece.push_back(&f);
-            piece_split(W.src + W.files[f.it->second.row].offset + f.off,
-                        gathered[k] ? (uint8_t *)d_gat.p + gat_off[k] + f.posblock : nullptr, f.size, kFragPiece,
-                        [&](uint64_t, const CopyPiece &p) { v.push_back(p); });
-        }
-        if (gathered[k]) in[k] = (const uint8_t *)d_gat.p + gat_off[k];
-    }
-    const size_t nstore = pc[1].size();
-    for (size_t i = 0; i < ff.size(); i++) if (!ff_store[i]) ff[i].first += (uint32_t)nstore;
-    pc[1].insert(pc[1].end(), pc[0].begin(), pc[0].end());
-    const std::vector<CopyPiece> &fp = pc[1];
-    if (!ff.empty()) {
-        DevBuf d_fp, d_ff, d_sums, d_res;
-        if (!dev_upload(W, d_fp, fp.data(), fp.size() * sizeof(CopyPiece)) || !dev_upload(W, d_ff, ff.data(), ff.size() * sizeof(FragFold))
-            || !d_sums.alloc(fp.size() * sizeof(PieceSums)) || !d_res.alloc(ff.size() * sizeof(FragResult))) return CSCMI_DEVICE_ERROR;
-        if (nstore) {
-            W.tm.begin();
-            launch_frag_pieces(d_fp.p, d_sums.p, (uint32_t)nstore, true, W.tm.st);
-            W.S.launches++;
-            if (!W.tm.end(&g_write_ms[0])) return CSCMI_DEVICE_ERROR;
-        }
-        if (fp.size() > nstore) {
-            W.tm.begin();
-            launch_frag_pieces((const CopyPiece *)d_fp.p + nstore, (PieceSums *)d_sums.p + nstore, (uint32_t)(fp.size() - nstore), false, W.tm.st);
-            W.S.launches++;
-            if (!W.tm.end(&g_write_ms[0])) return CSCMI_DEVICE_ERROR;
-        }
-        W.tm.begin();
-        launch_frag_fold(d_ff.p, d_sums.p, d_res.p, (uint32_t)ff.size(), W.tm.st);
-        W.S.launches++;
-        if (!W.tm.end(&g_write_ms[1])) return CSCMI_DEVICE_ERROR;
-        std::vector<FragResult> res(ff.size());
-        if (!HIP_OK(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(FragResult), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-        W.S.readback_bytes += res.size() * sizeof(FragResult);
-        for (size_t i = 0; i < res.size(); i++) ff_piece[i]->checksum = res[i].adler;        // csa_io.h:250
-    }
-
-    // 3. encode: csa_worker.cpp:23-56 for every task of the wave at once, into scratch of this layer
-    std::vector<CSCMIDevEncode> jobs(count);
-    uint64_t scr_bytes = 0;
-    std::vector<uint64_t> scr_off(count);
-    for (size_t k = 0; k < count; k++) {
-        scr_off[k] = scr_bytes;
-        scr_bytes += (stream_cap(W, P.tasks[first + k].total) + 255) & ~255ull;
-    }
-    DevBuf d_scr;
-    std::list<DevBuf> more;
-    if (!d_scr.alloc(scr_bytes)) return CSCMI_DEVICE_ERROR;
-    for (size_t k = 0; k < count; k++) {
-        const Task &t = P.tasks[first + k];
-        CSCMIDevEncode &j = jobs[k];
-        memset(&j, 0, sizeof(j));
-        CSCEncProps_Init(&j.props, (uint32_t)std::min<uint64_t>(P.o.dict_size, t.total), P.o.level);   // csa_worker.cpp:35
-        j.src = t.total ? (const void *)in[k] : d_scr.p;                     // (no byte of it is loaded when the task is empty)
-        j.src_size = (size_t)t.total;
-        j.dst = (uint8_t *)d_scr.p + scr_off[k];
-        j.dst_cap = (size_t)stream_cap(W, t.total);
-    }
-    int rc = dev_encode(W, jobs, more);
-    if (rc) return rc;
-
-    // 4. block tables: BlockSink::put over the Write sizes the file path would have seen
-    std::vector<BlockTableJob> bj(count);
-    uint64_t slots = 0;
-    for (size_t k = 0; k < count; k++) {
-        const uint64_t mb = table_bound(jobs[k].produced, jobs[k].props.csc_blocksize);
-        if (mb > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
-        bj[k] = BlockTableJob{(const uint8_t *)jobs[k].dst, (uint64_t)jobs[k].produced, jobs[k].props.csc_blocksize, (uint32_t)mb, slots};
-        slots += mb;
-    }
-    std::vector<BlockTableRes> br(count);
-    std::vector<uint64_t> sizes;
-    {
-        DevBuf d_bj, d_slots, d_res, d_sizes;
-        if (!dev_upload(W, d_bj, bj.data(), bj.size() * sizeof(BlockTableJob)) || !d_slots.alloc(slots * 8) || !d_res.alloc(count * sizeof(BlockTableRes))
-            || !d_sizes.alloc(slots * 8)) return CSCMI_DEVICE_ERROR;
-        W.tm.begin();
-        launch_block_table(d_bj.p, (uint32_t)count, d_slots.p, d_res.p, d_sizes.p, W.tm.st);
-        W.S.launches++;
-        if (!W.tm.end(&g_write_ms[2])) return CSCMI_DEVICE_ERROR;
-        if (!HIP_OK(hipMemcpy(br.data(), d_res.p, count * sizeof(BlockTableRes), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-        W.S.readback_bytes += count * sizeof(BlockTableRes);
-        uint64_t nb = 0;
-        for (size_t k = 0; k < count; k++) {
-            if (br[k].status != kTableOk || br[k].nblocks > bj[k].max_blocks) {
-                fprintf(stderr, "csa-mi355x: task %zu: its stream does not end where its encoder said (block table status %u)\n", first + k, br[k].status);
-                return CSCMI_DEVICE_ERROR;
-            }
-            nb += br[k].nblocks;
-        }
-        sizes.resize(nb);
-        if (nb && !HIP_OK(hipMemcpy(sizes.data(), d_sizes.p, nb * 8, hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-        W.S.readback_bytes += nb * 8;
-        W.S.blocks += nb;
-    }
-
-    // 5. placement, and the tasks' extents (csa_io.h:559-573; id == task index, csarc.cpp:393-394)
-    uint64_t pos = W.arc_end;
-    size_t at = 0;
-    for (size_t k = 0; k < count; k++) {
-        std::vector<Extent> &ext = W.abindex[first + k];
-        const uint64_t begin = pos;
-        for (uint32_t i = 0; i < br[k].nblocks; i++, at++) { ext.push_back(Extent{pos, sizes[at]}); pos += sizes[at]; }
-        if (pos - begin != CSC_PROP_SIZE + (uint64_t)jobs[k].produced) return CSCMI_DEVICE_ERROR;
-    }
-    return dev_place(W, jobs, nullptr);
-}
-
-}   // namespace
-
-extern "C" {
-
-int CSAMI_DeviceWritePlan(const CSADevFile *files, uint32_t n_files, const char *arcname, const CSAOptions *opt,
-                          uint32_t *n_tasks, uint32_t *max_frags, uint64_t *raw_bytes)
-{
-    (void)arcname;
-    AddPlan P;
-    uint64_t raw = 0;
-    const int rc = plan_write(P, files, n_files, opt, false, 0, &raw);
-    if (rc == -1) return -1;
-    std::map<const void *, uint32_t> nfr;
-    uint32_t mx = 0;
-    for (const Task &t : P.tasks)
-        for (const FilePiece &f : t.files) mx = std::max(mx, ++nfr[(const void *)&*f.it]);
-    if (n_tasks) *n_tasks = (uint32_t)P.tasks.size();
-    if (max_frags) *max_frags = mx;
-    if (raw_bytes) *raw_bytes = raw;
-    return rc;
-}
-
-int CSAMI_DeviceWrite(const void *src_dev, uint64_t src_size, CSADevFile *files, uint32_t n_files, const char *arcname,
-                      void *arc_dev, uint64_t arc_cap, const CSAOptions *opt, CSADevWriteStats *st)
-{
-    const double t0 = now_s();
-    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
-    WriteCtx W;
-    memset(&W.S, 0, sizeof(W.S));
-    if (st) *st = W.S;
-    for (double &m : g_write_ms) m = 0;
-    // ---- everything the host can refuse, before any launch
-    const uintptr_t s0 = (uintptr_t)src_dev, a0 = (uintptr_t)arc_dev;
-    uint64_t s1, a1;
-    if (!arcname || (!src_dev && src_size) || (!arc_dev && arc_cap) || !add_ok(s0, src_size, &s1) || !add_ok(a0, arc_cap, &a1)) return -1;
-    if (src_size && arc_cap && s0 < a1 && a0 < s1) return -1;
-    AddPlan P;
-    int rc = plan_write(P, files, n_files, opt, true, src_size, &W.S.raw_bytes);
-    if (rc) return rc;
-    if (arc_cap < kHeaderSize) return WRITE_ERROR;
-    if (const char *e = getenv("CSA_DEVWRITE_SLACK")) { W.slack = (int64_t)strtoull(e, nullptr, 10); if (W.slack < 0) W.slack = -1; }
-    W.src = (const uint8_t *)src_dev; W.arc = (uint8_t *)arc_dev; W.arc_cap = arc_cap; W.files = files;
-    if (!W.tm.ok) return CSCMI_DEVICE_ERROR;
-
-    // ---- waves of consecutive task ids, largest first (csarc.cpp:355): the plan's order and the archive's
-    size_t mem_free = 0, mem_total = 0;
-    if (!HIP_OK(hipMemGetInfo(&mem_free, &mem_total))) return CSCMI_DEVICE_ERROR;
-    const uint64_t budget = P.o.hbm_budget ? P.o.hbm_budget : (uint64_t)mem_free / 4 * 3;
-    size_t width = P.o.device_streams > 0 ? (size_t)P.o.device_streams : csadev::kTableMaxJobs;
-    width = std::min<size_t>(width, csadev::kTableMaxJobs);
-    for (size_t first = 0; rc == 0 && first < P.tasks.size();) {
-        size_t count = 0;
-        uint64_t mem = 0;
-        while (first + count < P.tasks.size() && count < width) {
-            // what the task's encoder holds (as encode_tasks reckons), a gathered copy of its input (at most) and its scratch stream
-            const Task &t = P.tasks[first + count];
-            CSCProps p;
-            CSCEncProps_Init(&p, (uint32_t)std::min<uint64_t>(P.o.dict_size, t.total), P.o.level);
-            const uint64_t need = CSCEnc_EstMemUsage(&p) + (24ull << 20) + t.total + stream_cap(W, t.total);
-            if (count && mem + need > budget) break;
-            mem += need;
-            count++;
-        }
-        rc = dev_write_wave(W, P, first, count);
-        W.S.waves++;
-        for (size_t k = first; k < first + count; k++) { W.S.tasks++; W.S.frags += P.tasks[k].files.size(); }
-        first += count;
-    }
-
-    // ---- fragments, index stream, header: csarc.cpp:371-386, 219-288
-    if (rc == 0) {
-        for (size_t ti = 0; ti < P.tasks.size(); ti++)
-            for (const FilePiece &f : P.tasks[ti].files)
-                f.it->second.frags.push_back(CSAFrag{(uint32_t)ti, f.checksum, f.posblock, f.size, f.off});
-        const std::vector<uint8_t> raw = pack_index(P.index, W.abindex, arcname);
-        DevBuf d_raw, d_scr;
-        std::list<DevBuf> more;
-        std::vector<CSCMIDevEncode> job(1);
-        memset(&job[0], 0, sizeof(job[0]));
-        CSCEncProps_Init(&job[0].props, 256 * 1024, 2);                      // csarc.cpp:251
-        if (raw.size() > 0xFFFFFFFFull) rc = WRITE_ERROR;                    // (the header has 32 bits for it)
-        else if (!dev_upload(W, d_raw, raw.data(), raw.size()) || !d_scr.alloc(stream_cap(W, raw.size()))) rc = CSCMI_DEVICE_ERROR;
-        if (rc == 0) {
-            job[0].src = d_raw.p; job[0].src_size = raw.size();
-            job[0].dst = d_scr.p; job[0].dst_cap = (size_t)stream_cap(W, raw.size());
-            rc = dev_encode(W, job, more);
-        }
-        const uint64_t csize = CSC_PROP_SIZE + (uint64_t)job[0].produced;
-        if (rc == 0 && csize > 0xFFFFFFFFull) rc = WRITE_ERROR;
-        if (rc == 0) {
-            uint8_t hdr[kHeaderSize];                                        // csarc.cpp:268-287
-            hdr[0] = 'C'; hdr[1] = 'S'; hdr[2] = 'A'; hdr[7] = '1';
-            store_le(hdr + 3, kMagicNum, 4);
-            store_le(hdr + 8, W.arc_end, 8);
-            store_le(hdr + 16, csize, 4);
-            store_le(hdr + 20, raw.size(), 4);
-            rc = dev_place(W, job, hdr);
-        }
-        if (rc == 0) {
-            W.S.index_raw_size = raw.size();
-            W.S.index_compressed_size = csize;
-            W.S.archive_bytes = W.arc_end;
-            W.S.n_entries = (uint32_t)P.index.size();
-            for (const auto &kv : P.index) {
-                files[kv.second.row].size = (uint64_t)kv.second.esize;
-                files[kv.second.row].nfrags = (uint32_t)kv.second.frags.size();
-            }
-        }
-    }
-    W.S.kernel_ms = g_write_ms[0] + g_write_ms[1] + g_write_ms[2] + g_write_ms[3];
-    W.S.seconds_total = now_s() - t0;
-    if (st) *st = W.S;
-    return rc;
-}
-
-void CSAMI_DeviceWriteKernelMs(double ms[4])
-{
-    for (int i = 0; i < 4; i++) ms[i] = g_write_ms[i];
 }
 
 }   // extern "C"

@@ -1,7 +1,8 @@
-// csa_dev_kernels.hip -- the three kernels of the device-resident archive read (CSAMI_DeviceRead, csa_archive.cpp): per wave of
-// tasks one launch of each, whatever the number of tasks and fragments.  All three are bandwidth-bound: a byte is loaded once and
+// csa_dev_kernels.hip -- the three kernels of the device-resident archive read (CSAMI_DeviceRead, csa_dev_archive.cpp): per wave
+// of tasks one launch of each, whatever the number of tasks and fragments.  All three are bandwidth-bound: a byte is loaded once and
 // stored at most once, in 16-byte accesses wherever the two ends allow it (csa_dev_read.h: copy_sum).  The device-resident write
-// (CSAMI_DeviceWrite) runs the same three the other way round -- fragments gathered and summed, streams placed -- and one more:
+// (CSAMI_DeviceWrite) runs the same three the other way round -- fragments gathered and summed, streams placed -- and one more.
+// k_frag_pieces<false> is also the adler32 of CSA_Add's fragments and of CSAMI_Adler32Device (csa_archive.cpp):
 //
 //   k_gather_extents      one workgroup per <= 64 KiB piece of an archive block: the blocks of a task, which interleave with other
 //                         tasks' in an archive written by several workers (AsyncArchiveReader, csa_io.h:466-542), go back to back

@@ -8,8 +8,9 @@
 // here k_gather_extents copies them into one range; AsyncFileWriter (csa_io.h:274-408) cuts the decoded task into its fragments,
 // writes each at its file offset and folds adler32 (csa_adler32.cpp:63-129) over it -- here k_frag_pieces and k_frag_fold.
 //
-// adler32 piecewise, as csa_kernels.hip: a piece of `len` bytes gives A = sum(b_i) and B = sum((len - i) * b_i) as plain integers,
-// and consecutive pieces fold as b' = b + len * a + B, a' = a + A (mod 65521), seed 0.
+// adler32 piecewise: a piece of `len` bytes gives A = sum(b_i) and B = sum((len - i) * b_i) as plain integers, and consecutive
+// pieces fold as b' = b + len * a + B, a' = a + A (mod 65521), seed 0.  CSA_Add and CSAMI_Adler32Device (csa_archive.cpp) take
+// the same sums with k_frag_pieces<false> and fold them on the host: their pieces are cut per chunk and their seed runs on.
 //
 // The template parameter PLANT switches one deliberate mistake on (0: none).  The product instantiates 0 only; the model runs each
 // of the others and has to see it caught by a named case.

@@ -11,7 +11,7 @@
  *   CSArc::Extract  csarc.cpp:600-650            CSA_Extract
  *   CSArc::Test     csarc.cpp:667-700            CSA_Test
  *   CSArc::List     csarc.cpp:652-665            CSA_List
- *   adler32()       csa_adler32.cpp:63-129       CSA_Adler32 (host), CSAMI_Adler32Device (HIP kernel)
+ *   adler32()       csa_adler32.cpp:63-129       CSA_Adler32 (host), CSAMI_Adler32Device (HIP: k_frag_pieces)
  *   PackIndex / UnpackIndex csa_indexpack.cpp:166-211   inside CSA_Add / the readers; CSA_ReadIndex exposes the raw bytes
  *
  * What runs where: the task streams and the index stream are libcsc streams produced by the HIP

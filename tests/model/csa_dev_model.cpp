@@ -2,12 +2,14 @@
 // (tests/test_archive_device_host.py builds and runs it; a program of its own, nothing is preloaded).
 //
 //   csa_dev_model PLANT        PLANT = 0: the text the kernels run; 1..4: one of the header's planted mistakes switched on
+//   csa_dev_model waves        the wave planner of the archive layer's host side (csc_amd/csrc/csa_waves.h), Part 3
 //
 // Part 1, copy_sum: source alignment 0..15 x destination alignment 0..15 x the lengths below, with and without the store.  The
 // ranges are heap buffers that END exactly where the range ends, so a load or a store behind it is the sanitizer's to report; in
 // front of a range lie only the `alignment` bytes that put it there -- they are poisoned as far as ASan's 8-byte granules allow
 // (source) and checked for change (destination).  Compared against memcpy and a byte-at-a-time adler32.
 // Part 2, piece_split + copy_sum + fold_pieces: whole fragments at task offsets (posblock) of residues 0..15.
+// Part 3, wave_count: how many tasks a wave takes under a width and a budget, at the edges of both and of 64 bits.
 //
 // The first case that fails is named on a line "FAIL <case>"; when AddressSanitizer ends the run, the case it happened in is named
 // on a line "AT <case>".  UBSan's runtime makes no such call, so with a mistake planted every case is announced on a line
@@ -21,6 +23,7 @@
 #include <vector>
 
 #include "csa_dev_read.h"
+#include "csa_waves.h"
 
 using namespace csadev;
 
@@ -120,9 +123,62 @@ static int run_all()
     return 0;
 }
 
+// Part 3, wave_count (csa_waves.h): every expected count below is written out by hand.
+static int run_waves()
+{
+    using csa::wave_count;
+    const uint64_t M = UINT64_MAX;
+    uint64_t ncases = 0;
+    struct Case { const char *name; std::vector<uint64_t> need; size_t first, width; uint64_t budget; size_t want; };
+    const std::vector<Case> cases = {
+        {"width 1", {10, 10, 10}, 0, 1, 1000, 1},
+        {"first task over the whole budget: taken, alone", {5000, 1, 1}, 0, 8, 1000, 1},
+        {"exact fit", {400, 300, 300, 1}, 0, 8, 1000, 3},
+        {"one byte more than fits", {400, 300, 301, 1}, 0, 8, 1000, 2},
+        {"fewer tasks left than width", {10, 10, 10, 10, 10}, 3, 8, 1000, 2},
+        {"none left", {10, 10}, 2, 8, 1000, 0},
+        {"need UINT64_MAX, not first", {10, M, 10}, 0, 8, M, 1},
+        {"need UINT64_MAX, first", {10, M, 10}, 1, 8, M, 1},
+        {"a sum that would wrap", {M - 5, 6, 1}, 0, 8, M, 1},
+        {"a sum just short of wrapping, over the budget", {M - 5, 4, 1}, 0, 8, M - 2, 1},
+    };
+    for (const Case &c : cases) {
+        snprintf(g_case, sizeof(g_case), "waves %s", c.name);
+        const std::vector<uint64_t> &need = c.need;
+        if (wave_count(c.first, need.size(), c.width, c.budget, [&](size_t t) { return need.at(t); }) != c.want) return fail();
+        ncases++;
+    }
+    // a walk over eight tasks, budget 100, width 3:
+    //   60 + 40 = 100 fits, + 1 does not            -> [0, 2)
+    //   1 + 99 = 100 fits, + 100 does not           -> [2, 4)
+    //   100 alone, + 30 does not                    -> [4, 5)
+    //   30 + 30 + 30 = 90 fits, and width is reached -> [5, 8)
+    snprintf(g_case, sizeof(g_case), "waves walk");
+    const std::vector<uint64_t> need = {60, 40, 1, 99, 100, 30, 30, 30};
+    const std::vector<size_t> want = {0, 2, 4, 5, 8};
+    std::vector<size_t> got = {0};
+    for (size_t first = 0; first < need.size() && got.size() < 16;) {
+        first += wave_count(first, need.size(), 3, 100, [&](size_t t) { return need.at(t); });
+        got.push_back(first);
+    }
+    if (got != want) return fail();
+    ncases++;
+    // hbm_budget: the override, else 3/4 of what is free
+    snprintf(g_case, sizeof(g_case), "waves budget");
+    CSAOptions o;
+    memset(&o, 0, sizeof(o));
+    if (csa::hbm_budget(o, 4000) != 3000) return fail();
+    o.hbm_budget = 64u << 20;
+    if (csa::hbm_budget(o, 4000) != (64u << 20)) return fail();
+    ncases++;
+    printf("ok waves %llu\n", (unsigned long long)ncases);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
     __sanitizer_set_death_callback(on_death);
+    if (argc > 1 && !strcmp(argv[1], "waves")) return run_waves();
     const int plant = argc > 1 ? atoi(argv[1]) : 0;
     switch (plant) {
     case kPlantNone: return run_all<kPlantNone>();

@@ -224,6 +224,15 @@ def test_copy_sum_split_and_fold_under_the_sanitizers(model):
     assert out.stdout.strip() == f"ok {2 * 16 * 16 * 17 + 7 * 16 * 2}"
 
 
+def test_wave_planner_under_the_sanitizers(model):
+    """wave_count and hbm_budget (csc_amd/csrc/csa_waves.h), which size the waves of CSA_Test / CSA_Extract, CSAMI_DeviceRead and
+    CSAMI_DeviceWrite: width 1, a first task over the budget, the exact fit and one byte more, fewer tasks than the width, a need of
+    UINT64_MAX, sums that wrap, and a walk over eight tasks"""
+    out = model("waves")
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
+    assert out.stdout.strip() == "ok waves 12"
+
+
 @pytest.mark.parametrize("plant,where,how", [
     (1, "copy store=1 sa=0 da=0 n=1", "FAIL"),            # tail bytes dropped: the one byte of a 1-byte range is a tail byte
     (2, "copy store=1 sa=0 da=0 n=1", "FAIL"),            # weight len - i off by one: B of one byte is that byte

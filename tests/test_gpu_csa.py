@@ -212,6 +212,29 @@ def test_list_test_extract(csa, case, tmp_path, monkeypatch, orc_dec):
             assert d.is_dir() and stat.S_IMODE(d.stat().st_mode) == 0o755
 
 
+def test_test_and_extract_are_independent_of_wave_size(csa, tmp_path, monkeypatch):
+    """the host read path's waves (read_archive over wave_count): one task per wave and a tight HBM budget give what the default
+    call gives -- return code, task count, no verify failure, and the same bytes in every extracted file"""
+    content = csa_cases.make_tree(str(tmp_path), "many_files")
+    monkeypatch.chdir(tmp_path)
+    assert _add(csa, "many_files")[0] == 0
+
+    def read(tag, **opts):
+        rc_t, st_t = csa.test(csa_cases.ARCNAME, **opts)
+        out = tmp_path / tag
+        rc_x, st_x = csa.extract(csa_cases.ARCNAME, to_dir=str(out), **opts)
+        files = {os.path.relpath(os.path.join(d, f), out): open(os.path.join(d, f), "rb").read() for d, _, fs in os.walk(out) for f in fs}
+        return (rc_t, st_t["n_tasks"], st_t["verify_failures"], rc_x, st_x["n_tasks"], st_x["verify_failures"]), files
+
+    want, files = read("default")
+    assert want[0] == 0 and want[3] == 0 and want[1] == want[4] > 1 and want[2] == want[5] == 0
+    assert files == content
+    for tag, opts in (("one_stream", {"device_streams": 1}), ("tight_budget", {"hbm_budget": 64 << 20})):
+        got, got_files = read(tag, **opts)
+        assert got == want, tag
+        assert got_files == files, tag
+
+
 def test_selection_by_name_and_wildcard(csa, tmp_path, monkeypatch):
     content = csa_cases.make_tree(str(tmp_path), "mixed_tree")
     monkeypatch.chdir(tmp_path)

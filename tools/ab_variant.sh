@@ -8,5 +8,5 @@ root=$(cd "$(dirname "$0")/.." && pwd)
 cd "$root/csc_amd/csrc"
 mkdir -p build/ab
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wall -Wno-unused-function -DCSCMI_TU=1 "$@" -c csc_kernels.hip -o build/ab/${name}_k.o 2>/dev/null
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o build/ab/${name}.so build/ab/${name}_k.o build/csc_kernels_other.o build/csc_host.o build/csc_dec_kernels.o build/csc_dec_device.o build/csa_kernels.o build/csa_archive.o -lpthread
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -Wl,-Bsymbolic -o build/ab/${name}.so build/ab/${name}_k.o build/csc_kernels_other.o build/csc_host.o build/csc_enc_frame.o build/csc_dec_kernels.o build/csc_dec_device.o build/csa_dev_kernels.o build/csa_archive.o build/csa_dev_archive.o -lpthread
 echo "built $name ($*)"

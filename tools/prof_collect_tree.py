@@ -14,7 +14,7 @@ total = line["last_step_stats_rank0"]["raw_bytes"] * line["steps"]
 tot, launches, kernels = {}, {}, set()
 for f in glob.glob(os.path.join(src, "pmc_*", "**", "*counter_collection.csv"), recursive=True):
     for r in csv.DictReader(open(f)):
-        if "encode_runs" in r["Kernel_Name"] or "adler" in r["Kernel_Name"] or "analyze" in r["Kernel_Name"]:
+        if "encode_runs" in r["Kernel_Name"] or "frag_pieces" in r["Kernel_Name"] or "analyze" in r["Kernel_Name"]:
             tot[r["Counter_Name"]] = tot.get(r["Counter_Name"], 0.0) + float(r["Counter_Value"])
             launches[r["Counter_Name"]] = launches.get(r["Counter_Name"], 0) + 1
             kernels.add(r["Kernel_Name"].split("(")[0])
