@@ -69,6 +69,13 @@ class CSADevWriteStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CSADevDiff(C.Structure):
+    _fields_ = [("first_diff", C.c_uint64), ("status", C.c_uint32), ("failed_frags", C.c_uint32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 LIST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(CSAFrag))
 
 SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", "CSA_ReadIndex",
@@ -76,13 +83,17 @@ SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", 
            "CSAMI_AddShardEncode", "CSAMI_FreeBlob", "CSAMI_AddShardAssemble", "CSAMI_PlanInfo", "CSAMI_PlanShards", "CSA_IndexRoundTrip",
            "CSAMI_DeviceOpen", "CSAMI_DevicePlan", "CSAMI_DeviceRead", "CSAMI_DeviceClose", "CSAMI_PlanDeviceLayout", "CSAMI_DeviceKernelMs",
            "CSAMI_DeviceReadStop", "CSAMI_PlanDeviceStops",
-           "CSAMI_DeviceWritePlan", "CSAMI_DeviceWrite", "CSAMI_DeviceWriteKernelMs"]
+           "CSAMI_DeviceWritePlan", "CSAMI_DeviceWrite", "CSAMI_DeviceWriteKernelMs",
+           "CSAMI_CheckBuffers", "CSAMI_DeviceWriteFrom", "CSAMI_DeviceReadInto", "CSAMI_DeviceCompare"]
 
 CSA_MAX_FRAGMENTS = 127
 CSA_TOO_MANY_FRAGMENTS = -94
 CSA_UNSAFE_NAME = -93
 CSCMI_DEVICE_ERROR = -95
 WRITE_ERROR = -97
+CSAMI_DEV_STOP_EARLY = 1
+CSA_DIFF_BYTES, CSA_DIFF_SIZE, CSA_DIFF_SKIPPED, CSA_DIFF_SHORT = 1, 2, 4, 8
+NO_DIFF = (1 << 64) - 1                    # CSADevDiff.first_diff without CSA_DIFF_BYTES
 
 _lib = None
 
@@ -150,6 +161,17 @@ def lib():
         L.CSAMI_DeviceWrite.restype = C.c_int
         L.CSAMI_DeviceWriteKernelMs.argtypes = [C.POINTER(C.c_double)]
         L.CSAMI_DeviceWriteKernelMs.restype = None
+        ptrs = C.POINTER(C.c_void_p)
+        L.CSAMI_CheckBuffers.argtypes = [ptrs, u64s, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]
+        L.CSAMI_CheckBuffers.restype = C.c_int
+        L.CSAMI_DeviceWriteFrom.argtypes = [ptrs] + L.CSAMI_DeviceWrite.argtypes[2:]
+        L.CSAMI_DeviceWriteFrom.restype = C.c_int
+        L.CSAMI_DeviceReadInto.argtypes = [C.c_void_p, names, C.c_int, ptrs, u64s, C.c_uint32, C.c_uint32, C.POINTER(CSAOptions), files,
+                                           C.POINTER(CSADevReadStats), C.POINTER(CSADevStopStats)]
+        L.CSAMI_DeviceReadInto.restype = C.c_int
+        L.CSAMI_DeviceCompare.argtypes = [C.c_void_p, names, C.c_int, ptrs, u64s, C.c_uint32, C.c_uint32, C.POINTER(CSAOptions), files,
+                                          C.POINTER(CSADevDiff), C.POINTER(CSADevReadStats), C.POINTER(CSADevStopStats)]
+        L.CSAMI_DeviceCompare.restype = C.c_int
         _lib = L
     return _lib
 
@@ -359,6 +381,21 @@ def device_write_kernel_ms():
     return tuple(ms)
 
 
+def check_buffers(ptrs: Sequence[int], sizes: Sequence[int], excl=(0, 0), disjoint: bool = False):
+    """CSAMI_CheckBuffers (host only): the address checks write_tensors, extract_into and compare make before anything is launched.
+    ptrs, sizes: addresses and byte counts; excl: (address, size) of the range none may overlap -> (rc, lowest refused index or None)"""
+    n = len(ptrs)
+    pa, sa = (C.c_void_p * max(n, 1))(*ptrs), (C.c_uint64 * max(n, 1))(*sizes)
+    bad = C.c_uint32(0xFFFFFFFF)
+    rc = lib().CSAMI_CheckBuffers(pa, sa, n, C.c_void_p(excl[0]), excl[1], int(disjoint), C.byref(bad))
+    return rc, (int(bad.value) if rc != 0 else None)
+
+
+def _is_bytes_tensor(t) -> bool:
+    import torch
+    return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.dim() == 1
+
+
 class DeviceArchive:
     """A `.csa` that lies in device memory (CSAMI_DeviceOpen ... CSAMI_DeviceClose): `csarc x` / `csarc t` without the archive,
     the decoded tasks or the files crossing the bus.  torch is the plumbing: it owns the buffers and hands out views."""
@@ -470,8 +507,103 @@ class DeviceArchive:
         d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
         return rc, (arc[:st.archive_bytes] if rc == 0 else None), d
 
+    @staticmethod
+    def write_tensors(entries, arcname: str = "out.csa", arc=None, **opts):
+        """`csarc a -t1` of entries that lie in tensors of their own (CSAMI_DeviceWriteFrom) -> (rc, uint8 CUDA view of the archive,
+        stats dict), as write.  entries: dicts with name, tensor, edate, eattr; tensor: a 1-d contiguous torch.uint8 CUDA tensor of any
+        alignment, its numel the entry's size, or None for directories and empty files.  The tensors may alias each other, not arc."""
+        import torch
+        files = []
+        for e in entries:
+            t = e["tensor"]
+            if not (t is None or _is_bytes_tensor(t)):
+                raise TypeError("tensor: a contiguous 1-d torch.uint8 CUDA tensor, or None")
+            files.append({"name": e["name"], "esize": 0 if t is None else int(t.numel()), "edate": e["edate"], "eattr": e["eattr"]})
+        if not (arc is None or _is_bytes_tensor(arc)):
+            raise TypeError("arc: a contiguous 1-d torch.uint8 CUDA tensor")
+        live = [e["tensor"] for e in entries]                      # alive across the call
+        ptrs = (C.c_void_p * max(len(live), 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in live])
+        device = arc.device if arc is not None else next((t.device for t in live if t is not None), "cuda")
+        o = options(**opts)
+        caps = [None]
+        if arc is None:
+            rc, nt, _, raw = device_write_plan(files, arcname, **opts)
+            if rc != 0:
+                return rc, None, {"files": []}
+            cap = 24 + raw + raw // 8 + (64 << 10) * (nt + 1) + (1 << 20)
+            caps = [cap, 2 * cap]
+        for cap in caps:
+            if cap is not None:
+                arc = torch.empty(cap, dtype=torch.uint8, device=device)
+            arr, keep = _write_table(files)
+            st = CSADevWriteStats()
+            torch.cuda.synchronize()                   # the tensors were filled on torch's stream, the library launches on its own
+            rc = lib().CSAMI_DeviceWriteFrom(ptrs, arr, len(keep), arcname.encode(), C.c_void_p(arc.data_ptr()) if arc.numel() else None,
+                                             int(arc.numel()), C.byref(o), C.byref(st))
+            if rc != WRITE_ERROR:
+                break
+        del live
+        d = st.as_dict()
+        d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
+        return rc, (arc[:st.archive_bytes] if rc == 0 else None), d
+
+    def _by_name(self, bufs, names):
+        """the selection's files table and, per entry of it, the caller's tensor (None: verified only).  KeyError for a key that is
+        no selected entry."""
+        files = self.plan(names)[0]
+        bufs = dict(bufs)
+        unknown = set(bufs) - {f["name"] for f in files}
+        if unknown:
+            raise KeyError(sorted(unknown)[0])
+        live = [bufs.get(f["name"]) for f in files]
+        if not all(t is None or _is_bytes_tensor(t) for t in live):
+            raise TypeError("a contiguous 1-d torch.uint8 CUDA tensor, or None")
+        # (an empty tensor may have no address: it stands for itself with the archive's, which a range of size 0 never overlaps)
+        ptrs = (C.c_void_p * max(len(live), 1))(*[None if t is None else (t.data_ptr() or self._arc.data_ptr()) for t in live])
+        sizes = (C.c_uint64 * max(len(live), 1))(*[0 if t is None else int(t.numel()) for t in live])
+        return files, live, ptrs, sizes
+
+    def extract_into(self, dsts, names: Sequence[str] = (), stop_early=False, **opts):
+        """`csarc x` into tensors of the caller's (CSAMI_DeviceReadInto) -> (rc, stats dict); stats["files"] as in extract.
+        dsts: {stored name: 1-d contiguous torch.uint8 CUDA tensor of at least the entry's size, or None}; a selected entry that is
+        absent or None is verified only.  The tensors must not overlap each other or the archive."""
+        import torch
+        files, live, ptrs, caps = self._by_name(dsts, names)
+        arr, n = _names(names)
+        table, st, ss, o = (CSADevFile * max(len(files), 1))(), CSADevReadStats(), CSADevStopStats(), options(**opts)
+        torch.cuda.synchronize()
+        rc = lib().CSAMI_DeviceReadInto(self._h, arr, n, ptrs, caps, len(files), CSAMI_DEV_STOP_EARLY if stop_early else 0, C.byref(o),
+                                        table, C.byref(st), C.byref(ss))
+        del live
+        out = st.as_dict()
+        if stop_early:
+            out.update(ss.as_dict())
+        out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(table, files)]
+        return rc, out
+
+    def compare(self, srcs, names: Sequence[str] = (), stop_early=False, **opts):
+        """`csarc t` and a byte-for-byte comparison with tensors of the caller's in one pass (CSAMI_DeviceCompare) ->
+        (rc, {name: {"status", "first_diff", "failed_frags"}}, stats dict).  srcs: as dsts of extract_into; the tensors are only read
+        and may alias each other.  status: 0 or a sum of CSA_DIFF_*; first_diff: NO_DIFF without CSA_DIFF_BYTES.  rc is the
+        archive's health, as test returns it."""
+        import torch
+        files, live, ptrs, sizes = self._by_name(srcs, names)
+        arr, n = _names(names)
+        table, st, ss, o = (CSADevFile * max(len(files), 1))(), CSADevReadStats(), CSADevStopStats(), options(**opts)
+        diffs = (CSADevDiff * max(len(files), 1))()
+        torch.cuda.synchronize()
+        rc = lib().CSAMI_DeviceCompare(self._h, arr, n, ptrs, sizes, len(files), CSAMI_DEV_STOP_EARLY if stop_early else 0, C.byref(o),
+                                       table, diffs, C.byref(st), C.byref(ss))
+        del live
+        out = st.as_dict()
+        if stop_early:
+            out.update(ss.as_dict())
+        out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(table, files)]
+        return rc, {f["name"]: d.as_dict() for f, d in zip(files, diffs)}, out
+
     def kernel_ms(self):
-        """HIP-event milliseconds of the last extract / test by kernel: (k_gather_extents, k_frag_pieces, k_frag_fold)"""
+        """HIP-event milliseconds of the last extract / test by kernel: (k_gather_extents, k_frag_pieces, k_frag_fold); after compare:
+        (k_gather_extents, k_frag_compare, k_frag_fold_diff)"""
         ms = (C.c_double * 3)()
         lib().CSAMI_DeviceKernelMs(self._h, ms)
         return tuple(ms)

@@ -23,7 +23,9 @@ using namespace csa;
 // device-resident read: CSAMI_DeviceOpen / Plan / Read / Close, CSAMI_PlanDeviceLayout (include/csa_mi355x.h).
 // Host side: the index, the layout of dst, the validation of everything the index says, the piece tables.  The bytes move in
 // csa_dev_kernels.hip (tables and copy: csa_dev_read.h) and in CSCMI_DecodeDeviceBatch; CSAMI_DeviceReadStop is the same body with
-// every task stopped behind its last selected byte (CSCMI_DecodeDeviceBatchStop).
+// every task stopped behind its last selected byte (CSCMI_DecodeDeviceBatchStop).  All of them are one path over a device pointer
+// per entry (ReadBufs, dev_read_run): CSAMI_DeviceReadInto hands the caller's pointers in, CSAMI_DeviceRead / ReadStop the layout's
+// offsets into dst, and CSAMI_DeviceCompare the caller's pointers to be compared with instead of stored to.
 // ---------------------------------------------------------------------------------------------
 struct CSADevArchive {
     const uint8_t *arc = nullptr;
@@ -162,22 +164,29 @@ struct DevTimer {                              // HIP-event time of this layer's
 struct FragTables {
     std::vector<csadev::CopyPiece> pieces;
     std::vector<csadev::FragFold> frags;
-    DevBuf d_pieces, d_frags, d_sums, d_res;
-    // a fragment of `size` > 0 bytes at src, copied to dst unless that is NULL; false: more pieces than a launch takes
-    bool add(const uint8_t *src, uint8_t *dst, uint64_t size, uint32_t checksum)
+    DevBuf d_pieces, d_frags, d_sums, d_res, d_firsts;
+    // a fragment of `size` > 0 bytes at src, copied to dst unless that is NULL; false: more pieces than a launch takes.
+    // With `cmp` (k_frag_compare) dst is the caller's range instead, and the fragment's first cmp <= size bytes are compared with it.
+    bool add(const uint8_t *src, uint8_t *dst, uint64_t size, uint32_t checksum, uint64_t cmp = 0)
     {
         using namespace csadev;
         const uint64_t np = piece_count(size, kFragPiece);
         if (pieces.size() + np > 0x7FFFFFFFull) return false;
         frags.push_back(FragFold{size, (uint32_t)pieces.size(), (uint32_t)np, checksum, 0});
-        piece_split(src, dst, size, kFragPiece, [&](uint64_t, const CopyPiece &p) { pieces.push_back(p); });
+        piece_split(src, dst, size, kFragPiece, [&](uint64_t k, CopyPiece p) {
+            const uint64_t off = k * kFragPiece;
+            p.cmp = (uint32_t)(cmp > off ? std::min<uint64_t>(cmp - off, p.len) : 0);
+            pieces.push_back(p);
+        });
         return true;
     }
     uint64_t upload_bytes() const { return pieces.size() * sizeof(csadev::CopyPiece) + frags.size() * sizeof(csadev::FragFold); }
-    bool upload()
+    bool upload(bool compare = false)
     {
         return d_pieces.upload(pieces.data(), pieces.size() * sizeof(csadev::CopyPiece)) && d_frags.upload(frags.data(), frags.size() * sizeof(csadev::FragFold))
-               && d_sums.alloc(pieces.size() * sizeof(csadev::PieceSums)) && d_res.alloc(frags.size() * sizeof(csadev::FragResult));
+               && d_sums.alloc(pieces.size() * sizeof(csadev::PieceSums))
+               && d_res.alloc(frags.size() * (compare ? sizeof(csadev::FragDiff) : sizeof(csadev::FragResult)))
+               && (!compare || d_firsts.alloc(pieces.size() * sizeof(uint32_t)));
     }
     // k_frag_fold over the sums k_frag_pieces left, and the fragments' results read back: res.size() * sizeof(FragResult) bytes
     bool fold(DevTimer &tm, double *ms, uint64_t &launches, std::vector<csadev::FragResult> &res)
@@ -186,13 +195,28 @@ struct FragTables {
         res.resize(frags.size());
         return res.empty() || HIP_OK(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(csadev::FragResult), hipMemcpyDeviceToHost));
     }
+    // k_frag_fold_diff over what k_frag_compare left: res.size() * sizeof(FragDiff) bytes read back
+    bool fold_diff(DevTimer &tm, double *ms, uint64_t &launches, std::vector<csadev::FragDiff> &res)
+    {
+        if (!tm.timed(ms, launches, [&] { launch_frag_fold_diff(d_frags.p, d_sums.p, d_firsts.p, d_res.p, (uint32_t)frags.size(), tm.st); })) return false;
+        res.resize(frags.size());
+        return res.empty() || HIP_OK(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(csadev::FragDiff), hipMemcpyDeviceToHost));
+    }
+};
+
+// The caller's side of a read: entry i of the layout (L.files) is delivered to -- or, with `diffs`, compared with -- ptrs[i].
+struct ReadBufs {
+    uint8_t *const *ptrs = nullptr;            // per entry; NULL (the table, or an entry of it): verified only
+    const uint64_t *lim = nullptr;             // compare: per entry, the bytes that are compared -- min(the entry's size, the caller's)
+    CSADevDiff *diffs = nullptr;               // compare: per entry; first_diff, CSA_DIFF_BYTES and CSA_DIFF_SHORT are added here
+    uint8_t *at(uint32_t file) const { return ptrs ? ptrs[file] : nullptr; }
 };
 
 // One wave: tasks [first, first + count) of L.  Returns 0, -1 (a stream failed) or CSCMI_DEVICE_ERROR.
 // SS != nullptr (CSAMI_DeviceReadStop): a task is decoded only up to its `stop` -- capacity, scratch and stop position are that --
 // and SS is added to.  The coded stream of a task of several archive blocks is still gathered whole: how many coded bytes a
 // prefix of the raw bytes needs is not known before it is decoded.
-int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t count, uint8_t *dst, std::vector<uint32_t> &failed,
+int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t count, const ReadBufs &B, std::vector<uint32_t> &failed,
                   CSADevReadStats &S, DevTimer &tm, CSADevStopStats *SS)
 {
     using namespace csadev;
@@ -285,25 +309,50 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
         }
     }
 
-    // 4. scatter and verify: the fragments at least one byte of which was delivered, clipped to what was delivered
+    // 4. scatter (or compare) and verify: the fragments at least one byte of which was delivered, clipped to what was delivered
     FragTables T;
     std::vector<uint32_t> ff_file;
+    std::vector<uint64_t> ff_posfile;
+    bool store = false;
     for (size_t k = 0; k < count; k++) {
         const DevTask &t = L.tasks[first + k];
         for (const DevFrag &f : t.frags) {
-            if (f.posblock >= produced[k]) continue;
-            const uint64_t n = std::min<uint64_t>(f.size, produced[k] - f.posblock);
-            if (!T.add((const uint8_t *)d_raw.p + raw_off[k] + f.posblock, dst ? dst + L.files[f.file].offset + f.posfile : nullptr, n, f.checksum))
-                return CSCMI_DEVICE_ERROR;
+            const uint64_t n = f.posblock < produced[k] ? std::min<uint64_t>(f.size, produced[k] - f.posblock) : 0;
+            uint8_t *p = B.at(f.file);
+            uint64_t cmp = 0;
+            if (B.diffs && p && B.lim[f.file] > f.posfile) {
+                const uint64_t want = std::min<uint64_t>(f.size, B.lim[f.file] - f.posfile);
+                cmp = std::min(n, want);
+                if (n < want) B.diffs[f.file].status |= CSA_DIFF_SHORT;
+            }
+            if (!n) continue;
+            if (!T.add((const uint8_t *)d_raw.p + raw_off[k] + f.posblock, p ? p + f.posfile : nullptr, n, f.checksum, cmp)) return CSCMI_DEVICE_ERROR;
             ff_file.push_back(f.file);
+            ff_posfile.push_back(f.posfile);
+            store = store || p;
         }
     }
     // (both launches even when no fragment was delivered: a wave is always the same three)
     std::vector<FragResult> res;
-    if (!T.upload()
-        || !tm.timed(&A.kernel_ms[1], S.launches, [&] { launch_frag_pieces(T.d_pieces.p, T.d_sums.p, (uint32_t)T.pieces.size(), dst != nullptr, tm.st); })
-        || !T.fold(tm, &A.kernel_ms[2], S.launches, res)) return CSCMI_DEVICE_ERROR;
-    S.readback_bytes += res.size() * sizeof(FragResult);
+    if (B.diffs) {
+        std::vector<FragDiff> rd;
+        if (!T.upload(true)
+            || !tm.timed(&A.kernel_ms[1], S.launches, [&] { launch_frag_compare(T.d_pieces.p, T.d_sums.p, T.d_firsts.p, (uint32_t)T.pieces.size(), tm.st); })
+            || !T.fold_diff(tm, &A.kernel_ms[2], S.launches, rd)) return CSCMI_DEVICE_ERROR;
+        S.readback_bytes += rd.size() * sizeof(FragDiff);
+        for (size_t i = 0; i < rd.size(); i++) {
+            res.push_back(FragResult{rd[i].adler, rd[i].ok});
+            if (rd[i].first >= T.frags[i].size) continue;
+            CSADevDiff &d = B.diffs[ff_file[i]];
+            d.status |= CSA_DIFF_BYTES;
+            d.first_diff = std::min(d.first_diff, ff_posfile[i] + rd[i].first);
+        }
+    } else {
+        if (!T.upload()
+            || !tm.timed(&A.kernel_ms[1], S.launches, [&] { launch_frag_pieces(T.d_pieces.p, T.d_sums.p, (uint32_t)T.pieces.size(), store, tm.st); })
+            || !T.fold(tm, &A.kernel_ms[2], S.launches, res)) return CSCMI_DEVICE_ERROR;
+        S.readback_bytes += res.size() * sizeof(FragResult);
+    }
     for (size_t i = 0; i < res.size(); i++)
         if (!res[i].ok) {
             fprintf(stderr, "******** %s extraction/verify failed\n", L.files[ff_file[i]].it->first.c_str());   // csa_io.h:332,398
@@ -373,18 +422,21 @@ int CSAMI_DevicePlan(CSADevArchive *a, const char *const *names, int nnames,
 
 namespace {
 
-// CSAMI_DeviceRead (ss == nullptr) and CSAMI_DeviceReadStop (ss: its stop statistics, never null there)
-int dev_read(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
-             const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st, CSADevStopStats *ss)
+// The one read path below CSAMI_DeviceReadInto, CSAMI_DeviceCompare, CSAMI_DeviceRead and CSAMI_DeviceReadStop: the address checks,
+// then the waves.  sizes[i] are the bytes of B.ptrs[i] that may be touched (ignored where that is NULL); `disjoint`: they are
+// written, so no two may overlap.  ss: stop every task behind its last selected byte, and add to *ss.  `failed` gets one count per
+// entry.  -1 with nothing launched where CSAMI_CheckBuffers refuses the buffers.
+int dev_read_run(CSADevArchive *a, const DevLayout &L, const ReadBufs &B, const uint64_t *sizes, bool disjoint, const CSAOptions *opt,
+                 std::vector<uint32_t> &failed, CSADevReadStats &S, CSADevStopStats *ss)
 {
     const double t0 = now_s();
-    CSADevReadStats S;
-    memset(&S, 0, sizeof(S));
-    if (st) *st = S;
-    DevLayout L;
-    if (!a || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L)) return -1;
-    dev_fill_files(L, files, cap);
-    if (dst && dst_cap < L.dst_bytes) return WRITE_ERROR;
+    failed.assign(L.files.size(), 0);
+    if (B.ptrs) {
+        std::vector<uint64_t> touched(L.files.size());
+        for (size_t i = 0; i < L.files.size(); i++) touched[i] = B.ptrs[i] ? sizes[i] : 0;
+        if (CSAMI_CheckBuffers((const void *const *)B.ptrs, touched.data(), (uint32_t)L.files.size(), a->arc, a->arc_size, disjoint, nullptr) != 0)
+            return -1;
+    }
     CSAOptions o;
     if (opt) o = *opt; else CSA_OptionsInit(&o);
     a->kernel_ms[0] = a->kernel_ms[1] = a->kernel_ms[2] = 0;
@@ -395,7 +447,6 @@ int dev_read(CSADevArchive *a, const char *const *names, int nnames, void *dst, 
     const size_t width = o.device_streams > 0 ? (size_t)o.device_streams : L.tasks.size();
     DevTimer tm;
     if (!tm.ok) return CSCMI_DEVICE_ERROR;
-    std::vector<uint32_t> failed(L.files.size(), 0);
     int worst = 0;
     S.readback_bytes = a->open_readback;
     for (size_t first = 0; first < L.tasks.size() && worst != CSCMI_DEVICE_ERROR;) {
@@ -408,16 +459,14 @@ int dev_read(CSADevArchive *a, const char *const *names, int nnames, void *dst, 
             if (!add_ok(need, out, &need) || !add_ok(need, raw, &need)) need = UINT64_MAX;
             return need;
         });
-        int r = dev_read_wave(*a, L, first, count, (uint8_t *)dst, failed, S, tm, ss);
+        int r = dev_read_wave(*a, L, first, count, B, failed, S, tm, ss);
         if (r < 0 && worst != CSCMI_DEVICE_ERROR) worst = r;
         S.waves++;
         for (size_t k = first; k < first + count; k++) { S.tasks++; S.frags += L.tasks[k].frags.size(); S.raw_bytes += L.tasks[k].total; }
         first += count;
     }
-    for (size_t i = 0; files && i < L.files.size() && i < cap; i++) files[i].failed_frags = failed[i];
     S.kernel_ms = a->kernel_ms[0] + a->kernel_ms[1] + a->kernel_ms[2];
     S.seconds_total = now_s() - t0;
-    if (st) *st = S;
     if (worst == CSCMI_DEVICE_ERROR) return CSCMI_DEVICE_ERROR;
     if (worst < 0) {
         fprintf(stderr, "Extraction error, archive corrupted\n");           // csarc.cpp:464-467
@@ -426,9 +475,74 @@ int dev_read(CSADevArchive *a, const char *const *names, int nnames, void *dst, 
     return 0;
 }
 
+// CSAMI_DeviceRead (ss == nullptr) and CSAMI_DeviceReadStop (ss: its stop statistics, never null there): the layout's offsets into
+// dst as the entries' pointers
+int dev_read(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
+             const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st, CSADevStopStats *ss)
+{
+    CSADevReadStats S;
+    memset(&S, 0, sizeof(S));
+    if (st) *st = S;
+    DevLayout L;
+    if (!a || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L)) return -1;
+    dev_fill_files(L, files, cap);
+    if (dst && dst_cap < L.dst_bytes) return WRITE_ERROR;
+    std::vector<uint8_t *> ptrs(L.files.size());
+    std::vector<uint64_t> sizes(L.files.size());
+    for (size_t i = 0; i < L.files.size(); i++) { ptrs[i] = dst ? (uint8_t *)dst + L.files[i].offset : nullptr; sizes[i] = L.files[i].size; }
+    ReadBufs B;
+    if (dst) B.ptrs = ptrs.data();
+    std::vector<uint32_t> failed;
+    const int rc = dev_read_run(a, L, B, sizes.data(), true, opt, failed, S, ss);
+    for (size_t i = 0; files && i < failed.size() && i < cap; i++) files[i].failed_frags = failed[i];
+    if (st) *st = S;
+    return rc;
+}
+
+// What CSAMI_DeviceReadInto and CSAMI_DeviceCompare share in front of dev_read_run: the refusal without a device, the zeroed
+// statistics, the layout, n, the files table with offset 0.  0 to go on.
+int dev_into_begin(CSADevArchive *a, const char *const *names, int nnames, uint32_t n, CSADevFile *files, CSADevReadStats *st,
+                   CSADevStopStats *stop_stats, DevLayout &L)
+{
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;               // (before anything of the caller's is touched)
+    if (st) memset(st, 0, sizeof(*st));
+    if (stop_stats) memset(stop_stats, 0, sizeof(*stop_stats));
+    if (!a || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L) || L.files.size() != n) return -1;
+    dev_fill_files(L, files, n);
+    for (uint32_t i = 0; files && i < n; i++) files[i].offset = 0;
+    return 0;
+}
+
 }   // namespace
 
 extern "C" {
+
+int CSAMI_CheckBuffers(const void *const *ptrs, const uint64_t *sizes, uint32_t n, const void *excl, uint64_t excl_size, int disjoint,
+                       uint32_t *bad)
+{
+    uint32_t worst = UINT32_MAX;
+    const uint64_t e0 = (uint64_t)(uintptr_t)excl;
+    struct R { uint64_t lo, hi; uint32_t i; };                             // [lo, hi]: hi is the last byte, so a range may end at 2^64
+    std::vector<R> rs;
+    for (uint32_t i = 0; n && ptrs && sizes && i < n; i++) {
+        if (!sizes[i]) continue;
+        const uint64_t lo = (uint64_t)(uintptr_t)ptrs[i], hi = lo + (sizes[i] - 1);
+        const bool hits = excl_size && lo <= e0 + (excl_size - 1) && e0 <= hi;    // (an excl that itself wraps is the caller's to refuse)
+        if (!lo || hi < lo || hits) { worst = std::min(worst, i); continue; }
+        if (disjoint) rs.push_back(R{lo, hi, i});
+    }
+    if (n && (!ptrs || !sizes)) worst = 0;
+    // ranges in address order: one that begins at or before the furthest end so far overlaps the range that reaches it.  Every
+    // range that overlaps another is found as one of the two: the range next behind it begins inside it, or inside a longer one.
+    std::sort(rs.begin(), rs.end(), [](const R &a, const R &b) { return a.lo != b.lo ? a.lo < b.lo : a.i < b.i; });
+    for (size_t k = 1, far = 0; k < rs.size(); k++) {
+        if (rs[k].lo <= rs[far].hi) worst = std::min(worst, std::min(rs[k].i, rs[far].i));
+        if (rs[k].hi > rs[far].hi) far = k;
+    }
+    if (worst == UINT32_MAX) return 0;
+    if (bad) *bad = worst;
+    return -1;
+}
 
 int CSAMI_DeviceRead(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
                      const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st)
@@ -444,6 +558,64 @@ int CSAMI_DeviceReadStop(CSADevArchive *a, const char *const *names, int nnames,
     memset(&SS, 0, sizeof(SS));
     if (stop_stats) *stop_stats = SS;
     const int rc = dev_read(a, names, nnames, dst, dst_cap, opt, files, cap, st, &SS);
+    if (stop_stats) *stop_stats = SS;
+    return rc;
+}
+
+int CSAMI_DeviceReadInto(CSADevArchive *a, const char *const *names, int nnames, void *const *ptrs, const uint64_t *caps, uint32_t n,
+                         uint32_t flags, const CSAOptions *opt, CSADevFile *files, CSADevReadStats *st, CSADevStopStats *stop_stats)
+{
+    DevLayout L;
+    int rc = dev_into_begin(a, names, nnames, n, files, st, stop_stats, L);
+    if (rc) return rc;
+    std::vector<uint64_t> sizes(n);
+    for (uint32_t i = 0; i < n; i++) {
+        sizes[i] = L.files[i].size;
+        if (ptrs && ptrs[i] && (!caps || caps[i] < sizes[i])) return WRITE_ERROR;
+    }
+    ReadBufs B;
+    B.ptrs = (uint8_t *const *)ptrs;
+    CSADevReadStats S;
+    CSADevStopStats SS;
+    memset(&S, 0, sizeof(S));
+    memset(&SS, 0, sizeof(SS));
+    std::vector<uint32_t> failed;
+    rc = dev_read_run(a, L, B, sizes.data(), true, opt, failed, S, (flags & CSAMI_DEV_STOP_EARLY) ? &SS : nullptr);
+    for (uint32_t i = 0; files && i < n; i++) files[i].failed_frags = failed[i];
+    if (st) *st = S;
+    if (stop_stats) *stop_stats = SS;
+    return rc;
+}
+
+int CSAMI_DeviceCompare(CSADevArchive *a, const char *const *names, int nnames, const void *const *ptrs, const uint64_t *sizes, uint32_t n,
+                        uint32_t flags, const CSAOptions *opt, CSADevFile *files, CSADevDiff *diffs, CSADevReadStats *st,
+                        CSADevStopStats *stop_stats)
+{
+    DevLayout L;
+    int rc = dev_into_begin(a, names, nnames, n, files, st, stop_stats, L);
+    if (rc) return rc;
+    if (n && (!diffs || (ptrs && !sizes))) return -1;
+    std::vector<uint64_t> lim(n), given(n);
+    for (uint32_t i = 0; i < n; i++) {
+        const bool have = ptrs && ptrs[i];
+        given[i] = have ? sizes[i] : 0;
+        lim[i] = std::min<uint64_t>(L.files[i].size, given[i]);
+        diffs[i].first_diff = UINT64_MAX;
+        diffs[i].status = !have ? CSA_DIFF_SKIPPED : given[i] != L.files[i].size ? CSA_DIFF_SIZE : 0u;
+        diffs[i].failed_frags = 0;
+    }
+    ReadBufs B;
+    B.ptrs = (uint8_t *const *)ptrs;                                       // (k_frag_compare only loads from them)
+    B.lim = lim.data();
+    B.diffs = diffs;
+    CSADevReadStats S;
+    CSADevStopStats SS;
+    memset(&S, 0, sizeof(S));
+    memset(&SS, 0, sizeof(SS));
+    std::vector<uint32_t> failed;
+    rc = dev_read_run(a, L, B, given.data(), false, opt, failed, S, (flags & CSAMI_DEV_STOP_EARLY) ? &SS : nullptr);
+    for (uint32_t i = 0; i < n; i++) { diffs[i].failed_frags = failed[i]; if (files) files[i].failed_frags = failed[i]; }
+    if (st) *st = S;
     if (stop_stats) *stop_stats = SS;
     return rc;
 }
@@ -534,9 +706,8 @@ namespace {
 
 thread_local double g_write_ms[4] = {0, 0, 0, 0};      // CSAMI_DeviceWriteKernelMs
 
-// The caller's table as an index, and its plan.  -1 for a table the host refuses; src_size is checked where check_src.
-int plan_write(AddPlan &P, const CSADevFile *files, uint32_t n_files, const CSAOptions *opt, bool check_src, uint64_t src_size,
-               uint64_t *raw_bytes)
+// The caller's table as an index, and its plan.  -1 for a table the host refuses; where the entries' bytes lie is not looked at.
+int plan_write(AddPlan &P, const CSADevFile *files, uint32_t n_files, const CSAOptions *opt, uint64_t *raw_bytes)
 {
     if (opt) P.o = *opt; else CSA_OptionsInit(&P.o);
     if (n_files && !files) return -1;
@@ -546,8 +717,6 @@ int plan_write(AddPlan &P, const CSADevFile *files, uint32_t n_files, const CSAO
         if (!f.name || f.esize < 0) return -1;
         const std::string name(f.name);
         if (!name.empty() && name[name.size() - 1] == '/' && f.esize != 0) return -1;
-        uint64_t end;
-        if (check_src && (!add_ok(f.offset, (uint64_t)f.esize, &end) || end > src_size)) return -1;
         if (!add_ok(sum, (uint64_t)f.esize, &sum) || sum > (1ull << 60)) return -1;   // (every later sum of sizes stays far from 2^64)
         auto ins = P.index.insert(std::make_pair(name, Entry()));
         if (!ins.second) return -1;
@@ -560,10 +729,10 @@ int plan_write(AddPlan &P, const CSADevFile *files, uint32_t n_files, const CSAO
 }
 
 struct WriteCtx {
-    const uint8_t *src = nullptr;
+    const void *const *ptrs = nullptr;         // entry `row` of the caller's table lies at ptrs[row]
     uint8_t *arc = nullptr;
     uint64_t arc_cap = 0, arc_end = kHeaderSize;
-    const CSADevFile *files = nullptr;
+    const uint8_t *at(const FilePiece &f) const { return (const uint8_t *)ptrs[f.it->second.row] + f.off; }
     int64_t slack = -1;                        // CSA_DEVWRITE_SLACK, -1: not set
     CSADevWriteStats S;
     DevTimer tm;
@@ -658,7 +827,7 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
         for (FilePiece &f : t.files) {
             f.posblock = cum;                                                // csa_io.h:239
             cum += f.size;
-            if (f.size) { nonempty++; in[k] = W.src + W.files[f.it->second.row].offset + f.off; }
+            if (f.size) { nonempty++; in[k] = W.at(f); }
             npieces += piece_count(f.size, kFragPiece);
         }
         if (nonempty > 1) {
@@ -683,8 +852,7 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
                 for (FilePiece &f : P.tasks[first + k].files) {
                     f.checksum = 0;
                     if (!f.size) continue;                                       // adler32 of nothing, seed 0
-                    if (!T.add(W.src + W.files[f.it->second.row].offset + f.off, store ? (uint8_t *)d_gat.p + gat_off[k] + f.posblock : nullptr,
-                               f.size, 0)) return CSCMI_DEVICE_ERROR;
+                    if (!T.add(W.at(f), store ? (uint8_t *)d_gat.p + gat_off[k] + f.posblock : nullptr, f.size, 0)) return CSCMI_DEVICE_ERROR;
                     ff_piece.push_back(&f);
                 }
                 if (store) in[k] = (const uint8_t *)d_gat.p + gat_off[k];
@@ -786,7 +954,7 @@ int CSAMI_DeviceWritePlan(const CSADevFile *files, uint32_t n_files, const char 
     (void)arcname;
     AddPlan P;
     uint64_t raw = 0;
-    const int rc = plan_write(P, files, n_files, opt, false, 0, &raw);
+    const int rc = plan_write(P, files, n_files, opt, &raw);
     if (rc == -1) return -1;
     std::map<const void *, uint32_t> nfr;
     uint32_t mx = 0;
@@ -801,6 +969,27 @@ int CSAMI_DeviceWritePlan(const CSADevFile *files, uint32_t n_files, const char 
 int CSAMI_DeviceWrite(const void *src_dev, uint64_t src_size, CSADevFile *files, uint32_t n_files, const char *arcname,
                       void *arc_dev, uint64_t arc_cap, const CSAOptions *opt, CSADevWriteStats *st)
 {
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
+    if (st) memset(st, 0, sizeof(*st));
+    for (double &m : g_write_ms) m = 0;
+    // ---- what only this call can refuse: the entries against src_size, and src as a whole against arc
+    const uintptr_t s0 = (uintptr_t)src_dev, a0 = (uintptr_t)arc_dev;
+    uint64_t s1, a1;
+    if (!arcname || (!src_dev && src_size) || (!arc_dev && arc_cap) || !add_ok(s0, src_size, &s1) || !add_ok(a0, arc_cap, &a1)) return -1;
+    if (src_size && arc_cap && s0 < a1 && a0 < s1) return -1;
+    if (n_files && !files) return -1;
+    std::vector<const void *> ptrs(n_files, nullptr);
+    for (uint32_t i = 0; i < n_files; i++) {
+        uint64_t end;
+        if (files[i].esize < 0 || !add_ok(files[i].offset, (uint64_t)files[i].esize, &end) || end > src_size) return -1;
+        if (files[i].esize) ptrs[i] = (const uint8_t *)src_dev + files[i].offset;
+    }
+    return CSAMI_DeviceWriteFrom(ptrs.data(), files, n_files, arcname, arc_dev, arc_cap, opt, st);
+}
+
+int CSAMI_DeviceWriteFrom(const void *const *ptrs, CSADevFile *files, uint32_t n_files, const char *arcname,
+                          void *arc_dev, uint64_t arc_cap, const CSAOptions *opt, CSADevWriteStats *st)
+{
     const double t0 = now_s();
     if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
     WriteCtx W;
@@ -808,16 +997,17 @@ int CSAMI_DeviceWrite(const void *src_dev, uint64_t src_size, CSADevFile *files,
     if (st) *st = W.S;
     for (double &m : g_write_ms) m = 0;
     // ---- everything the host can refuse, before any launch
-    const uintptr_t s0 = (uintptr_t)src_dev, a0 = (uintptr_t)arc_dev;
-    uint64_t s1, a1;
-    if (!arcname || (!src_dev && src_size) || (!arc_dev && arc_cap) || !add_ok(s0, src_size, &s1) || !add_ok(a0, arc_cap, &a1)) return -1;
-    if (src_size && arc_cap && s0 < a1 && a0 < s1) return -1;
+    uint64_t a1;
+    if (!arcname || (!arc_dev && arc_cap) || !add_ok((uintptr_t)arc_dev, arc_cap, &a1) || (n_files && !ptrs)) return -1;
     AddPlan P;
-    int rc = plan_write(P, files, n_files, opt, true, src_size, &W.S.raw_bytes);
+    int rc = plan_write(P, files, n_files, opt, &W.S.raw_bytes);
     if (rc) return rc;
+    std::vector<uint64_t> sizes(n_files);
+    for (uint32_t i = 0; i < n_files; i++) sizes[i] = (uint64_t)files[i].esize;
+    if (CSAMI_CheckBuffers(ptrs, sizes.data(), n_files, arc_dev, arc_cap, 0, nullptr) != 0) return -1;
     if (arc_cap < kHeaderSize) return WRITE_ERROR;
     if (const char *e = getenv("CSA_DEVWRITE_SLACK")) { W.slack = (int64_t)strtoull(e, nullptr, 10); if (W.slack < 0) W.slack = -1; }
-    W.src = (const uint8_t *)src_dev; W.arc = (uint8_t *)arc_dev; W.arc_cap = arc_cap; W.files = files;
+    W.ptrs = ptrs; W.arc = (uint8_t *)arc_dev; W.arc_cap = arc_cap;
     if (!W.tm.ok) return CSCMI_DEVICE_ERROR;
 
     // ---- waves of consecutive task ids, largest first (csarc.cpp:355): the plan's order and the archive's

@@ -9,7 +9,11 @@
 //                         into the task's gathered stream; the 10 property bytes of every task go to the wave's property table
 //   k_frag_pieces<STORE>  one workgroup per <= 16 KiB piece of a fragment: adler32's A and B over it, and with STORE the bytes to
 //                         their place in the caller's buffer in the same pass (AsyncFileWriter, csa_io.h:274-408)
+//                         (a piece without a destination -- an entry CSAMI_DeviceReadInto only verifies -- is summed and not stored)
 //   k_frag_fold           one lane per fragment: its pieces folded in order and compared with the index's checksum
+//   k_frag_compare        k_frag_pieces<true> for CSAMI_DeviceCompare: the piece against the caller's bytes instead of onto them --
+//                         two loads in the place of a load and a store -- and the first differing index beside the sums
+//   k_frag_fold_diff      k_frag_fold, and the fragment's first differing offset from its pieces'
 //   k_block_table         one lane per task stream of a wave (write only): the archive-block table AsyncWriter would have made of
 //                         the encoder's Write calls (csa_io.h:145-201), read off the stream's framing (csa_dev_write.h)
 //
@@ -37,7 +41,8 @@ __global__ __launch_bounds__(kThreads) void k_frag_pieces(const CopyPiece *piece
     if (blockIdx.x >= npieces) return;
     const CopyPiece pc = pieces[blockIdx.x];
     uint64_t a = 0, b = 0;
-    copy_sum<STORE, true>(pc.dst, pc.src, pc.len, threadIdx.x, kThreads, a, b);
+    if (STORE && pc.dst == nullptr) copy_sum<false, true>(nullptr, pc.src, pc.len, threadIdx.x, kThreads, a, b);   // (the same for the whole workgroup)
+    else copy_sum<STORE, true>(pc.dst, pc.src, pc.len, threadIdx.x, kThreads, a, b);
     for (int off = 32; off > 0; off >>= 1) {
         a += __shfl_down(a, off, 64);
         b += __shfl_down(b, off, 64);
@@ -53,6 +58,35 @@ __global__ __launch_bounds__(kThreads) void k_frag_pieces(const CopyPiece *piece
     }
 }
 
+// k_frag_pieces<true> with two loads in the place of a load and a store: the piece's first `cmp` bytes against the caller's
+// (compare_piece, csa_dev_read.h), and the smallest differing index of the workgroup reduced the way the sums are
+__global__ __launch_bounds__(kThreads) void k_frag_compare(const CopyPiece *pieces, PieceSums *out, uint32_t *first_out, uint32_t npieces)
+{
+    if (blockIdx.x >= npieces) return;
+    const CopyPiece pc = pieces[blockIdx.x];
+    uint64_t a = 0, b = 0;
+    uint32_t first;
+    compare_piece(pc.src, pc.dst, pc.len, pc.dst ? pc.cmp : 0u, threadIdx.x, kThreads, a, b, first);
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_down(a, off, 64);
+        b += __shfl_down(b, off, 64);
+        const uint32_t f = __shfl_down(first, off, 64);
+        first = f < first ? f : first;
+    }
+    __shared__ uint64_t red[2 * (kThreads / 64)];
+    __shared__ uint32_t redf[kThreads / 64];
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[2 * wave] = a; red[2 * wave + 1] = b; redf[wave] = first; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        PieceSums s = {0, 0};
+        uint32_t f = pc.len;
+        for (uint32_t w = 0; w < kThreads / 64; w++) { s.a += red[2 * w]; s.b += red[2 * w + 1]; f = redf[w] < f ? redf[w] : f; }
+        out[blockIdx.x] = s;
+        first_out[blockIdx.x] = f;
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void k_frag_fold(const FragFold *frags, const PieceSums *sums, FragResult *out, uint32_t nfrags)
 {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
@@ -62,6 +96,21 @@ __global__ __launch_bounds__(kThreads) void k_frag_fold(const FragFold *frags, c
     FragResult r;
     r.adler = fold_pieces([s](uint32_t k) { return s[k]; }, f.npieces, f.size);
     r.ok = r.adler == f.checksum ? 1u : 0u;
+    out[i] = r;
+}
+
+__global__ __launch_bounds__(kThreads) void k_frag_fold_diff(const FragFold *frags, const PieceSums *sums, const uint32_t *firsts, FragDiff *out,
+                                                             uint32_t nfrags)
+{
+    const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
+    if (i >= nfrags) return;
+    const FragFold f = frags[i];
+    const PieceSums *s = sums + f.first;
+    const uint32_t *d = firsts + f.first;
+    FragDiff r;
+    r.adler = fold_pieces([s](uint32_t k) { return s[k]; }, f.npieces, f.size);
+    r.ok = r.adler == f.checksum ? 1u : 0u;
+    r.first = fold_first([d](uint32_t k) { return d[k]; }, f.npieces, f.size);
     out[i] = r;
 }
 
@@ -77,10 +126,21 @@ void launch_frag_pieces(const void *pieces, void *sums, uint32_t npieces, bool s
     else hipLaunchKernelGGL(k_frag_pieces<false>, dim3(npieces ? npieces : 1), dim3(kThreads), 0, st, (const CopyPiece *)pieces, (PieceSums *)sums, npieces);
 }
 
+void launch_frag_compare(const void *pieces, void *sums, void *firsts, uint32_t npieces, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_frag_compare, dim3(npieces ? npieces : 1), dim3(kThreads), 0, st, (const CopyPiece *)pieces, (PieceSums *)sums, (uint32_t *)firsts, npieces);
+}
+
 void launch_frag_fold(const void *frags, const void *sums, void *out, uint32_t nfrags, hipStream_t st)
 {
     hipLaunchKernelGGL(k_frag_fold, dim3(nfrags ? (nfrags + kThreads - 1) / kThreads : 1), dim3(kThreads), 0, st,
                        (const FragFold *)frags, (const PieceSums *)sums, (FragResult *)out, nfrags);
+}
+
+void launch_frag_fold_diff(const void *frags, const void *sums, const void *firsts, void *out, uint32_t nfrags, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_frag_fold_diff, dim3(nfrags ? (nfrags + kThreads - 1) / kThreads : 1), dim3(kThreads), 0, st,
+                       (const FragFold *)frags, (const PieceSums *)sums, (const uint32_t *)firsts, (FragDiff *)out, nfrags);
 }
 
 // One workgroup for the wave: lane t walks tasks t, t + 256, ... -- a step is one coder block, a few dependent byte loads, so the

@@ -12,8 +12,12 @@
 // pieces fold as b' = b + len * a + B, a' = a + A (mod 65521), seed 0.  CSA_Add and CSAMI_Adler32Device (csa_archive.cpp) take
 // the same sums with k_frag_pieces<false> and fold them on the host: their pieces are cut per chunk and their seed runs on.
 //
-// The template parameter PLANT switches one deliberate mistake on (0: none).  The product instantiates 0 only; the model runs each
-// of the others and has to see it caught by a named case.
+// CSAMI_DeviceCompare runs the same tables with k_frag_compare and k_frag_fold_diff in the place of the last two: compare_sum reads a
+// fragment's piece and the caller's range side by side, compare_piece joins a compared front and a summed rest into one piece's sums,
+// fold_first folds the pieces' first differences (tests/model/csa_dev_compare_model.cpp is their model).
+//
+// The template parameter PLANT switches one deliberate mistake on (0: none).  The product instantiates 0 only; the models run each
+// of the others and have to see it caught by a named case.
 #pragma once
 #include <stdint.h>
 
@@ -30,13 +34,17 @@ constexpr uint32_t kGatherPiece = 65536;        // bytes of an extent one workgr
 constexpr uint32_t kFragPiece = 16384;          // bytes of a fragment one workgroup sums (and stores)
 constexpr uint32_t kAdlerBase = 65521;
 
-enum Plant { kPlantNone = 0, kPlantTailDropped = 1, kPlantWeightOffByOne = 2, kPlantFoldLastLen = 3, kPlantHeadWrongPointer = 4 };
+enum Plant {
+    kPlantNone = 0, kPlantTailDropped = 1, kPlantWeightOffByOne = 2, kPlantFoldLastLen = 3, kPlantHeadWrongPointer = 4,
+    // compare_sum and fold_first (tests/model/csa_dev_compare_model.cpp)
+    kPlantCmpHeadNotCompared = 5, kPlantCmpUnitWithoutHead = 6, kPlantCmpWindowPastEnd = 7, kPlantFirstPieceIndex = 8
+};
 
-struct CopyPiece {         // one workgroup of k_gather_extents / k_frag_pieces
+struct CopyPiece {         // one workgroup of k_gather_extents / k_frag_pieces / k_frag_compare
     const uint8_t *src;
-    uint8_t *dst;          // k_frag_pieces<false>: unused
+    uint8_t *dst;          // k_frag_pieces<false>: unused; k_frag_pieces<true>: NULL = summed, not stored; k_frag_compare: the caller's range y, read only
     uint32_t len;          // <= kGatherPiece / kFragPiece
-    uint32_t pad;
+    uint32_t cmp;          // k_frag_compare: the leading bytes that are compared, <= len, 0 where dst is NULL; the others: 0, unused
 };
 struct PieceSums { uint64_t a, b; };
 struct FragFold {          // one lane of k_frag_fold
@@ -47,6 +55,10 @@ struct FragFold {          // one lane of k_frag_fold
     uint32_t pad;
 };
 struct FragResult { uint32_t adler, ok; };      // all the host reads back of a fragment
+struct FragDiff {                               // ... of a fragment that was compared (k_frag_fold_diff)
+    uint32_t adler, ok;
+    uint64_t first;        // the first differing offset in the fragment's delivered bytes, FragFold::size if there is none
+};
 
 CSADEV_FHD uint64_t piece_count(uint64_t size, uint32_t piece) { return (size + piece - 1) / piece; }
 
@@ -60,7 +72,7 @@ CSADEV_FHD uint64_t piece_split(const uint8_t *src, uint8_t *dst, uint64_t size,
         p.src = src + off;
         p.dst = dst ? dst + off : nullptr;
         p.len = (uint32_t)(size - off < piece ? size - off : piece);
-        p.pad = 0;
+        p.cmp = 0;
         put(k, p);
     }
     return k;
@@ -80,6 +92,36 @@ CSADEV_FHD void sum_word(uint32_t w, uint32_t i0, uint32_t wl, uint64_t &a, uint
 #endif
     a += s;
     b += (uint64_t)(wl - i0) * s - t;
+}
+
+// Unit i -- the 16 bytes [s0 + 16 i, s0 + 16 i + 16) -- of a range r[0, n), where s0 = r + head has any alignment and the unit lies
+// inside the range: one aligned 16-byte load; or two of them, funnel-shifted into place; or, where that 32-byte window would begin
+// before r or end behind r + n (the first and the last unit, at most), the 16 bytes one by one.
+template <bool WINDOW_UNCHECKED = false>
+CSADEV_FHD Vec16 load_unit(const uint8_t *s0, uint32_t head, uint32_t n, uint32_t i)
+{
+    const uint32_t m = (uint32_t)(uintptr_t)s0 & 15u;
+    const uintptr_t base = (uintptr_t)s0 - m;                         // aligned; vector i of it covers bytes [16 i - m, 16 i - m + 16) of s0
+    const uint32_t sw = m >> 2, sb = 8 * (m & 3u);
+    Vec16 o;
+    if (m == 0) {
+        o = *(const Vec16 *)(base + 16ull * i);
+    } else if (WINDOW_UNCHECKED || (head + 16 * i >= m && head + 16 * i + 32 <= n + m)) {   // the window [16 i - m, 16 i - m + 32) of s0 lies in r[0, n)
+        const Vec16 x = *(const Vec16 *)(base + 16ull * i), y = *(const Vec16 *)(base + 16ull * i + 16);
+        const uint32_t t0 = (sw & 2u) ? x.w[2] : x.w[0], t1 = (sw & 2u) ? x.w[3] : x.w[1], t2 = (sw & 2u) ? y.w[0] : x.w[2],
+                       t3 = (sw & 2u) ? y.w[1] : x.w[3], t4 = (sw & 2u) ? y.w[2] : y.w[0], t5 = (sw & 2u) ? y.w[3] : y.w[1];
+        const uint32_t u0 = (sw & 1u) ? t1 : t0, u1 = (sw & 1u) ? t2 : t1, u2 = (sw & 1u) ? t3 : t2, u3 = (sw & 1u) ? t4 : t3,
+                       u4 = (sw & 1u) ? t5 : t4;
+        o.w[0] = (uint32_t)((((uint64_t)u1 << 32) | u0) >> sb);
+        o.w[1] = (uint32_t)((((uint64_t)u2 << 32) | u1) >> sb);
+        o.w[2] = (uint32_t)((((uint64_t)u3 << 32) | u2) >> sb);
+        o.w[3] = (uint32_t)((((uint64_t)u4 << 32) | u3) >> sb);
+    } else {
+        const uint8_t *p = s0 + 16 * i;
+        for (uint32_t k = 0; k < 4; k++)
+            o.w[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
+    }
+    return o;
 }
 
 // Thread `tid` of `nthreads`: its share of src[0, n) -- copied to dst[0, n) (STORE) and/or summed into a, b as one piece of n bytes
@@ -111,28 +153,8 @@ CSADEV_FHD void copy_sum(uint8_t *dst, const uint8_t *src, uint32_t n, uint32_t 
         if (SUM) { a += v; b += (uint64_t)(wl - k) * v; }
     }
     const uint8_t *s0 = src + head;                                   // unit i is source bytes [s0 + 16 i, s0 + 16 i + 16)
-    const uint32_t m = (uint32_t)(uintptr_t)s0 & 15u;
-    const uintptr_t base = (uintptr_t)s0 - m;                         // aligned; vector i of it covers source bytes [16 i - m, 16 i - m + 16) of s0
-    const uint32_t sw = m >> 2, sb = 8 * (m & 3u);
     for (uint32_t i = tid; i < units; i += nthreads) {
-        Vec16 o;
-        if (m == 0) {
-            o = *(const Vec16 *)(base + 16ull * i);
-        } else if (head + 16 * i >= m && head + 16 * i + 32 <= n + m) {       // the window [16 i - m, 16 i - m + 32) of s0 lies in src[0, n)
-            const Vec16 x = *(const Vec16 *)(base + 16ull * i), y = *(const Vec16 *)(base + 16ull * i + 16);
-            const uint32_t t0 = (sw & 2u) ? x.w[2] : x.w[0], t1 = (sw & 2u) ? x.w[3] : x.w[1], t2 = (sw & 2u) ? y.w[0] : x.w[2],
-                           t3 = (sw & 2u) ? y.w[1] : x.w[3], t4 = (sw & 2u) ? y.w[2] : y.w[0], t5 = (sw & 2u) ? y.w[3] : y.w[1];
-            const uint32_t u0 = (sw & 1u) ? t1 : t0, u1 = (sw & 1u) ? t2 : t1, u2 = (sw & 1u) ? t3 : t2, u3 = (sw & 1u) ? t4 : t3,
-                           u4 = (sw & 1u) ? t5 : t4;
-            o.w[0] = (uint32_t)((((uint64_t)u1 << 32) | u0) >> sb);
-            o.w[1] = (uint32_t)((((uint64_t)u2 << 32) | u1) >> sb);
-            o.w[2] = (uint32_t)((((uint64_t)u3 << 32) | u2) >> sb);
-            o.w[3] = (uint32_t)((((uint64_t)u4 << 32) | u3) >> sb);
-        } else {
-            const uint8_t *p = s0 + 16 * i;
-            for (uint32_t k = 0; k < 4; k++)
-                o.w[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
-        }
+        const Vec16 o = load_unit(s0, head, n, i);
         if (STORE) *(Vec16 *)(dst + head + 16 * i) = o;
         if (SUM) {
             const uint32_t i0 = head + 16 * i;
@@ -142,6 +164,84 @@ CSADEV_FHD void copy_sum(uint8_t *dst, const uint8_t *src, uint32_t n, uint32_t 
             sum_word(o.w[3], i0 + 12, wl, a, b);
         }
     }
+}
+
+// Thread `tid` of `nthreads`: its share of x[0, n) against y[0, n) (CSAMI_DeviceCompare).  x[0, n) is summed into a, b exactly as
+// copy_sum<false, true> sums it (SUM) and compared with y[0, n): `first` is the smallest index at which THIS thread saw a difference,
+// n if it saw none (the caller takes the minimum over the threads).  n <= 65536.  x and y have any, unrelated, alignment, and
+// nothing outside x[0, n) or y[0, n) is loaded, not even by an aligned 16-byte window.
+//
+// The anchor is x: up to 15 head bytes bring it to a 16-byte line and up to 15 tail bytes end the range, byte by byte on both
+// sides.  Between them a unit is one aligned 16-byte load of x against load_unit of y -- two aligned loads funnel-shifted, or bytes
+// where that window would leave y[0, n).  The first differing byte of a unit is read off the XOR of its words: trailing zeros / 8.
+template <bool SUM, int PLANT = kPlantNone>
+CSADEV_FHD void compare_sum(const uint8_t *x, const uint8_t *y, uint32_t n, uint32_t tid, uint32_t nthreads, uint64_t &a, uint64_t &b,
+                            uint32_t &first)
+{
+    uint32_t head = (0u - (uint32_t)(uintptr_t)x) & 15u;
+    if (head > n) head = n;
+    const uint32_t units = (n - head) >> 4, tail = (n - head) & 15u;
+    first = n;
+    if (tid < head) {
+        const uint32_t v = x[tid];
+        if (PLANT != kPlantCmpHeadNotCompared && v != y[tid]) first = tid;
+        if (SUM) { a += v; b += (uint64_t)(n - tid) * v; }
+    }
+    if (nthreads - 1 - tid < tail) {
+        const uint32_t k = head + 16 * units + (nthreads - 1 - tid);
+        const uint32_t v = x[k];
+        if (v != y[k] && k < first) first = k;
+        if (SUM) { a += v; b += (uint64_t)(n - k) * v; }
+    }
+    for (uint32_t i = tid; i < units; i += nthreads) {
+        const uint32_t i0 = head + 16 * i;
+        const Vec16 p = *(const Vec16 *)(x + i0), q = load_unit<PLANT == kPlantCmpWindowPastEnd>(y + head, head, n, i);
+        const uint64_t lo = ((uint64_t)(p.w[1] ^ q.w[1]) << 32) | (p.w[0] ^ q.w[0]), hi = ((uint64_t)(p.w[3] ^ q.w[3]) << 32) | (p.w[2] ^ q.w[2]);
+        if (lo | hi) {
+            const uint32_t at = (PLANT == kPlantCmpUnitWithoutHead ? 16 * i : i0)
+                                + (lo ? (uint32_t)__builtin_ctzll(lo) >> 3 : 8u + ((uint32_t)__builtin_ctzll(hi) >> 3));
+            if (at < first) first = at;
+        }
+        if (SUM) {
+            sum_word(p.w[0], i0, n, a, b);
+            sum_word(p.w[1], i0 + 4, n, a, b);
+            sum_word(p.w[2], i0 + 8, n, a, b);
+            sum_word(p.w[3], i0 + 12, n, a, b);
+        }
+    }
+}
+
+// A piece of k_frag_compare: the first `cmp` of its `len` bytes are compared (compare_sum), the rest are summed only
+// (copy_sum<false, true>), and the two parts' sums join as one piece of `len` bytes -- a byte of the front part weighs
+// len - i = (cmp - i) + (len - cmp).  cmp == 0 (nothing to compare against, y may be NULL) and cmp == len are the usual cases; a
+// piece in between is the one that straddles the end of the caller's buffer.  `first`: as compare_sum over [0, cmp), else len.
+template <int PLANT = kPlantNone>
+CSADEV_FHD void compare_piece(const uint8_t *x, const uint8_t *y, uint32_t len, uint32_t cmp, uint32_t tid, uint32_t nthreads, uint64_t &a,
+                              uint64_t &b, uint32_t &first)
+{
+    first = len;
+    if (cmp) {
+        uint64_t fa = 0, fb = 0;
+        uint32_t f;
+        compare_sum<true, PLANT>(x, y, cmp, tid, nthreads, fa, fb, f);
+        a += fa;
+        b += fb + (uint64_t)(len - cmp) * fa;
+        if (f < cmp) first = f;
+    }
+    if (cmp < len) copy_sum<false, true>(nullptr, x + cmp, len - cmp, tid, nthreads, a, b);
+}
+
+// The first differing offset of a fragment of `size` delivered bytes from its pieces' `first` values (first(k): piece k's, its
+// length where the piece saw none): first_piece_index * kFragPiece + first, or `size` if no piece saw one
+template <int PLANT = kPlantNone, class First>
+CSADEV_FHD uint64_t fold_first(First first, uint32_t npieces, uint64_t size)
+{
+    for (uint32_t k = 0; k < npieces; k++) {
+        const uint64_t left = size - (uint64_t)k * kFragPiece, len = left < kFragPiece ? left : kFragPiece;
+        const uint32_t f = first(k);
+        if (f < len) return (uint64_t)(PLANT == kPlantFirstPieceIndex ? 0u : k) * kFragPiece + f;
+    }
+    return size;
 }
 
 // adler32 (seed 0) of a fragment of `size` bytes from the sums of its piece_count(size, kFragPiece) consecutive pieces; sums(k)

@@ -248,7 +248,8 @@ typedef struct CSADevStopStats {
 } CSADevStopStats;
 int CSAMI_DeviceReadStop(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
                          const CSAOptions *o, CSADevFile *files, uint32_t cap, CSADevReadStats *st, CSADevStopStats *stop_stats);
-/* HIP-event milliseconds of the last CSAMI_DeviceRead's launches by kernel: [0] k_gather_extents, [1] k_frag_pieces, [2] k_frag_fold */
+/* HIP-event milliseconds of the last CSAMI_DeviceRead's launches by kernel: [0] k_gather_extents, [1] k_frag_pieces, [2] k_frag_fold
+ * (after CSAMI_DeviceCompare: [1] k_frag_compare, [2] k_frag_fold_diff) */
 void CSAMI_DeviceKernelMs(const CSADevArchive *a, double ms[3]);
 void CSAMI_DeviceClose(CSADevArchive *a);
 /* host only, no GPU: the same plan from raw (unpacked) index bytes, as CSA_ReadIndex returns them.  files[i].name points at the
@@ -329,6 +330,76 @@ int CSAMI_DeviceWrite(const void *src_dev, uint64_t src_size, CSADevFile *files,
 /* HIP-event milliseconds of this thread's last CSAMI_DeviceWrite by kernel: [0] k_frag_pieces, [1] k_frag_fold, [2] k_block_table,
  * [3] k_gather_extents (placement) */
 void CSAMI_DeviceWriteKernelMs(double ms[4]);
+
+/* ---- the device-resident archive over the caller's own buffers: write from, read into, compare against; not in the reference ----
+ *
+ * CSAMI_DeviceWrite and CSAMI_DeviceRead want every entry in ONE buffer -- src plus an offset per entry, dst in a layout the library
+ * chooses.  The three calls below take one device pointer per entry instead, so a set of separately allocated buffers (the tensors
+ * of a state dict, a batch of shards) is archived where it lies, an archive is read straight into the buffers that are to hold it,
+ * and "does this archive hold exactly what these buffers hold?" is answered on the device, byte for byte -- what `tar --compare`
+ * answers.  The contiguous calls are these calls with ptrs[i] = src + offset_i / dst + offset_i: there is one write path and one
+ * read path, and every sentence of the two sections above that does not speak of src, dst or the layout of dst holds here.
+ * Every pointer may have any alignment.  Without a visible device all three return CSCMI_DEVICE_ERROR and touch nothing. */
+
+/* host only, no GPU: the address checks the three calls below make before anything is launched.
+ * Range i is [ptrs[i], ptrs[i] + sizes[i]); a range of size 0 overlaps nothing and may be NULL.
+ * Returns 0, or -1 with *bad (bad may be NULL) set to the lowest index of a range that is refused: a NULL pointer with size > 0; one
+ * whose end wraps in 64 bits (ptr + size == 2^64 does not); one that overlaps [excl, excl + excl_size) (excl_size 0: nothing does);
+ * and, with disjoint != 0, one that overlaps another range of the table -- both ranges of such a pair are refused, ranges that touch
+ * are not.  ptrs or sizes NULL with n > 0 refuses index 0.  The ranges are sorted, not compared pair by pair: n log n. */
+int CSAMI_CheckBuffers(const void *const *ptrs, const uint64_t *sizes, uint32_t n,
+                       const void *excl, uint64_t excl_size, int disjoint, uint32_t *bad);
+
+/* CSAMI_DeviceWrite with entry i's bytes at ptrs[i][0, esize_i); files[i].offset is ignored, ptrs[i] is not looked at where esize_i
+ * is 0 and may be NULL there.  The plan, the archive bytes (byte for byte what CSA_Add and CSAMI_DeviceWrite write for the same entries
+ * and options), the return values, *st, the safety contract -- nothing outside [ptrs[i], ptrs[i] + esize_i) is loaded, not even by an
+ * aligned 16-byte window -- the bus contract, CSA_DEVWRITE_SLACK and CSAMI_DeviceWriteKernelMs are CSAMI_DeviceWrite's; a task that
+ * is one range of one entry is still encoded where it lies.  The entries are only read, so they may alias each other.  -1 with
+ * nothing launched, besides what CSAMI_DeviceWrite refuses in a table: ptrs == NULL with n_files > 0, and whatever
+ * CSAMI_CheckBuffers(ptrs, esizes, n_files, arc_dev, arc_cap, 0) refuses -- an entry that overlaps [arc, arc + arc_cap) above all. */
+int CSAMI_DeviceWriteFrom(const void *const *ptrs, CSADevFile *files, uint32_t n_files, const char *arcname,
+                          void *arc_dev, uint64_t arc_cap, const CSAOptions *o, CSADevWriteStats *st);
+
+#define CSAMI_DEV_STOP_EARLY 1u
+/* CSAMI_DeviceRead (flags == 0) or CSAMI_DeviceReadStop (flags & CSAMI_DEV_STOP_EARLY; then *stop_stats is filled, else zeroed;
+ * it may be NULL) with entry i of the selection -- in the order CSAMI_DevicePlan lists it -- delivered to ptrs[i][0, size_i), of which
+ * caps[i] bytes are the caller's.  n must be that plan's *n_files, else -1; files, if not NULL, has room for n and is filled as by
+ * CSAMI_DeviceRead, with offset 0.  ptrs[i] == NULL (or ptrs == NULL: all of them): the entry is verified only, `csarc t` for that
+ * entry; it is still selected, so it counts for which tasks are decoded and where they stop.  A wave stays three launches:
+ * k_frag_pieces sums a piece without a destination and does not store it.
+ * Refused with nothing launched and *st zeroed: WRITE_ERROR for a non-NULL ptrs[i] with caps[i] < size_i; -1 for what
+ * CSAMI_CheckBuffers(ptrs, sizes, n, arc, arc_size, 1) refuses -- destinations that overlap each other or the archive.
+ * Nothing outside [ptrs[i], ptrs[i] + size_i) is stored, and bytes of it that no delivered fragment covers stay untouched.
+ * The return value otherwise, which fragments are verified, failed_frags and st->verify_failures, st->launches == 3 * st->waves,
+ * the read-back bound and CSAMI_DeviceKernelMs: as documented at CSAMI_DeviceRead and CSAMI_DeviceReadStop. */
+int CSAMI_DeviceReadInto(CSADevArchive *a, const char *const *names, int nnames, void *const *ptrs, const uint64_t *caps, uint32_t n,
+                         uint32_t flags, const CSAOptions *o, CSADevFile *files, CSADevReadStats *st, CSADevStopStats *stop_stats);
+
+/* Entry i of the selection against the sizes[i] bytes at ptrs[i]: `csarc t` and a byte-for-byte comparison in the same pass.
+ * Arguments as CSAMI_DeviceReadInto; nothing of the caller's is written, so the buffers may alias each other, but not the archive
+ * (-1, nothing launched, for what CSAMI_CheckBuffers(ptrs, sizes, n, arc, arc_size, 0) refuses, and for diffs == NULL with n > 0).
+ * diffs[i].status == 0: the entry equals the buffer.  Otherwise it is the sum of
+ *   CSA_DIFF_SIZE     sizes[i] != size_i; the comparison then covers the offsets below the smaller of the two (the compared size)
+ *   CSA_DIFF_BYTES    a compared byte differs; first_diff is the smallest such offset in the entry (UINT64_MAX without this flag):
+ *                     the minimum, taken on the host, of posfile + offset over the entry's fragments
+ *   CSA_DIFF_SKIPPED  ptrs[i] == NULL: the entry is verified only; no other flag is set then
+ *   CSA_DIFF_SHORT    a byte below the compared size belongs to a fragment but was not delivered -- its task failed or ended early --
+ *                     so it was not compared
+ * Bytes of the entry that no fragment covers are not compared.  failed_frags is the entry's count of failed adler32s, as in files.
+ * adler32 is taken over every delivered fragment in the same pass and reported as by CSAMI_DeviceRead with dst == NULL, and the return
+ * value is the archive's health, exactly what CSAMI_DeviceReadInto with every pointer NULL returns: differences never change it.
+ * Per wave three launches of this layer: k_gather_extents; k_frag_compare -- k_frag_pieces with two loads in the place of a load and
+ * a store, its time in slot [1] of CSAMI_DeviceKernelMs; k_frag_fold_diff, which also folds each fragment's first differing offset.
+ * Read back: at most 16 bytes a task and 16 bytes a fragment (st->readback_bytes, with CSAMI_DeviceOpen's).
+ * Nothing outside [ptrs[i], ptrs[i] + min(sizes[i], size_i)) is loaded, not even by an aligned 16-byte window. */
+typedef struct CSADevDiff { uint64_t first_diff; uint32_t status; uint32_t failed_frags; } CSADevDiff;
+#define CSA_DIFF_BYTES 1u
+#define CSA_DIFF_SIZE 2u
+#define CSA_DIFF_SKIPPED 4u
+#define CSA_DIFF_SHORT 8u
+int CSAMI_DeviceCompare(CSADevArchive *a, const char *const *names, int nnames, const void *const *ptrs, const uint64_t *sizes, uint32_t n,
+                        uint32_t flags, const CSAOptions *o, CSADevFile *files, CSADevDiff *diffs, CSADevReadStats *st,
+                        CSADevStopStats *stop_stats);
 
 /* YYYYMMDDHHMMSS <-> time_t, csa_common.cpp:3-39 */
 int64_t CSA_DecimalTime(int64_t unix_seconds);
