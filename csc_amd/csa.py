@@ -76,6 +76,17 @@ class CSADevDiff(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CSADevSlice(C.Structure):
+    _fields_ = [("offset", C.c_uint64), ("run", C.c_uint64), ("stride", C.c_uint64), ("count", C.c_uint64)]
+
+
+class CSADevSliceStats(C.Structure):
+    _fields_ = [("selected_bytes", C.c_uint64), ("touched_bytes", C.c_uint64), ("periodic_pieces", C.c_uint64), ("plain_pieces", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 LIST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(CSAFrag))
 
 SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", "CSA_ReadIndex",
@@ -84,7 +95,8 @@ SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", 
            "CSAMI_DeviceOpen", "CSAMI_DevicePlan", "CSAMI_DeviceRead", "CSAMI_DeviceClose", "CSAMI_PlanDeviceLayout", "CSAMI_DeviceKernelMs",
            "CSAMI_DeviceReadStop", "CSAMI_PlanDeviceStops",
            "CSAMI_DeviceWritePlan", "CSAMI_DeviceWrite", "CSAMI_DeviceWriteKernelMs",
-           "CSAMI_CheckBuffers", "CSAMI_DeviceWriteFrom", "CSAMI_DeviceReadInto", "CSAMI_DeviceCompare"]
+           "CSAMI_CheckBuffers", "CSAMI_DeviceWriteFrom", "CSAMI_DeviceReadInto", "CSAMI_DeviceCompare",
+           "CSAMI_DeviceReadSlices", "CSAMI_PlanDeviceSlices"]
 
 CSA_MAX_FRAGMENTS = 127
 CSA_TOO_MANY_FRAGMENTS = -94
@@ -172,6 +184,13 @@ def lib():
         L.CSAMI_DeviceCompare.argtypes = [C.c_void_p, names, C.c_int, ptrs, u64s, C.c_uint32, C.c_uint32, C.POINTER(CSAOptions), files,
                                           C.POINTER(CSADevDiff), C.POINTER(CSADevReadStats), C.POINTER(CSADevStopStats)]
         L.CSAMI_DeviceCompare.restype = C.c_int
+        slices = C.POINTER(CSADevSlice)
+        L.CSAMI_DeviceReadSlices.argtypes = [C.c_void_p, names, C.c_int, slices, ptrs, u64s, C.c_uint32, C.c_uint32, C.POINTER(CSAOptions), files,
+                                             C.POINTER(CSADevReadStats), C.POINTER(CSADevStopStats), C.POINTER(CSADevSliceStats)]
+        L.CSAMI_DeviceReadSlices.restype = C.c_int
+        L.CSAMI_PlanDeviceSlices.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, names, C.c_int, slices, C.c_uint32, u64s, u64s, u64s, C.c_uint32,
+                                             C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.CSAMI_PlanDeviceSlices.restype = C.c_int
         _lib = L
     return _lib
 
@@ -352,6 +371,51 @@ def plan_device_stops(raw_index: bytes, arc_size: int, names: Sequence[str] = ()
     bids, stops, raws = ((C.c_uint64 * max(k, 1))() for _ in range(3))
     rc = lib().CSAMI_PlanDeviceStops(buf, len(raw_index), arc_size, arr, n, bids, stops, raws, k, C.byref(nt))
     return rc, [{"bid": int(b), "stop": int(s), "raw": int(r)} for b, s, r in zip(bids[:k], stops[:k], raws[:k])]
+
+
+def rows_slice(row_bytes: int, r0: int, r1: int, c0: int = 0, c1: Optional[int] = None):
+    """the slice (offset, run, stride, count) for rows r0..r1 and byte columns c0..c1 (c1 None: the row's end) of a row-major matrix
+    of row_bytes a row; a block of whole rows, or of one row, is one byte range (count == 1)"""
+    c1 = row_bytes if c1 is None else c1
+    if not (0 <= r0 < r1 and 0 <= c0 < c1 <= row_bytes):
+        raise ValueError("an empty or inverted block")
+    if (c0, c1) == (0, row_bytes) or r1 - r0 == 1:
+        return (r0 * row_bytes + c0, (r1 - r0 - 1) * row_bytes + c1 - c0, (r1 - r0 - 1) * row_bytes + c1 - c0, 1)
+    return (r0 * row_bytes + c0, c1 - c0, row_bytes, r1 - r0)
+
+
+def _slice_table(files, slices):
+    """the CSADevSlice of every entry of a files table; slices: {stored name: (offset, length) | (offset, run, stride, count)}, an entry
+    without a key gets count 0.  KeyError for a key that is no entry of the table."""
+    slices = dict(slices)
+    unknown = set(slices) - {f["name"] for f in files}
+    if unknown:
+        raise KeyError(sorted(unknown)[0])
+    arr = (CSADevSlice * max(len(files), 1))()
+    for a, f in zip(arr, files):
+        s = slices.get(f["name"])
+        if s is not None:
+            a.offset, a.run, a.stride, a.count = (s[0], s[1], s[1], 1) if len(s) == 2 else s
+    return arr
+
+
+def plan_device_slices(raw_index: bytes, arc_size: int, slices_by_entry, names: Sequence[str] = ()):
+    """CSAMI_PlanDeviceSlices (host only): the tasks DeviceArchive.extract_slices(slices_by_entry, names=names) decodes for these raw
+    index bytes, in decode order, each with its stop under stop_early -> (rc, [{"bid", "stop", "raw"}], number of touched fragments)"""
+    rc, files, _, _ = plan_device_layout(raw_index, arc_size, names)
+    if rc != 0:
+        return rc, [], 0
+    table = _slice_table(files, slices_by_entry)
+    buf = (C.c_uint8 * max(len(raw_index), 1)).from_buffer_copy(raw_index or b"\0")
+    arr, n = _names(names)
+    nt, touched = C.c_uint32(), C.c_uint32()
+    rc = lib().CSAMI_PlanDeviceSlices(buf, len(raw_index), arc_size, arr, n, table, len(files), None, None, None, 0, C.byref(nt), C.byref(touched))
+    if rc != 0:
+        return rc, [], 0
+    k = nt.value
+    bids, stops, raws = ((C.c_uint64 * max(k, 1))() for _ in range(3))
+    rc = lib().CSAMI_PlanDeviceSlices(buf, len(raw_index), arc_size, arr, n, table, len(files), bids, stops, raws, k, C.byref(nt), C.byref(touched))
+    return rc, [{"bid": int(b), "stop": int(s), "raw": int(r)} for b, s, r in zip(bids[:k], stops[:k], raws[:k])], int(touched.value)
 
 
 def _write_table(files):
@@ -580,6 +644,33 @@ class DeviceArchive:
             out.update(ss.as_dict())
         out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(table, files)]
         return rc, out
+
+    def extract_slices(self, slices, dsts=None, names: Sequence[str] = (), stop_early=True, **opts):
+        """byte ranges and strided slices of entries (CSAMI_DeviceReadSlices) -> (rc, {name: uint8 CUDA tensor of the packed slice},
+        stats dict); stats["files"] as in extract, and the slice statistics beside the read's.  slices: {stored name: (offset,
+        length) | (offset, run, stride, count)} -- rows_slice makes them for a matrix; a selected entry without a key is not read at
+        all.  dsts: as in extract_into, except that a sliced entry that is absent gets a tensor allocated here; None: its touched
+        fragments are verified only.  A tensor needs at least run * count bytes and the result is its front of that size."""
+        import torch
+        files = self.plan(names)[0]
+        table = _slice_table(files, slices)
+        given = dict(dsts or {})
+        for f, s in zip(files, table):
+            if f["name"] not in given and s.count:
+                given[f["name"]] = torch.empty(s.run * s.count, dtype=torch.uint8, device=self._arc.device)
+        files, live, ptrs, caps = self._by_name(given, names)
+        arr, n = _names(names)
+        ftab, st, ss, sl, o = (CSADevFile * max(len(files), 1))(), CSADevReadStats(), CSADevStopStats(), CSADevSliceStats(), options(**opts)
+        torch.cuda.synchronize()
+        rc = lib().CSAMI_DeviceReadSlices(self._h, arr, n, table, ptrs, caps, len(files), CSAMI_DEV_STOP_EARLY if stop_early else 0, C.byref(o),
+                                          ftab, C.byref(st), C.byref(ss), C.byref(sl))
+        out = st.as_dict()
+        if stop_early:
+            out.update(ss.as_dict())
+        out.update(sl.as_dict())
+        out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(ftab, files)]
+        got = {f["name"]: t[:s.run * s.count] for f, t, s in zip(files, live, table) if t is not None and s.count and rc != WRITE_ERROR}
+        return rc, got, out
 
     def compare(self, srcs, names: Sequence[str] = (), stop_early=False, **opts):
         """`csarc t` and a byte-for-byte comparison with tensors of the caller's in one pass (CSAMI_DeviceCompare) ->

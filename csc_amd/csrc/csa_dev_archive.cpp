@@ -25,7 +25,8 @@ using namespace csa;
 // csa_dev_kernels.hip (tables and copy: csa_dev_read.h) and in CSCMI_DecodeDeviceBatch; CSAMI_DeviceReadStop is the same body with
 // every task stopped behind its last selected byte (CSCMI_DecodeDeviceBatchStop).  All of them are one path over a device pointer
 // per entry (ReadBufs, dev_read_run): CSAMI_DeviceReadInto hands the caller's pointers in, CSAMI_DeviceRead / ReadStop the layout's
-// offsets into dst, and CSAMI_DeviceCompare the caller's pointers to be compared with instead of stored to.
+// offsets into dst, and CSAMI_DeviceCompare the caller's pointers to be compared with instead of stored to.  CSAMI_DeviceReadSlices
+// is that path over a layout that holds only the fragments its slices touch (dev_layout), with k_frag_slices as the middle kernel.
 // ---------------------------------------------------------------------------------------------
 struct CSADevArchive {
     const uint8_t *arc = nullptr;
@@ -48,6 +49,11 @@ struct DevLayout {
     std::vector<DevFilePlan> files;
     std::vector<DevTask> tasks;                // decode order
     uint64_t dst_bytes = 0;
+    // CSAMI_DeviceReadSlices only: per entry its checked slice and the bytes it selects; the tasks then hold the TOUCHED fragments
+    bool sliced = false;
+    std::vector<csadev::Slice> slices;
+    std::vector<uint64_t> slice_bytes;
+    uint64_t touched_frags = 0, touched_bytes = 0;
 };
 
 // A task's raw size: max(posblock + size) over ALL fragments of its bid.  false if any sum of the index wraps.
@@ -65,17 +71,35 @@ bool dev_task_sizes(const Index &index, std::map<uint64_t, uint64_t> &raw)
 }
 
 // The layout of dst and the tasks to decode for a selection.  false if the sum wraps.
-bool dev_layout(const Index &index, const std::map<uint64_t, uint64_t> &raw, const Selection &sel, DevLayout &L)
+// With `slices` (one per selected entry, nslices of them; false for another number and for a slice slice_check refuses) a fragment
+// counts only if its entry's slice touches it: for the tasks, their order and their stops.
+bool dev_layout(const Index &index, const std::map<uint64_t, uint64_t> &raw, const Selection &sel, DevLayout &L,
+                const CSADevSlice *slices = nullptr, size_t nslices = 0)
 {
     std::map<uint64_t, size_t> idmap;
     uint64_t off = 0;
+    L.sliced = slices != nullptr;
     for (Index::const_iterator it = index.begin(); it != index.end(); ++it) {
         if (!sel.has(it->first.c_str())) continue;
         uint64_t size = 0;
         const uint32_t fi = (uint32_t)L.files.size();
+        for (const CSAFrag &f : it->second.frags) size = std::max(size, f.posfile + f.size);   // (checked by dev_task_sizes)
+        csadev::Slice sl = {0, 0, 0, 0};
+        if (L.sliced) {
+            if (fi >= nslices) return false;
+            sl = csadev::Slice{slices[fi].offset, slices[fi].run, slices[fi].stride, slices[fi].count};
+            uint64_t bytes;
+            if (!csadev::slice_check(sl, size, &bytes)) return false;
+            L.slices.push_back(sl);
+            L.slice_bytes.push_back(bytes);
+        }
         for (const CSAFrag &f : it->second.frags) {
-            size = std::max(size, f.posfile + f.size);                     // (checked by dev_task_sizes)
             if (!f.size) continue;
+            if (L.sliced) {
+                if (csadev::slice_next(sl, f.posfile) >= f.posfile + f.size) continue;
+                L.touched_frags++;
+                if (!add_ok(L.touched_bytes, f.size, &L.touched_bytes)) return false;
+            }
             auto m = idmap.find(f.bid);
             if (m == idmap.end()) {
                 m = idmap.insert(std::make_pair((uint64_t)f.bid, L.tasks.size())).first;
@@ -92,6 +116,7 @@ bool dev_layout(const Index &index, const std::map<uint64_t, uint64_t> &raw, con
         uint64_t r;
         if (!add_ok(size, 15, &r) || !add_ok(off, r & ~15ull, &off)) return false;
     }
+    if (L.sliced && L.files.size() != nslices) return false;
     L.dst_bytes = off;
     std::sort(L.tasks.begin(), L.tasks.end(), [](const DevTask &a, const DevTask &b) {                        // csarc.cpp:430
         return a.total != b.total ? a.total > b.total : a.bid < b.bid;
@@ -180,13 +205,37 @@ struct FragTables {
         });
         return true;
     }
+    // CSAMI_DeviceReadSlices, in the place of add() and `pieces`: the fragment lies at [posfile, posfile + size) of an entry under the
+    // (checked) slice sl, and dst is the entry's packed destination, or NULL.  Each 16 KiB cell is classified (slice_reduce).
+    std::vector<csadev::SlicePiece> spieces;
+    bool add_sliced(const uint8_t *src, uint8_t *dst, const csadev::Slice &sl, uint64_t posfile, uint64_t size, uint32_t checksum,
+                    CSADevSliceStats &SL)
+    {
+        using namespace csadev;
+        const uint64_t np = piece_count(size, kFragPiece);
+        if (spieces.size() + np > 0x7FFFFFFFull) return false;
+        frags.push_back(FragFold{size, (uint32_t)spieces.size(), (uint32_t)np, checksum, 0});
+        piece_split(src, nullptr, size, kFragPiece, [&](uint64_t k, const CopyPiece &p) {
+            SlicePiece sp = {p.src, nullptr, p.len, 0, 0, 0, 0, 0};
+            SliceCut c;
+            const SliceKind kind = dst ? slice_reduce(sl, posfile + k * kFragPiece, p.len, c) : kSliceNone;
+            if (kind != kSliceNone) sp.dst = (uint8_t *)((uintptr_t)dst + c.dst);
+            if (kind == kSlicePeriodic) { sp.lo = c.lo; sp.hi = c.hi; sp.phase = c.phase; sp.run = c.run; sp.stride = c.stride; }
+            (kind == kSlicePeriodic ? SL.periodic_pieces : SL.plain_pieces)++;
+            spieces.push_back(sp);
+        });
+        return true;
+    }
     uint64_t upload_bytes() const { return pieces.size() * sizeof(csadev::CopyPiece) + frags.size() * sizeof(csadev::FragFold); }
     bool upload(bool compare = false)
     {
-        return d_pieces.upload(pieces.data(), pieces.size() * sizeof(csadev::CopyPiece)) && d_frags.upload(frags.data(), frags.size() * sizeof(csadev::FragFold))
-               && d_sums.alloc(pieces.size() * sizeof(csadev::PieceSums))
+        const size_t np = pieces.size() + spieces.size();                    // (one of the two tables is in use)
+        return (spieces.empty() ? d_pieces.upload(pieces.data(), pieces.size() * sizeof(csadev::CopyPiece))
+                                : d_pieces.upload(spieces.data(), spieces.size() * sizeof(csadev::SlicePiece)))
+               && d_frags.upload(frags.data(), frags.size() * sizeof(csadev::FragFold))
+               && d_sums.alloc(np * sizeof(csadev::PieceSums))
                && d_res.alloc(frags.size() * (compare ? sizeof(csadev::FragDiff) : sizeof(csadev::FragResult)))
-               && (!compare || d_firsts.alloc(pieces.size() * sizeof(uint32_t)));
+               && (!compare || d_firsts.alloc(np * sizeof(uint32_t)));
     }
     // k_frag_fold over the sums k_frag_pieces left, and the fragments' results read back: res.size() * sizeof(FragResult) bytes
     bool fold(DevTimer &tm, double *ms, uint64_t &launches, std::vector<csadev::FragResult> &res)
@@ -209,6 +258,7 @@ struct ReadBufs {
     uint8_t *const *ptrs = nullptr;            // per entry; NULL (the table, or an entry of it): verified only
     const uint64_t *lim = nullptr;             // compare: per entry, the bytes that are compared -- min(the entry's size, the caller's)
     CSADevDiff *diffs = nullptr;               // compare: per entry; first_diff, CSA_DIFF_BYTES and CSA_DIFF_SHORT are added here
+    CSADevSliceStats *slice_stats = nullptr;   // slices (a layout with L.sliced, never null there): ptrs[i] takes entry i's packed slice, and the piece counts are added here
     uint8_t *at(uint32_t file) const { return ptrs ? ptrs[file] : nullptr; }
 };
 
@@ -326,7 +376,9 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
                 if (n < want) B.diffs[f.file].status |= CSA_DIFF_SHORT;
             }
             if (!n) continue;
-            if (!T.add((const uint8_t *)d_raw.p + raw_off[k] + f.posblock, p ? p + f.posfile : nullptr, n, f.checksum, cmp)) return CSCMI_DEVICE_ERROR;
+            const uint8_t *src = (const uint8_t *)d_raw.p + raw_off[k] + f.posblock;
+            if (!(L.sliced ? T.add_sliced(src, p, L.slices[f.file], f.posfile, n, f.checksum, *B.slice_stats)
+                           : T.add(src, p ? p + f.posfile : nullptr, n, f.checksum, cmp))) return CSCMI_DEVICE_ERROR;
             ff_file.push_back(f.file);
             ff_posfile.push_back(f.posfile);
             store = store || p;
@@ -349,7 +401,9 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
         }
     } else {
         if (!T.upload()
-            || !tm.timed(&A.kernel_ms[1], S.launches, [&] { launch_frag_pieces(T.d_pieces.p, T.d_sums.p, (uint32_t)T.pieces.size(), store, tm.st); })
+            || !tm.timed(&A.kernel_ms[1], S.launches, [&] {
+                   if (L.sliced) launch_frag_slices(T.d_pieces.p, T.d_sums.p, (uint32_t)T.spieces.size(), tm.st);
+                   else launch_frag_pieces(T.d_pieces.p, T.d_sums.p, (uint32_t)T.pieces.size(), store, tm.st); })
             || !T.fold(tm, &A.kernel_ms[2], S.launches, res)) return CSCMI_DEVICE_ERROR;
         S.readback_bytes += res.size() * sizeof(FragResult);
     }
@@ -422,7 +476,16 @@ int CSAMI_DevicePlan(CSADevArchive *a, const char *const *names, int nnames,
 
 namespace {
 
-// The one read path below CSAMI_DeviceReadInto, CSAMI_DeviceCompare, CSAMI_DeviceRead and CSAMI_DeviceReadStop: the address checks,
+// false where CSAMI_CheckBuffers refuses the caller's buffers: sizes[i] bytes at B.ptrs[i], nothing where that is NULL
+bool dev_bufs_ok(const CSADevArchive *a, const DevLayout &L, const ReadBufs &B, const uint64_t *sizes, bool disjoint)
+{
+    if (!B.ptrs) return true;
+    std::vector<uint64_t> touched(L.files.size());
+    for (size_t i = 0; i < L.files.size(); i++) touched[i] = B.ptrs[i] ? sizes[i] : 0;
+    return CSAMI_CheckBuffers((const void *const *)B.ptrs, touched.data(), (uint32_t)L.files.size(), a->arc, a->arc_size, disjoint, nullptr) == 0;
+}
+
+// The one read path below CSAMI_DeviceReadInto, CSAMI_DeviceReadSlices, CSAMI_DeviceCompare, CSAMI_DeviceRead and CSAMI_DeviceReadStop: the address checks,
 // then the waves.  sizes[i] are the bytes of B.ptrs[i] that may be touched (ignored where that is NULL); `disjoint`: they are
 // written, so no two may overlap.  ss: stop every task behind its last selected byte, and add to *ss.  `failed` gets one count per
 // entry.  -1 with nothing launched where CSAMI_CheckBuffers refuses the buffers.
@@ -431,12 +494,7 @@ int dev_read_run(CSADevArchive *a, const DevLayout &L, const ReadBufs &B, const 
 {
     const double t0 = now_s();
     failed.assign(L.files.size(), 0);
-    if (B.ptrs) {
-        std::vector<uint64_t> touched(L.files.size());
-        for (size_t i = 0; i < L.files.size(); i++) touched[i] = B.ptrs[i] ? sizes[i] : 0;
-        if (CSAMI_CheckBuffers((const void *const *)B.ptrs, touched.data(), (uint32_t)L.files.size(), a->arc, a->arc_size, disjoint, nullptr) != 0)
-            return -1;
-    }
+    if (!dev_bufs_ok(a, L, B, sizes, disjoint)) return -1;
     CSAOptions o;
     if (opt) o = *opt; else CSA_OptionsInit(&o);
     a->kernel_ms[0] = a->kernel_ms[1] = a->kernel_ms[2] = 0;
@@ -620,6 +678,43 @@ int CSAMI_DeviceCompare(CSADevArchive *a, const char *const *names, int nnames, 
     return rc;
 }
 
+int CSAMI_DeviceReadSlices(CSADevArchive *a, const char *const *names, int nnames, const CSADevSlice *slices, void *const *ptrs,
+                           const uint64_t *caps, uint32_t n, uint32_t flags, const CSAOptions *opt, CSADevFile *files, CSADevReadStats *st,
+                           CSADevStopStats *stop_stats, CSADevSliceStats *slice_stats)
+{
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;               // (before anything of the caller's is touched)
+    if (st) memset(st, 0, sizeof(*st));
+    if (stop_stats) memset(stop_stats, 0, sizeof(*stop_stats));
+    if (slice_stats) memset(slice_stats, 0, sizeof(*slice_stats));
+    static const CSADevSlice kNone = {0, 0, 0, 0};
+    DevLayout L;
+    if (!a || (n && !slices) || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L, slices ? slices : &kNone, n)) return -1;
+    dev_fill_files(L, files, n);
+    for (uint32_t i = 0; files && i < n; i++) files[i].offset = 0;
+    CSADevSliceStats SL;
+    memset(&SL, 0, sizeof(SL));
+    SL.touched_bytes = L.touched_bytes;
+    for (uint32_t i = 0; i < n; i++) {
+        if (ptrs && ptrs[i] && (!caps || caps[i] < L.slice_bytes[i])) return WRITE_ERROR;
+        if (!add_ok(SL.selected_bytes, L.slice_bytes[i], &SL.selected_bytes)) return -1;
+    }
+    ReadBufs B;
+    B.ptrs = (uint8_t *const *)ptrs;
+    B.slice_stats = &SL;
+    CSADevReadStats S;
+    CSADevStopStats SS;
+    memset(&S, 0, sizeof(S));
+    memset(&SS, 0, sizeof(SS));
+    std::vector<uint32_t> failed;
+    if (!dev_bufs_ok(a, L, B, L.slice_bytes.data(), true)) return -1;      // (here too, so that a refusal leaves *slice_stats zeroed)
+    const int rc = dev_read_run(a, L, B, L.slice_bytes.data(), true, opt, failed, S, (flags & CSAMI_DEV_STOP_EARLY) ? &SS : nullptr);
+    for (uint32_t i = 0; files && i < n; i++) files[i].failed_frags = failed[i];
+    if (st) *st = S;
+    if (stop_stats) *stop_stats = SS;
+    if (slice_stats) *slice_stats = SL;
+    return rc;
+}
+
 void CSAMI_DeviceKernelMs(const CSADevArchive *a, double ms[3])
 {
     for (int i = 0; i < 3; i++) ms[i] = a ? a->kernel_ms[i] : 0;
@@ -634,7 +729,7 @@ namespace {
 // the strict host-only plan of CSAMI_PlanDeviceLayout / CSAMI_PlanDeviceStops: false for an index that does not parse, whose sizes
 // wrap, or with an archive block outside [0, arc_size).  L.files point into `index`.
 bool dev_plan_strict(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
-                     Index &index, DevLayout &L)
+                     Index &index, DevLayout &L, const CSADevSlice *slices = nullptr, size_t nslices = 0)
 {
     BlockIndex abindex;
     std::map<uint64_t, uint64_t> raw;
@@ -644,7 +739,21 @@ bool dev_plan_strict(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_s
             uint64_t end;
             if (!add_ok(x.off, x.size, &end) || end > arc_size) return false;
         }
-    return dev_layout(index, raw, make_selection(names, nnames), L);
+    return dev_layout(index, raw, make_selection(names, nnames), L, slices, nslices);
+}
+
+// what CSAMI_PlanDeviceStops and CSAMI_PlanDeviceSlices hand out of a layout; -1 for a task whose stop cannot be
+int dev_fill_stops(const DevLayout &L, uint64_t *bids, uint64_t *stops, uint64_t *raws, uint32_t cap, uint32_t *n_tasks)
+{
+    for (const DevTask &t : L.tasks)
+        if (t.stop == 0 || t.stop > t.raw) return -1;                       // (a selected fragment past its task: cannot be, by construction)
+    for (size_t i = 0; i < L.tasks.size() && i < cap; i++) {
+        if (bids) bids[i] = L.tasks[i].bid;
+        if (stops) stops[i] = L.tasks[i].stop;
+        if (raws) raws[i] = L.tasks[i].raw;
+    }
+    if (n_tasks) *n_tasks = (uint32_t)L.tasks.size();
+    return 0;
 }
 
 }   // namespace
@@ -683,15 +792,19 @@ int CSAMI_PlanDeviceStops(const uint8_t *raw_index, uint64_t raw_size, uint64_t 
     Index index;
     DevLayout L;
     if (!dev_plan_strict(raw_index, raw_size, arc_size, names, nnames, index, L)) return -1;
-    for (const DevTask &t : L.tasks)
-        if (t.stop == 0 || t.stop > t.raw) return -1;                       // (a selected fragment past its task: cannot be, by construction)
-    for (size_t i = 0; i < L.tasks.size() && i < cap; i++) {
-        if (bids) bids[i] = L.tasks[i].bid;
-        if (stops) stops[i] = L.tasks[i].stop;
-        if (raws) raws[i] = L.tasks[i].raw;
-    }
-    if (n_tasks) *n_tasks = (uint32_t)L.tasks.size();
-    return 0;
+    return dev_fill_stops(L, bids, stops, raws, cap, n_tasks);
+}
+
+int CSAMI_PlanDeviceSlices(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
+                           const CSADevSlice *slices, uint32_t n, uint64_t *bids, uint64_t *stops, uint64_t *raws, uint32_t cap,
+                           uint32_t *n_tasks, uint32_t *n_touched)
+{
+    static const CSADevSlice kNone = {0, 0, 0, 0};
+    Index index;
+    DevLayout L;
+    if ((n && !slices) || !dev_plan_strict(raw_index, raw_size, arc_size, names, nnames, index, L, slices ? slices : &kNone, n)) return -1;
+    if (n_touched) *n_touched = (uint32_t)L.touched_frags;
+    return dev_fill_stops(L, bids, stops, raws, cap, n_tasks);
 }
 
 }   // extern "C"

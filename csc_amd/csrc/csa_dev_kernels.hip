@@ -14,6 +14,8 @@
 //   k_frag_compare        k_frag_pieces<true> for CSAMI_DeviceCompare: the piece against the caller's bytes instead of onto them --
 //                         two loads in the place of a load and a store -- and the first differing index beside the sums
 //   k_frag_fold_diff      k_frag_fold, and the fragment's first differing offset from its pieces'
+//   k_frag_slices         k_frag_pieces<true> for CSAMI_DeviceReadSlices: a piece is still summed whole, and the bytes of it that its
+//                         entry's slice selects -- all, none, or the runs of a periodic pattern -- go to their packed places
 //   k_block_table         one lane per task stream of a wave (write only): the archive-block table AsyncWriter would have made of
 //                         the encoder's Write calls (csa_io.h:145-201), read off the stream's framing (csa_dev_write.h)
 //
@@ -87,6 +89,32 @@ __global__ __launch_bounds__(kThreads) void k_frag_compare(const CopyPiece *piec
     }
 }
 
+// k_frag_pieces<true> for CSAMI_DeviceReadSlices: a piece that lies inside one run of its entry's slice, or holds no selected byte, is
+// copy_sum's as there; any other is summed whole and stored in part (slice_sum, csa_dev_read.h).  Which of the three: the same for
+// the whole workgroup.
+__global__ __launch_bounds__(kThreads) void k_frag_slices(const SlicePiece *pieces, PieceSums *out, uint32_t npieces)
+{
+    if (blockIdx.x >= npieces) return;
+    const SlicePiece pc = pieces[blockIdx.x];
+    uint64_t a = 0, b = 0;
+    if (pc.stride) slice_sum(pc, threadIdx.x, kThreads, a, b);
+    else if (pc.dst == nullptr) copy_sum<false, true>(nullptr, pc.src, pc.len, threadIdx.x, kThreads, a, b);
+    else copy_sum<true, true>(pc.dst, pc.src, pc.len, threadIdx.x, kThreads, a, b);
+    for (int off = 32; off > 0; off >>= 1) {
+        a += __shfl_down(a, off, 64);
+        b += __shfl_down(b, off, 64);
+    }
+    __shared__ uint64_t red[2 * (kThreads / 64)];
+    const uint32_t wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[2 * wave] = a; red[2 * wave + 1] = b; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        PieceSums s = {0, 0};
+        for (uint32_t w = 0; w < kThreads / 64; w++) { s.a += red[2 * w]; s.b += red[2 * w + 1]; }
+        out[blockIdx.x] = s;
+    }
+}
+
 __global__ __launch_bounds__(kThreads) void k_frag_fold(const FragFold *frags, const PieceSums *sums, FragResult *out, uint32_t nfrags)
 {
     const uint32_t i = blockIdx.x * kThreads + threadIdx.x;
@@ -129,6 +157,11 @@ void launch_frag_pieces(const void *pieces, void *sums, uint32_t npieces, bool s
 void launch_frag_compare(const void *pieces, void *sums, void *firsts, uint32_t npieces, hipStream_t st)
 {
     hipLaunchKernelGGL(k_frag_compare, dim3(npieces ? npieces : 1), dim3(kThreads), 0, st, (const CopyPiece *)pieces, (PieceSums *)sums, (uint32_t *)firsts, npieces);
+}
+
+void launch_frag_slices(const void *pieces, void *sums, uint32_t npieces, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_frag_slices, dim3(npieces ? npieces : 1), dim3(kThreads), 0, st, (const SlicePiece *)pieces, (PieceSums *)sums, npieces);
 }
 
 void launch_frag_fold(const void *frags, const void *sums, void *out, uint32_t nfrags, hipStream_t st)

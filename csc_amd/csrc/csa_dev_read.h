@@ -16,6 +16,9 @@
 // fragment's piece and the caller's range side by side, compare_piece joins a compared front and a summed rest into one piece's sums,
 // fold_first folds the pieces' first differences (tests/model/csa_dev_compare_model.cpp is their model).
 //
+// CSAMI_DeviceReadSlices runs them with k_frag_slices in the middle: slice_check / slice_next / slice_reduce are its planner's,
+// slice_sum the piece that is summed whole and stored in part (tests/model/csa_dev_slice_model.cpp is their model).
+//
 // The template parameter PLANT switches one deliberate mistake on (0: none).  The product instantiates 0 only; the models run each
 // of the others and have to see it caught by a named case.
 #pragma once
@@ -37,7 +40,9 @@ constexpr uint32_t kAdlerBase = 65521;
 enum Plant {
     kPlantNone = 0, kPlantTailDropped = 1, kPlantWeightOffByOne = 2, kPlantFoldLastLen = 3, kPlantHeadWrongPointer = 4,
     // compare_sum and fold_first (tests/model/csa_dev_compare_model.cpp)
-    kPlantCmpHeadNotCompared = 5, kPlantCmpUnitWithoutHead = 6, kPlantCmpWindowPastEnd = 7, kPlantFirstPieceIndex = 8
+    kPlantCmpHeadNotCompared = 5, kPlantCmpUnitWithoutHead = 6, kPlantCmpWindowPastEnd = 7, kPlantFirstPieceIndex = 8,
+    // slice_sum (tests/model/csa_dev_slice_model.cpp)
+    kPlantSliceBorderLate = 9, kPlantSlicePhaseDropped = 10, kPlantSliceStraddleWhole = 11, kPlantSliceRowNotAdvanced = 12
 };
 
 struct CopyPiece {         // one workgroup of k_gather_extents / k_frag_pieces / k_frag_compare
@@ -229,6 +234,162 @@ CSADEV_FHD void compare_piece(const uint8_t *x, const uint8_t *y, uint32_t len, 
         if (f < cmp) first = f;
     }
     if (cmp < len) copy_sum<false, true>(nullptr, x + cmp, len - cmp, tid, nthreads, a, b);
+}
+
+// ---- slices of an entry (CSAMI_DeviceReadSlices): a piece that is summed whole and stored in part ----
+//
+// A slice selects the bytes [offset + k * stride, offset + k * stride + run), k < count, of an entry and delivers them packed, row
+// after row.  The pieces of a fragment stay on the fixed kFragPiece grid (fold_pieces needs it), so a piece may hold the tail of one
+// run, a gap and the head of the next -- or, where run and stride are small, many of them.  slice_check, slice_next and slice_reduce
+// are the host planner's; slice_sum is the workgroup's.
+
+struct Slice { uint64_t offset, run, stride, count; };     // CSADevSlice of include/csa_mi355x.h
+
+// What the read refuses in a slice of an entry of `size` bytes: false.  count == 1 gets stride = run; *bytes = run * count.
+CSADEV_FHD bool slice_check(Slice &s, uint64_t size, uint64_t *bytes)
+{
+    *bytes = 0;
+    if (!s.count) return true;
+    if (!s.run) return false;
+    if (s.count == 1) s.stride = s.run;
+    if (s.stride < s.run) return false;
+    uint64_t span, end;
+    if (__builtin_mul_overflow(s.count - 1, s.stride, &span) || __builtin_add_overflow(span, s.run, &span)
+        || __builtin_add_overflow(s.offset, span, &end) || end > size) return false;
+    *bytes = s.run * s.count;                                         // (<= span, as run <= stride)
+    return true;
+}
+
+// The first selected offset at or behind x of a checked slice, UINT64_MAX if there is none: one division, no walk over the rows.
+// [x, y) holds a selected byte exactly when slice_next(s, x) < y.
+CSADEV_FHD uint64_t slice_next(const Slice &s, uint64_t x)
+{
+    if (!s.count) return UINT64_MAX;
+    if (x <= s.offset) return s.offset;
+    const uint64_t t = x - s.offset, k = t / s.stride, r = t - k * s.stride;
+    if (k >= s.count) return UINT64_MAX;
+    if (r < s.run) return x;
+    return k + 1 < s.count ? s.offset + (k + 1) * s.stride : UINT64_MAX;
+}
+
+struct SlicePiece {        // one workgroup of k_frag_slices: 32-bit quantities and two addresses, whatever the slice's 64-bit ones are
+    const uint8_t *src;
+    uint8_t *dst;          // stride == 0: the piece's one contiguous destination, NULL = summed, not stored (copy_sum, as a CopyPiece);
+                           // else the address period position 0 would be stored to (it may lie in front of the caller's range: never stored to)
+    uint32_t len;          // <= kFragPiece
+    uint32_t lo, hi;       // periodic: only the piece's bytes [lo, hi) can be selected (the slice's hull cut to the piece)
+    uint32_t phase;        // periodic: byte i of the piece stands at pos = phase + i; row = pos / stride, r = pos % stride; it is
+    uint32_t run, stride;  //           selected when lo <= i < hi and r < run, and is stored to dst + row * run + r
+};
+
+enum SliceKind { kSliceNone = 0, kSliceWhole = 1, kSlicePeriodic = 2 };
+struct SliceCut { uint32_t lo, hi, phase, run, stride; uint64_t dst; };
+
+// The piece [at, at + len) of the entry, len <= kFragPiece, under a checked slice:
+//   kSliceNone      it holds no selected byte
+//   kSliceWhole     it lies inside one run; its bytes go to packed offset c.dst
+//   kSlicePeriodic  anything else: c is the SlicePiece's lo, hi, phase, run, stride, and c.dst the packed offset of period position 0
+//                   (modulo 2^64: it may stand for an offset below 0)
+// A piece sees at most kFragPiece consecutive bytes, so whatever run and stride are it sees the same as under a pattern whose run is
+// cut to kFragPiece -- the run it begins in from its front, since what lies before the piece is not seen, the next one from its
+// back -- and whose gap is cut to kFragPiece likewise: stride' <= 2 * kFragPiece, and phase + len < 2^16.  Patterns that fit are left
+// as they are (run' = run, stride' = stride).
+CSADEV_FHD SliceKind slice_reduce(const Slice &s, uint64_t at, uint32_t len, SliceCut &c)
+{
+    c = SliceCut{0, 0, 0, 0, 0, 0};
+    if (!s.count || !len) return kSliceNone;
+    const uint64_t hull_hi = s.offset + (s.count - 1) * s.stride + s.run;            // (checked by slice_check)
+    const uint64_t x0 = at > s.offset ? at : s.offset, x1 = at + len < hull_hi ? at + len : hull_hi;
+    if (x0 >= x1 || slice_next(s, x0) >= x1) return kSliceNone;
+    const uint64_t t = x0 - s.offset, k0 = t / s.stride, r0 = t - k0 * s.stride;
+    if (x0 == at && x1 == at + len && r0 < s.run && s.run - r0 >= len) {
+        c.dst = k0 * s.run + r0;
+        return kSliceWhole;
+    }
+    const uint64_t gap = s.stride - s.run;
+    const uint32_t R = (uint32_t)(s.run < kFragPiece ? s.run : kFragPiece), G = (uint32_t)(gap < kFragPiece ? gap : kFragPiece);
+    uint32_t ph;                                                                      // the period position of x0
+    uint64_t d;
+    if (r0 < s.run) {                                     // in a run, `left` bytes from its end
+        const uint64_t left = s.run - r0;
+        ph = R - (uint32_t)(left < R ? left : R);
+        d = k0 * s.run + r0 - ph;
+    } else {                                              // in the gap, `left` bytes from the next run
+        const uint64_t left = s.stride - r0;
+        ph = R + G - (uint32_t)(left < G ? left : G);
+        d = (k0 + 1) * s.run - R;
+    }
+    c.lo = (uint32_t)(x0 - at);
+    c.hi = (uint32_t)(x1 - at);
+    c.run = R;
+    c.stride = R + G;
+    // x0 is the piece's byte lo; the pattern is carried back to its byte 0 over whole periods
+    const uint32_t back = c.lo > ph ? (c.lo - ph + c.stride - 1) / c.stride : 0;
+    c.phase = ph + back * c.stride - c.lo;
+    c.dst = d - (uint64_t)back * R;
+    return kSlicePeriodic;
+}
+
+// Thread `tid` of `nthreads`: its share of a periodic piece.  Every byte of src[0, len) is loaded once -- the anchor is src, as x is in
+// compare_sum: head and tail bytes one by one, between them aligned 16-byte units, so no window leaves src[0, len) -- and summed into a, b as one piece of len bytes, so the sums
+// are copy_sum<false, true>'s; the selected bytes are stored to their packed places and nothing else is stored.  A unit that lies
+// inside one run goes out as 16 bytes -- one store, four, or sixteen, as its destination's alignment allows; any other unit that
+// meets [lo, hi) goes out byte by byte under the predicate.  No division in the unit loop: a thread's (row, r) advances by the
+// workgroup's step, 16 * nthreads positions, with one carry.
+template <int PLANT = kPlantNone>
+CSADEV_FHD void slice_sum(const SlicePiece &pc, uint32_t tid, uint32_t nthreads, uint64_t &a, uint64_t &b)
+{
+    const uint8_t *src = pc.src;
+    const uintptr_t d0 = (uintptr_t)pc.dst;
+    const uint32_t n = pc.len, lo = pc.lo, hi = pc.hi, run = pc.run, stride = pc.stride;
+    uint32_t head = (0u - (uint32_t)(uintptr_t)src) & 15u;
+    if (head > n) head = n;
+    const uint32_t units = (n - head) >> 4, tail = (n - head) & 15u;
+    const uint32_t border = PLANT == kPlantSliceBorderLate ? run + 1 : run;          // r < border: selected
+    auto one = [&](uint32_t idx) {
+        const uint32_t v = src[idx];
+        a += v;
+        b += (uint64_t)(n - idx) * v;
+        if (idx >= lo && idx < hi) {
+            const uint32_t pos = pc.phase + idx, row = pos / stride, r = pos - row * stride;
+            if (r < border) *(uint8_t *)(d0 + row * run + r) = (uint8_t)v;
+        }
+    };
+    if (tid < head) one(tid);
+    if (nthreads - 1 - tid < tail) one(head + 16 * units + (nthreads - 1 - tid));
+    if (tid >= units) return;
+    const uint32_t step = 16 * nthreads, srow = step / stride, sr = step - srow * stride;
+    const uint32_t pos = (PLANT == kPlantSlicePhaseDropped ? 0u : pc.phase) + head + 16 * tid;
+    uint32_t row = pos / stride, r = pos - row * stride;
+    for (uint32_t i = tid; i < units; i += nthreads) {
+        const uint32_t i0 = head + 16 * i;
+        const Vec16 o = *(const Vec16 *)(src + i0);                   // (aligned: the anchor is src, so load_unit has no window to shift)
+        sum_word(o.w[0], i0, n, a, b);
+        sum_word(o.w[1], i0 + 4, n, a, b);
+        sum_word(o.w[2], i0 + 8, n, a, b);
+        sum_word(o.w[3], i0 + 12, n, a, b);
+        if (i0 < hi && i0 + 16 > lo) {
+            if (i0 >= lo && i0 + 16 <= hi && (PLANT == kPlantSliceStraddleWhole ? r < run : r + 16 <= run)) {
+                const uintptr_t d = d0 + row * run + r;
+                if (!(d & 15u)) {
+                    *(Vec16 *)d = o;
+                } else if (!(d & 3u)) {
+                    for (uint32_t j = 0; j < 4; j++) ((uint32_t *)d)[j] = o.w[j];
+                } else {
+                    for (uint32_t j = 0; j < 16; j++) ((uint8_t *)d)[j] = (uint8_t)(o.w[j >> 2] >> (8 * (j & 3u)));
+                }
+            } else {
+                uint32_t row1 = row, r1 = r;
+                for (uint32_t j = 0; j < 16; j++) {
+                    if (i0 + j >= lo && i0 + j < hi && r1 < border) *(uint8_t *)(d0 + row1 * run + r1) = (uint8_t)(o.w[j >> 2] >> (8 * (j & 3u)));
+                    if (++r1 == stride) { r1 = 0; row1++; }
+                }
+            }
+        }
+        r += sr;
+        row += srow;
+        if (r >= stride) { r -= stride; if (PLANT != kPlantSliceRowNotAdvanced) row++; }
+    }
 }
 
 // The first differing offset of a fragment of `size` delivered bytes from its pieces' `first` values (first(k): piece k's, its

@@ -12,11 +12,12 @@
 #include "../../include/csc_mi355x.h"
 #include "../../include/csa_mi355x.h"
 
-// csa_dev_kernels.hip.  launch_gather_extents, launch_frag_pieces / _compare and launch_frag_fold / _fold_diff launch even for an
-// empty table (one workgroup that returns at once).
+// csa_dev_kernels.hip.  launch_gather_extents, launch_frag_pieces / _compare / _slices and launch_frag_fold / _fold_diff launch even
+// for an empty table (one workgroup that returns at once).
 void launch_gather_extents(const void *pieces, uint32_t npieces, hipStream_t st);
 void launch_frag_pieces(const void *pieces, void *sums, uint32_t npieces, bool store, hipStream_t st);
 void launch_frag_compare(const void *pieces, void *sums, void *firsts, uint32_t npieces, hipStream_t st);
+void launch_frag_slices(const void *pieces, void *sums, uint32_t npieces, hipStream_t st);
 void launch_frag_fold(const void *frags, const void *sums, void *out, uint32_t nfrags, hipStream_t st);
 void launch_frag_fold_diff(const void *frags, const void *sums, const void *firsts, void *out, uint32_t nfrags, hipStream_t st);
 void launch_block_table(const void *jobs, uint32_t njobs, void *scratch, void *res, void *sizes, hipStream_t st);

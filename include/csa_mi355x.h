@@ -237,8 +237,9 @@ int CSAMI_DeviceRead(CSADevArchive *a, const char *const *names, int nnames, voi
  * Unchanged: a fragment is clipped to what was produced and verified only if a byte of it was delivered; st->launches ==
  * 3 * st->waves; the read-back bound; and the gather: a task stream of more than one archive block is still copied WHOLE, because
  * how many coded bytes a prefix of the raw bytes needs is not known before it is decoded.
- * Out of scope: stopping inside a run (the granularity is one run, at most raw_blocksize = 2 MiB by default), byte ranges inside
- * an entry, gathering part of a multi-block stream, and the host paths (CSA_Extract / CSA_Test), which stop as they did.
+ * Out of scope: stopping inside a run (the granularity is one run, at most raw_blocksize = 2 MiB by default), gathering part of a
+ * multi-block stream, and the host paths (CSA_Extract / CSA_Test), which stop as they did.  The unit of selection here is the whole
+ * entry; byte ranges and strided slices inside an entry are CSAMI_DeviceReadSlices' (below).
  * Without a visible device CSCMI_DEVICE_ERROR is returned and nothing of the caller's is touched. */
 typedef struct CSADevStopStats {
     uint64_t decoded_bytes;     /* sum of the decode jobs' `produced`: the sum of the tasks' stops where every stream is intact */
@@ -400,6 +401,59 @@ typedef struct CSADevDiff { uint64_t first_diff; uint32_t status; uint32_t faile
 int CSAMI_DeviceCompare(CSADevArchive *a, const char *const *names, int nnames, const void *const *ptrs, const uint64_t *sizes, uint32_t n,
                         uint32_t flags, const CSAOptions *o, CSADevFile *files, CSADevDiff *diffs, CSADevReadStats *st,
                         CSADevStopStats *stop_stats);
+
+/* ---- byte ranges and strided slices of entries: a read that costs what it selects INSIDE an entry; not in the reference ----
+ *
+ * Of an entry of `size` bytes (the size CSAMI_DevicePlan lists) a slice selects the bytes [offset + k * stride, offset + k * stride +
+ * run) for k < count, and they are delivered packed, row after row, into ptrs[i][0, run * count): a block of rows of a row-major
+ * matrix is count == 1 (a byte range; stride is ignored then), a block of columns is one run out of every row.  count == 0 selects
+ * nothing: the entry is neither decoded, summed nor verified, and run is ignored.
+ * A slice is refused (-1, nothing launched, *st zeroed) for count > 0 with run == 0; count > 1 with stride < run (stride == run is
+ * allowed); any product or sum that wraps in 64 bits; a last selected byte at or behind `size` -- a slice lies inside its entry and is
+ * not clipped.
+ *
+ * Which tasks, how far, what is verified.  A fragment is TOUCHED when at least one selected byte lies in [posfile, posfile + size) --
+ * decided with one division a fragment, not by walking rows.  A task is decoded when it holds a touched fragment of non-zero size;
+ * without CSAMI_DEV_STOP_EARLY to its raw size, with it to stop = max(posblock + size) over its TOUCHED fragments, exactly as
+ * CSAMI_DeviceReadStop stops a task (scratch `stop` rounded up to 256, wave sizing at `stop`).  Every touched fragment is summed
+ * WHOLE and checked against the index, so no byte is delivered from a fragment whose adler32 was not taken, and a stop never falls
+ * inside a touched fragment.  Untouched fragments are neither summed nor verified, even where they lie in front of a stop and are
+ * decoded on the way.  st->tasks, st->frags and st->raw_bytes count the decoded tasks and their touched fragments; tasks go largest
+ * sum of touched fragment sizes first, equal sums by bid.  The return value, failed_frags, st->verify_failures, the clipping of a
+ * fragment to what its task produced, "verified only if a byte of it was delivered", st->launches == 3 * st->waves and the read-back
+ * bound: as documented at CSAMI_DeviceReadInto.  Bytes of a destination that no delivered fragment covers stay untouched.
+ *
+ * A wave is three launches: k_gather_extents, k_frag_slices, k_frag_fold.  The pieces of a fragment stay on its fixed 16 KiB grid.
+ * A piece that lies inside one run is stored whole and one without a selected byte is summed only, both as k_frag_pieces does it
+ * (slice_stats->plain_pieces); any other piece (periodic_pieces) is summed whole and stored in part: every source byte loaded once,
+ * a 16-byte unit inside one run stored as 16 bytes, a unit across a run border byte by byte.  Its table entry holds 32-bit
+ * quantities whatever run and stride are.  Nothing outside a fragment's decoded bytes is loaded, not even by an aligned 16-byte
+ * window, and nothing but the selected bytes' destinations is stored.
+ * Out of scope: stopping inside a fragment, CSAMI_DeviceCompare against a slice, writing or updating a slice, and the host paths
+ * (CSA_Extract / CSA_Test). */
+typedef struct CSADevSlice { uint64_t offset, run, stride, count; } CSADevSlice;
+typedef struct CSADevSliceStats {
+    uint64_t selected_bytes;    /* sum of run * count over the entries */
+    uint64_t touched_bytes;     /* sum of the touched fragments' sizes: what is summed where every task delivers its bytes */
+    uint64_t periodic_pieces;   /* pieces summed whole and stored in part */
+    uint64_t plain_pieces;      /* pieces stored whole or summed only */
+} CSADevSliceStats;
+/* Arguments as CSAMI_DeviceReadInto, with slices[i] for entry i of the selection in CSAMI_DevicePlan's order.  n must be that plan's
+ * *n_files, and slices == NULL with n > 0 is refused: -1.  ptrs[i] == NULL (or ptrs == NULL: all of them): the touched fragments are
+ * verified only.  WRITE_ERROR for a non-NULL ptrs[i] with caps[i] < run * count; -1 for what CSAMI_CheckBuffers(ptrs, run * count, n,
+ * arc, arc_size, 1) refuses; all refusals with nothing launched and *st, *stop_stats and *slice_stats (each may be NULL) zeroed.
+ * files[i].size is the entry's size, not the slice's.  CSAMI_DeviceKernelMs: [1] is k_frag_slices.  Without a visible device
+ * CSCMI_DEVICE_ERROR is returned and nothing of the caller's is touched; that refusal comes before the handle is looked at. */
+int CSAMI_DeviceReadSlices(CSADevArchive *a, const char *const *names, int nnames, const CSADevSlice *slices, void *const *ptrs,
+                           const uint64_t *caps, uint32_t n, uint32_t flags, const CSAOptions *o, CSADevFile *files, CSADevReadStats *st,
+                           CSADevStopStats *stop_stats, CSADevSliceStats *slice_stats);
+/* host only, no GPU: the tasks CSAMI_DeviceReadSlices decodes for this selection and these slices (n of them, one per selected entry,
+ * else -1), in the order it decodes them, with the strictness and the outputs of CSAMI_PlanDeviceStops: stops[i] is the task's stop
+ * under CSAMI_DEV_STOP_EARLY.  *n_touched (may be NULL) is the number of touched fragments.  -1 also for what the read refuses in a
+ * slice. */
+int CSAMI_PlanDeviceSlices(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
+                           const CSADevSlice *slices, uint32_t n, uint64_t *bids, uint64_t *stops, uint64_t *raws, uint32_t cap,
+                           uint32_t *n_tasks, uint32_t *n_touched);
 
 /* YYYYMMDDHHMMSS <-> time_t, csa_common.cpp:3-39 */
 int64_t CSA_DecimalTime(int64_t unix_seconds);
