@@ -87,6 +87,14 @@ class CSADevSliceStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CSADevGatherStats(C.Structure):
+    _fields_ = [("selected_bytes", C.c_uint64), ("hull_bytes", C.c_uint64), ("periodic_pieces", C.c_uint64), ("plain_pieces", C.c_uint64),
+                ("gathered_tasks", C.c_uint64), ("inplace_tasks", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 LIST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(CSAFrag))
 
 SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", "CSA_ReadIndex",
@@ -96,7 +104,7 @@ SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", 
            "CSAMI_DeviceReadStop", "CSAMI_PlanDeviceStops",
            "CSAMI_DeviceWritePlan", "CSAMI_DeviceWrite", "CSAMI_DeviceWriteKernelMs",
            "CSAMI_CheckBuffers", "CSAMI_DeviceWriteFrom", "CSAMI_DeviceReadInto", "CSAMI_DeviceCompare",
-           "CSAMI_DeviceReadSlices", "CSAMI_PlanDeviceSlices"]
+           "CSAMI_DeviceReadSlices", "CSAMI_PlanDeviceSlices", "CSAMI_DeviceWriteSlices"]
 
 CSA_MAX_FRAGMENTS = 127
 CSA_TOO_MANY_FRAGMENTS = -94
@@ -191,6 +199,8 @@ def lib():
         L.CSAMI_PlanDeviceSlices.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, names, C.c_int, slices, C.c_uint32, u64s, u64s, u64s, C.c_uint32,
                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.CSAMI_PlanDeviceSlices.restype = C.c_int
+        L.CSAMI_DeviceWriteSlices.argtypes = [ptrs, u64s, slices] + L.CSAMI_DeviceWrite.argtypes[2:] + [C.POINTER(CSADevGatherStats)]
+        L.CSAMI_DeviceWriteSlices.restype = C.c_int
         _lib = L
     return _lib
 
@@ -384,6 +394,39 @@ def rows_slice(row_bytes: int, r0: int, r1: int, c0: int = 0, c1: Optional[int] 
     return (r0 * row_bytes + c0, c1 - c0, row_bytes, r1 - r0)
 
 
+def tensor_slice(t):
+    """a torch tensor of any dtype whose layout is count rows of run contiguous bytes a constant stride apart -- a contiguous tensor, a
+    block of columns t2d[:, c0:c1], or more dimensions that collapse to that -- as (1-d uint8 view of its WHOLE storage, slice): the
+    slice's packed bytes are t.contiguous()'s bytes.  ValueError for any other layout (a negative or zero stride with more than one
+    element along it, rows that overlap, a third level of striding).  write_slices takes the pair as an entry's tensor and slice."""
+    import torch
+    if not isinstance(t, torch.Tensor):
+        raise TypeError("a torch tensor")
+    item = t.element_size()
+    base = torch.empty(0, dtype=torch.uint8, device=t.device).set_(t.untyped_storage())
+    offset = t.storage_offset() * item
+    if t.numel() == 0:
+        return base, (offset, 0, 0, 0)
+    # the dimensions that count, innermost first, in bytes; neighbours that continue each other collapse into one
+    dims = [(item, 1)]                                             # (extent in bytes, stride in bytes): the element itself
+    for n, st in zip(reversed(t.shape), reversed(t.stride())):
+        if n == 1:
+            continue
+        if st <= 0:
+            raise ValueError("a dimension with a stride that is not positive")
+        ext, step = dims[-1]
+        if st * item == ext * step:
+            dims[-1] = (ext * n, step)
+        else:
+            dims.append((n, st * item))
+    run = dims[0][0]                                               # (dims[0] has step 1: contiguous bytes)
+    if len(dims) == 1:
+        return base, (offset, run, run, 1)
+    if len(dims) > 2 or dims[1][1] < run:
+        raise ValueError("not rows of contiguous bytes a constant stride apart")
+    return base, (offset, run, dims[1][1], dims[1][0])
+
+
 def _slice_table(files, slices):
     """the CSADevSlice of every entry of a files table; slices: {stored name: (offset, length) | (offset, run, stride, count)}, an entry
     without a key gets count 0.  KeyError for a key that is no entry of the table."""
@@ -439,7 +482,8 @@ def device_write_plan(files, arcname: str = "out.csa", **opts):
 
 
 def device_write_kernel_ms():
-    """HIP-event milliseconds of this thread's last DeviceArchive.write by kernel: (k_frag_pieces, k_frag_fold, k_block_table, k_gather_extents)"""
+    """HIP-event milliseconds of this thread's last DeviceArchive.write by kernel: (k_frag_pieces -- k_frag_rows in a wave of write_slices
+    with a piece across a run border --, k_frag_fold, k_block_table, k_gather_extents)"""
     ms = (C.c_double * 4)()
     lib().CSAMI_DeviceWriteKernelMs(ms)
     return tuple(ms)
@@ -608,6 +652,54 @@ class DeviceArchive:
                 break
         del live
         d = st.as_dict()
+        d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
+        return rc, (arc[:st.archive_bytes] if rc == 0 else None), d
+
+    @staticmethod
+    def write_slices(entries, arcname: str = "out.csa", arc=None, **opts):
+        """`csarc a -t1` of entries gathered from strided slices of buffers (CSAMI_DeviceWriteSlices) -> (rc, uint8 CUDA view of the
+        archive, stats dict), as write_tensors, with the gather statistics beside the write's.  entries: dicts with name, tensor,
+        slice, edate, eattr; tensor: the 1-d contiguous torch.uint8 CUDA base buffer (None for directories and empty files); slice:
+        (offset, length) | (offset, run, stride, count) into it -- rows_slice makes one for a block of a row-major matrix,
+        tensor_slice both for a strided view.  The entry's bytes are the selected ones, packed: esize = run * count.  The buffers
+        are only read and may alias each other, not arc."""
+        import torch
+        files, table = [], (CSADevSlice * max(len(entries), 1))()
+        for a, e in zip(table, entries):
+            t = e["tensor"]
+            if not (t is None or _is_bytes_tensor(t)):
+                raise TypeError("tensor: a contiguous 1-d torch.uint8 CUDA tensor, or None")
+            s = e.get("slice") or (0, 0, 0, 0)
+            a.offset, a.run, a.stride, a.count = (s[0], s[1], s[1], 1 if s[1] else 0) if len(s) == 2 else s
+            files.append({"name": e["name"], "esize": a.run * a.count if a.count else 0, "edate": e["edate"], "eattr": e["eattr"]})
+        if not (arc is None or _is_bytes_tensor(arc)):
+            raise TypeError("arc: a contiguous 1-d torch.uint8 CUDA tensor")
+        live = [e["tensor"] for e in entries]                      # alive across the call
+        ptrs = (C.c_void_p * max(len(live), 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in live])
+        sizes = (C.c_uint64 * max(len(live), 1))(*[0 if t is None else int(t.numel()) for t in live])
+        device = arc.device if arc is not None else next((t.device for t in live if t is not None), "cuda")
+        o = options(**opts)
+        caps = [None]
+        if arc is None:
+            rc, nt, _, raw = device_write_plan(files, arcname, **opts)
+            if rc != 0:
+                return rc, None, {"files": []}
+            cap = 24 + raw + raw // 8 + (64 << 10) * (nt + 1) + (1 << 20)
+            caps = [cap, 2 * cap]
+        for cap in caps:
+            if cap is not None:
+                arc = torch.empty(cap, dtype=torch.uint8, device=device)
+            arr, keep = _write_table(files)
+            st, gs = CSADevWriteStats(), CSADevGatherStats()
+            torch.cuda.synchronize()                   # the buffers were filled on torch's stream, the library launches on its own
+            rc = lib().CSAMI_DeviceWriteSlices(ptrs, sizes, table, arr, len(keep), arcname.encode(),
+                                               C.c_void_p(arc.data_ptr()) if arc.numel() else None, int(arc.numel()), C.byref(o),
+                                               C.byref(st), C.byref(gs))
+            if rc != WRITE_ERROR:
+                break
+        del live
+        d = st.as_dict()
+        d.update(gs.as_dict())
         d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
         return rc, (arc[:st.archive_bytes] if rc == 0 else None), d
 

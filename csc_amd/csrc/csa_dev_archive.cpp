@@ -196,8 +196,8 @@ struct FragTables {
     {
         using namespace csadev;
         const uint64_t np = piece_count(size, kFragPiece);
-        if (pieces.size() + np > 0x7FFFFFFFull) return false;
-        frags.push_back(FragFold{size, (uint32_t)pieces.size(), (uint32_t)np, checksum, 0});
+        if (gpieces.size() + pieces.size() + np > 0x7FFFFFFFull) return false;
+        frags.push_back(FragFold{size, (uint32_t)(gpieces.size() + pieces.size()), (uint32_t)np, checksum, 0});
         piece_split(src, dst, size, kFragPiece, [&](uint64_t k, CopyPiece p) {
             const uint64_t off = k * kFragPiece;
             p.cmp = (uint32_t)(cmp > off ? std::min<uint64_t>(cmp - off, p.len) : 0);
@@ -226,12 +226,44 @@ struct FragTables {
         });
         return true;
     }
-    uint64_t upload_bytes() const { return pieces.size() * sizeof(csadev::CopyPiece) + frags.size() * sizeof(csadev::FragFold); }
+    // CSAMI_DeviceWriteSlices, in front of `pieces`: a fragment of `size` > 0 bytes that is the packed bytes [at, at + size) of the
+    // (checked) slice sl of the buffer `buf`, gathered to dst.  Each 16 KiB cell of the packed fragment is classified (gather_reduce).
+    // Its pieces and their sums come first: add() counts from behind them.
+    std::vector<csadev::GatherPiece> gpieces;
+    DevBuf d_gpieces;
+    bool add_gathered(const uint8_t *buf, uint8_t *dst, const csadev::Slice &sl, uint64_t at, uint64_t size, CSADevGatherStats &G)
+    {
+        using namespace csadev;
+        const uint64_t np = piece_count(size, kFragPiece);
+        if (!pieces.empty() || gpieces.size() + np > 0x7FFFFFFFull) return false;
+        frags.push_back(FragFold{size, (uint32_t)gpieces.size(), (uint32_t)np, 0, 0});
+        const uint8_t *lo = buf + sl.offset, *hi = lo + (sl.count - 1) * sl.stride + sl.run;
+        for (uint64_t off = 0; off < size; off += kFragPiece) {
+            GatherCut c;
+            const uint32_t len = (uint32_t)std::min<uint64_t>(size - off, kFragPiece);
+            const bool whole = gather_reduce(sl, at + off, len, c);
+            (whole ? G.plain_pieces : G.periodic_pieces)++;
+            gpieces.push_back(whole ? GatherPiece{buf + c.src, dst + off, 0, len, 0, 0, 0, nullptr, nullptr}
+                                    : GatherPiece{buf + c.src, dst + off, c.stride, len, c.phase, c.run, 0, lo, hi});
+        }
+        return true;
+    }
+    // no piece of `gpieces` is periodic: they become the CopyPieces they are, for k_frag_pieces<true>
+    void gathered_as_plain()
+    {
+        for (const csadev::GatherPiece &g : gpieces) pieces.push_back(csadev::CopyPiece{g.src, g.dst, g.len, 0});
+        gpieces.clear();
+    }
+    uint64_t upload_bytes() const
+    {
+        return gpieces.size() * sizeof(csadev::GatherPiece) + pieces.size() * sizeof(csadev::CopyPiece) + frags.size() * sizeof(csadev::FragFold);
+    }
     bool upload(bool compare = false)
     {
-        const size_t np = pieces.size() + spieces.size();                    // (one of the two tables is in use)
+        const size_t np = pieces.size() + spieces.size() + gpieces.size();   // (spieces, or pieces with gpieces in front of them)
         return (spieces.empty() ? d_pieces.upload(pieces.data(), pieces.size() * sizeof(csadev::CopyPiece))
                                 : d_pieces.upload(spieces.data(), spieces.size() * sizeof(csadev::SlicePiece)))
+               && (gpieces.empty() || d_gpieces.upload(gpieces.data(), gpieces.size() * sizeof(csadev::GatherPiece)))
                && d_frags.upload(frags.data(), frags.size() * sizeof(csadev::FragFold))
                && d_sums.alloc(np * sizeof(csadev::PieceSums))
                && d_res.alloc(frags.size() * (compare ? sizeof(csadev::FragDiff) : sizeof(csadev::FragResult)))
@@ -813,7 +845,9 @@ int CSAMI_PlanDeviceSlices(const uint8_t *raw_index, uint64_t raw_size, uint64_t
 // device-resident write: CSAMI_DeviceWritePlan / CSAMI_DeviceWrite (include/csa_mi355x.h).
 // Host side: the index from the caller's table, the plan CSA_Add makes (plan_index), the validation of every size, the piece
 // tables, arc_end, the index and the header.  The bytes move in csa_dev_kernels.hip (k_frag_pieces, k_frag_fold, k_block_table,
-// k_gather_extents; tables and walks: csa_dev_read.h, csa_dev_write.h) and in CSCMI_EncodeDeviceBatch.
+// k_gather_extents; tables and walks: csa_dev_read.h, csa_dev_write.h) and in CSCMI_EncodeDeviceBatch.  All of them are one path
+// over a device pointer and a slice per entry (CSAMI_DeviceWriteSlices): CSAMI_DeviceWrite and CSAMI_DeviceWriteFrom hand in whole
+// entries; where a slice has rows, a task's fragments are gathered across the run borders by k_frag_rows.
 // ---------------------------------------------------------------------------------------------
 namespace {
 
@@ -842,12 +876,15 @@ int plan_write(AddPlan &P, const CSADevFile *files, uint32_t n_files, const CSAO
 }
 
 struct WriteCtx {
-    const void *const *ptrs = nullptr;         // entry `row` of the caller's table lies at ptrs[row]
+    const void *const *ptrs = nullptr;         // entry `row` of the caller's table: the bytes that slices[row], checked, selects of
+    const csadev::Slice *slices = nullptr;     // the buffer at ptrs[row], packed row after row
     uint8_t *arc = nullptr;
     uint64_t arc_cap = 0, arc_end = kHeaderSize;
-    const uint8_t *at(const FilePiece &f) const { return (const uint8_t *)ptrs[f.it->second.row] + f.off; }
+    const uint8_t *buf(const FilePiece &f) const { return (const uint8_t *)ptrs[f.it->second.row]; }
+    const csadev::Slice &slice(const FilePiece &f) const { return slices[f.it->second.row]; }
     int64_t slack = -1;                        // CSA_DEVWRITE_SLACK, -1: not set
     CSADevWriteStats S;
+    CSADevGatherStats G;
     DevTimer tm;
     BlockIndex abindex;
 };
@@ -928,7 +965,8 @@ int dev_place(WriteCtx &W, const std::vector<CSCMIDevEncode> &jobs, const uint8_
 int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
 {
     using namespace csadev;
-    // 1. where each task's raw bytes lie: one range of one entry is encoded where it is, anything else is gathered
+    // 1. where each task's raw bytes lie: one range of one entry that lies inside one run of its slice is encoded where it is,
+    // anything else is gathered
     std::vector<const uint8_t *> in(count, nullptr);
     std::vector<uint64_t> gat_off(count, 0);
     std::vector<uint8_t> gathered(count, 0);
@@ -937,49 +975,69 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
         Task &t = P.tasks[first + k];
         uint64_t cum = 0;
         size_t nonempty = 0;
+        bool in_run = false;
         for (FilePiece &f : t.files) {
             f.posblock = cum;                                                // csa_io.h:239
             cum += f.size;
-            if (f.size) { nonempty++; in[k] = W.at(f); }
+            if (f.size) {
+                uint64_t src;
+                nonempty++;
+                in_run = gather_whole(W.slice(f), f.off, f.size, &src);
+                in[k] = W.buf(f) + src;
+            }
             npieces += piece_count(f.size, kFragPiece);
         }
-        if (nonempty > 1) {
+        if (nonempty > 1 || (nonempty == 1 && !in_run)) {
             gathered[k] = 1;
             gat_off[k] = gat_bytes;
             gat_bytes += (t.total + 255) & ~255ull;
+            W.G.gathered_tasks++;
+        } else if (nonempty) {
+            W.G.inplace_tasks++;
         }
     }
     if (npieces > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
     DevBuf d_gat;
     if (gat_bytes && !d_gat.alloc(gat_bytes)) return CSCMI_DEVICE_ERROR;
 
-    // 2. gather and sum in one pass: the fragments of the gathered tasks, whose pieces are stored, first; then those of the tasks
-    // encoded where they lie, whose pieces are only summed
+    // 2. gather and sum in one pass: the fragments of the gathered tasks, whose pieces are stored, first -- through k_frag_rows if
+    // one of them crosses a run border, else as the CopyPieces they all are; then those of the tasks encoded where they lie, whose
+    // pieces are only summed
     {
         FragTables T;
         std::vector<FilePiece *> ff_piece;
-        size_t nstore = 0;
-        for (int store = 1; store >= 0; store--) {
-            for (size_t k = 0; k < count; k++) {
-                if (gathered[k] != store) continue;
-                for (FilePiece &f : P.tasks[first + k].files) {
-                    f.checksum = 0;
-                    if (!f.size) continue;                                       // adler32 of nothing, seed 0
-                    if (!T.add(W.at(f), store ? (uint8_t *)d_gat.p + gat_off[k] + f.posblock : nullptr, f.size, 0)) return CSCMI_DEVICE_ERROR;
-                    ff_piece.push_back(&f);
-                }
-                if (store) in[k] = (const uint8_t *)d_gat.p + gat_off[k];
+        for (size_t k = 0; k < count; k++) {
+            if (!gathered[k]) continue;
+            for (FilePiece &f : P.tasks[first + k].files) {
+                f.checksum = 0;
+                if (!f.size) continue;                                           // adler32 of nothing, seed 0
+                if (!T.add_gathered(W.buf(f), (uint8_t *)d_gat.p + gat_off[k] + f.posblock, W.slice(f), f.off, f.size, W.G)) return CSCMI_DEVICE_ERROR;
+                ff_piece.push_back(&f);
             }
-            if (store) nstore = T.pieces.size();
+            in[k] = (const uint8_t *)d_gat.p + gat_off[k];
+        }
+        const size_t nstore = T.gpieces.size();
+        const bool rows = std::any_of(T.gpieces.begin(), T.gpieces.end(), [](const GatherPiece &g) { return g.stride != 0; });
+        if (!rows) T.gathered_as_plain();
+        for (size_t k = 0; k < count; k++) {
+            if (gathered[k]) continue;
+            for (FilePiece &f : P.tasks[first + k].files) {
+                f.checksum = 0;
+                if (!f.size) continue;
+                if (!T.add(in[k], nullptr, f.size, 0)) return CSCMI_DEVICE_ERROR;
+                ff_piece.push_back(&f);
+            }
         }
         if (!T.frags.empty()) {
-            const size_t nsum = T.pieces.size() - nstore;
+            const size_t nsum = T.gpieces.size() + T.pieces.size() - nstore, sum0 = rows ? 0 : nstore;   // sum0: the first summed piece in d_pieces
+            W.G.plain_pieces += nsum;
             W.S.upload_bytes += T.upload_bytes();
             if (!T.upload()) return CSCMI_DEVICE_ERROR;
             if (nstore && !W.tm.timed(&g_write_ms[0], W.S.launches, [&] {
-                    launch_frag_pieces(T.d_pieces.p, T.d_sums.p, (uint32_t)nstore, true, W.tm.st); })) return CSCMI_DEVICE_ERROR;
+                    if (rows) launch_frag_rows(T.d_gpieces.p, T.d_sums.p, (uint32_t)nstore, W.tm.st);
+                    else launch_frag_pieces(T.d_pieces.p, T.d_sums.p, (uint32_t)nstore, true, W.tm.st); })) return CSCMI_DEVICE_ERROR;
             if (nsum && !W.tm.timed(&g_write_ms[0], W.S.launches, [&] {
-                    launch_frag_pieces((const CopyPiece *)T.d_pieces.p + nstore, (PieceSums *)T.d_sums.p + nstore, (uint32_t)nsum, false, W.tm.st); }))
+                    launch_frag_pieces((const CopyPiece *)T.d_pieces.p + sum0, (PieceSums *)T.d_sums.p + nstore, (uint32_t)nsum, false, W.tm.st); }))
                 return CSCMI_DEVICE_ERROR;
             std::vector<FragResult> res;
             if (!T.fold(W.tm, &g_write_ms[1], W.S.launches, res)) return CSCMI_DEVICE_ERROR;
@@ -1103,24 +1161,54 @@ int CSAMI_DeviceWrite(const void *src_dev, uint64_t src_size, CSADevFile *files,
 int CSAMI_DeviceWriteFrom(const void *const *ptrs, CSADevFile *files, uint32_t n_files, const char *arcname,
                           void *arc_dev, uint64_t arc_cap, const CSAOptions *opt, CSADevWriteStats *st)
 {
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
+    // every entry whole: slices[i] = {0, esize, esize, 1} of a buffer of esize bytes (a table the write refuses is refused there)
+    std::vector<CSADevSlice> slices(n_files, CSADevSlice{0, 0, 0, 0});
+    std::vector<uint64_t> sizes(n_files, 0);
+    for (uint32_t i = 0; files && i < n_files; i++)
+        if (files[i].esize > 0) { sizes[i] = (uint64_t)files[i].esize; slices[i] = CSADevSlice{0, sizes[i], sizes[i], 1}; }
+    return CSAMI_DeviceWriteSlices(ptrs, sizes.data(), slices.data(), files, n_files, arcname, arc_dev, arc_cap, opt, st, nullptr);
+}
+
+int CSAMI_DeviceWriteSlices(const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices, CSADevFile *files, uint32_t n_files,
+                            const char *arcname, void *arc_dev, uint64_t arc_cap, const CSAOptions *opt, CSADevWriteStats *st,
+                            CSADevGatherStats *gather_stats)
+{
     const double t0 = now_s();
     if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
     WriteCtx W;
     memset(&W.S, 0, sizeof(W.S));
+    memset(&W.G, 0, sizeof(W.G));
     if (st) *st = W.S;
+    if (gather_stats) *gather_stats = W.G;
     for (double &m : g_write_ms) m = 0;
     // ---- everything the host can refuse, before any launch
     uint64_t a1;
-    if (!arcname || (!arc_dev && arc_cap) || !add_ok((uintptr_t)arc_dev, arc_cap, &a1) || (n_files && !ptrs)) return -1;
+    if (!arcname || (!arc_dev && arc_cap) || !add_ok((uintptr_t)arc_dev, arc_cap, &a1) || (n_files && (!ptrs || !sizes || !slices))) return -1;
     AddPlan P;
     int rc = plan_write(P, files, n_files, opt, &W.S.raw_bytes);
     if (rc) return rc;
-    std::vector<uint64_t> sizes(n_files);
-    for (uint32_t i = 0; i < n_files; i++) sizes[i] = (uint64_t)files[i].esize;
-    if (CSAMI_CheckBuffers(ptrs, sizes.data(), n_files, arc_dev, arc_cap, 0, nullptr) != 0) return -1;
+    // the slices, each inside its buffer and selecting exactly its entry's bytes; the hulls, which are all that is loaded
+    std::vector<csadev::Slice> sl(n_files);
+    std::vector<const void *> hull(n_files, nullptr);
+    std::vector<uint64_t> hull_size(n_files, 0);
+    CSADevGatherStats G = W.G;
+    for (uint32_t i = 0; i < n_files; i++) {
+        sl[i] = csadev::Slice{slices[i].offset, slices[i].run, slices[i].stride, slices[i].count};
+        uint64_t bytes, at;
+        if (!csadev::slice_check(sl[i], sizes[i], &bytes) || bytes != (uint64_t)files[i].esize) return -1;
+        if (!sl[i].count) continue;
+        if (!ptrs[i] || !add_ok((uintptr_t)ptrs[i], sl[i].offset, &at)) return -1;
+        hull[i] = (const void *)(uintptr_t)at;
+        hull_size[i] = (sl[i].count - 1) * sl[i].stride + sl[i].run;         // (checked by slice_check)
+        G.selected_bytes += bytes;                                           // (plan_write: the sizes sum to at most 2^60)
+        if (!add_ok(G.hull_bytes, hull_size[i], &G.hull_bytes)) return -1;
+    }
+    if (CSAMI_CheckBuffers(hull.data(), hull_size.data(), n_files, arc_dev, arc_cap, 0, nullptr) != 0) return -1;
     if (arc_cap < kHeaderSize) return WRITE_ERROR;
     if (const char *e = getenv("CSA_DEVWRITE_SLACK")) { W.slack = (int64_t)strtoull(e, nullptr, 10); if (W.slack < 0) W.slack = -1; }
-    W.ptrs = ptrs; W.arc = (uint8_t *)arc_dev; W.arc_cap = arc_cap;
+    W.ptrs = ptrs; W.slices = sl.data(); W.arc = (uint8_t *)arc_dev; W.arc_cap = arc_cap;
+    W.G = G;
     if (!W.tm.ok) return CSCMI_DEVICE_ERROR;
 
     // ---- waves of consecutive task ids, largest first (csarc.cpp:355): the plan's order and the archive's
@@ -1186,6 +1274,7 @@ int CSAMI_DeviceWriteFrom(const void *const *ptrs, CSADevFile *files, uint32_t n
     W.S.kernel_ms = g_write_ms[0] + g_write_ms[1] + g_write_ms[2] + g_write_ms[3];
     W.S.seconds_total = now_s() - t0;
     if (st) *st = W.S;
+    if (gather_stats) *gather_stats = W.G;
     return rc;
 }
 

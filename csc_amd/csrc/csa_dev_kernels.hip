@@ -16,6 +16,8 @@
 //   k_frag_fold_diff      k_frag_fold, and the fragment's first differing offset from its pieces'
 //   k_frag_slices         k_frag_pieces<true> for CSAMI_DeviceReadSlices: a piece is still summed whole, and the bytes of it that its
 //                         entry's slice selects -- all, none, or the runs of a periodic pattern -- go to their packed places
+//   k_frag_rows           k_frag_pieces<true> for CSAMI_DeviceWriteSlices, the transpose of k_frag_slices: a piece's destination is
+//                         contiguous and its source is the runs of a periodic pattern in the caller's buffer (or one range of it)
 //   k_block_table         one lane per task stream of a wave (write only): the archive-block table AsyncWriter would have made of
 //                         the encoder's Write calls (csa_io.h:145-201), read off the stream's framing (csa_dev_write.h)
 //
@@ -37,14 +39,9 @@ __global__ __launch_bounds__(kThreads) void k_gather_extents(const CopyPiece *pi
     copy_sum<true, false>(pc.dst, pc.src, pc.len, threadIdx.x, kThreads, a, b);
 }
 
-template <bool STORE>
-__global__ __launch_bounds__(kThreads) void k_frag_pieces(const CopyPiece *pieces, PieceSums *out, uint32_t npieces)
+// the workgroup's a and b added up and stored as its piece's sums
+__device__ inline void store_sums(uint64_t a, uint64_t b, PieceSums *out)
 {
-    if (blockIdx.x >= npieces) return;
-    const CopyPiece pc = pieces[blockIdx.x];
-    uint64_t a = 0, b = 0;
-    if (STORE && pc.dst == nullptr) copy_sum<false, true>(nullptr, pc.src, pc.len, threadIdx.x, kThreads, a, b);   // (the same for the whole workgroup)
-    else copy_sum<STORE, true>(pc.dst, pc.src, pc.len, threadIdx.x, kThreads, a, b);
     for (int off = 32; off > 0; off >>= 1) {
         a += __shfl_down(a, off, 64);
         b += __shfl_down(b, off, 64);
@@ -56,8 +53,19 @@ __global__ __launch_bounds__(kThreads) void k_frag_pieces(const CopyPiece *piece
     if (threadIdx.x == 0) {
         PieceSums s = {0, 0};
         for (uint32_t w = 0; w < kThreads / 64; w++) { s.a += red[2 * w]; s.b += red[2 * w + 1]; }
-        out[blockIdx.x] = s;
+        *out = s;
     }
+}
+
+template <bool STORE>
+__global__ __launch_bounds__(kThreads) void k_frag_pieces(const CopyPiece *pieces, PieceSums *out, uint32_t npieces)
+{
+    if (blockIdx.x >= npieces) return;
+    const CopyPiece pc = pieces[blockIdx.x];
+    uint64_t a = 0, b = 0;
+    if (STORE && pc.dst == nullptr) copy_sum<false, true>(nullptr, pc.src, pc.len, threadIdx.x, kThreads, a, b);   // (the same for the whole workgroup)
+    else copy_sum<STORE, true>(pc.dst, pc.src, pc.len, threadIdx.x, kThreads, a, b);
+    store_sums(a, b, out + blockIdx.x);
 }
 
 // k_frag_pieces<true> with two loads in the place of a load and a store: the piece's first `cmp` bytes against the caller's
@@ -100,19 +108,20 @@ __global__ __launch_bounds__(kThreads) void k_frag_slices(const SlicePiece *piec
     if (pc.stride) slice_sum(pc, threadIdx.x, kThreads, a, b);
     else if (pc.dst == nullptr) copy_sum<false, true>(nullptr, pc.src, pc.len, threadIdx.x, kThreads, a, b);
     else copy_sum<true, true>(pc.dst, pc.src, pc.len, threadIdx.x, kThreads, a, b);
-    for (int off = 32; off > 0; off >>= 1) {
-        a += __shfl_down(a, off, 64);
-        b += __shfl_down(b, off, 64);
-    }
-    __shared__ uint64_t red[2 * (kThreads / 64)];
-    const uint32_t wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) { red[2 * wave] = a; red[2 * wave + 1] = b; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        PieceSums s = {0, 0};
-        for (uint32_t w = 0; w < kThreads / 64; w++) { s.a += red[2 * w]; s.b += red[2 * w + 1]; }
-        out[blockIdx.x] = s;
-    }
+    store_sums(a, b, out + blockIdx.x);
+}
+
+// k_frag_pieces<true> for CSAMI_DeviceWriteSlices: a piece whose packed bytes lie inside one run of its entry's slice is copy_sum's
+// as there; any other is gathered across the run borders (gather_sum, csa_dev_write.h).  Which of the two: the same for the whole
+// workgroup.
+__global__ __launch_bounds__(kThreads) void k_frag_rows(const GatherPiece *pieces, PieceSums *out, uint32_t npieces)
+{
+    if (blockIdx.x >= npieces) return;
+    const GatherPiece pc = pieces[blockIdx.x];
+    uint64_t a = 0, b = 0;
+    if (pc.stride) gather_sum(pc, threadIdx.x, kThreads, a, b);
+    else copy_sum<true, true>(pc.dst, pc.src, pc.len, threadIdx.x, kThreads, a, b);
+    store_sums(a, b, out + blockIdx.x);
 }
 
 __global__ __launch_bounds__(kThreads) void k_frag_fold(const FragFold *frags, const PieceSums *sums, FragResult *out, uint32_t nfrags)
@@ -162,6 +171,11 @@ void launch_frag_compare(const void *pieces, void *sums, void *firsts, uint32_t 
 void launch_frag_slices(const void *pieces, void *sums, uint32_t npieces, hipStream_t st)
 {
     hipLaunchKernelGGL(k_frag_slices, dim3(npieces ? npieces : 1), dim3(kThreads), 0, st, (const SlicePiece *)pieces, (PieceSums *)sums, npieces);
+}
+
+void launch_frag_rows(const void *pieces, void *sums, uint32_t npieces, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_frag_rows, dim3(npieces ? npieces : 1), dim3(kThreads), 0, st, (const GatherPiece *)pieces, (PieceSums *)sums, npieces);
 }
 
 void launch_frag_fold(const void *frags, const void *sums, void *out, uint32_t nfrags, hipStream_t st)

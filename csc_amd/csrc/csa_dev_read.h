@@ -99,6 +99,31 @@ CSADEV_FHD void sum_word(uint32_t w, uint32_t i0, uint32_t wl, uint64_t &a, uint
     b += (uint64_t)(wl - i0) * s - t;
 }
 
+// The 16 bytes that begin m bytes, 0 < m < 16, into the aligned vector x, whose next one is y: funnel-shifted into place
+CSADEV_FHD Vec16 funnel16(const Vec16 &x, const Vec16 &y, uint32_t m)
+{
+    const uint32_t sw = m >> 2, sb = 8 * (m & 3u);
+    const uint32_t t0 = (sw & 2u) ? x.w[2] : x.w[0], t1 = (sw & 2u) ? x.w[3] : x.w[1], t2 = (sw & 2u) ? y.w[0] : x.w[2],
+                   t3 = (sw & 2u) ? y.w[1] : x.w[3], t4 = (sw & 2u) ? y.w[2] : y.w[0], t5 = (sw & 2u) ? y.w[3] : y.w[1];
+    const uint32_t u0 = (sw & 1u) ? t1 : t0, u1 = (sw & 1u) ? t2 : t1, u2 = (sw & 1u) ? t3 : t2, u3 = (sw & 1u) ? t4 : t3,
+                   u4 = (sw & 1u) ? t5 : t4;
+    Vec16 o;
+    o.w[0] = (uint32_t)((((uint64_t)u1 << 32) | u0) >> sb);
+    o.w[1] = (uint32_t)((((uint64_t)u2 << 32) | u1) >> sb);
+    o.w[2] = (uint32_t)((((uint64_t)u3 << 32) | u2) >> sb);
+    o.w[3] = (uint32_t)((((uint64_t)u4 << 32) | u3) >> sb);
+    return o;
+}
+
+// the 16 bytes at p, of any alignment, one by one
+CSADEV_FHD Vec16 load_bytes16(const uint8_t *p)
+{
+    Vec16 o;
+    for (uint32_t k = 0; k < 4; k++)
+        o.w[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
+    return o;
+}
+
 // Unit i -- the 16 bytes [s0 + 16 i, s0 + 16 i + 16) -- of a range r[0, n), where s0 = r + head has any alignment and the unit lies
 // inside the range: one aligned 16-byte load; or two of them, funnel-shifted into place; or, where that 32-byte window would begin
 // before r or end behind r + n (the first and the last unit, at most), the 16 bytes one by one.
@@ -107,26 +132,10 @@ CSADEV_FHD Vec16 load_unit(const uint8_t *s0, uint32_t head, uint32_t n, uint32_
 {
     const uint32_t m = (uint32_t)(uintptr_t)s0 & 15u;
     const uintptr_t base = (uintptr_t)s0 - m;                         // aligned; vector i of it covers bytes [16 i - m, 16 i - m + 16) of s0
-    const uint32_t sw = m >> 2, sb = 8 * (m & 3u);
-    Vec16 o;
-    if (m == 0) {
-        o = *(const Vec16 *)(base + 16ull * i);
-    } else if (WINDOW_UNCHECKED || (head + 16 * i >= m && head + 16 * i + 32 <= n + m)) {   // the window [16 i - m, 16 i - m + 32) of s0 lies in r[0, n)
-        const Vec16 x = *(const Vec16 *)(base + 16ull * i), y = *(const Vec16 *)(base + 16ull * i + 16);
-        const uint32_t t0 = (sw & 2u) ? x.w[2] : x.w[0], t1 = (sw & 2u) ? x.w[3] : x.w[1], t2 = (sw & 2u) ? y.w[0] : x.w[2],
-                       t3 = (sw & 2u) ? y.w[1] : x.w[3], t4 = (sw & 2u) ? y.w[2] : y.w[0], t5 = (sw & 2u) ? y.w[3] : y.w[1];
-        const uint32_t u0 = (sw & 1u) ? t1 : t0, u1 = (sw & 1u) ? t2 : t1, u2 = (sw & 1u) ? t3 : t2, u3 = (sw & 1u) ? t4 : t3,
-                       u4 = (sw & 1u) ? t5 : t4;
-        o.w[0] = (uint32_t)((((uint64_t)u1 << 32) | u0) >> sb);
-        o.w[1] = (uint32_t)((((uint64_t)u2 << 32) | u1) >> sb);
-        o.w[2] = (uint32_t)((((uint64_t)u3 << 32) | u2) >> sb);
-        o.w[3] = (uint32_t)((((uint64_t)u4 << 32) | u3) >> sb);
-    } else {
-        const uint8_t *p = s0 + 16 * i;
-        for (uint32_t k = 0; k < 4; k++)
-            o.w[k] = (uint32_t)p[4 * k] | (uint32_t)p[4 * k + 1] << 8 | (uint32_t)p[4 * k + 2] << 16 | (uint32_t)p[4 * k + 3] << 24;
-    }
-    return o;
+    if (m == 0) return *(const Vec16 *)(base + 16ull * i);
+    if (WINDOW_UNCHECKED || (head + 16 * i >= m && head + 16 * i + 32 <= n + m))    // the window [16 i - m, 16 i - m + 32) of s0 lies in r[0, n)
+        return funnel16(*(const Vec16 *)(base + 16ull * i), *(const Vec16 *)(base + 16ull * i + 16), m);
+    return load_bytes16(s0 + 16 * i);
 }
 
 // Thread `tid` of `nthreads`: its share of src[0, n) -- copied to dst[0, n) (STORE) and/or summed into a, b as one piece of n bytes

@@ -1,7 +1,8 @@
 // csa_dev_write.h -- the device-resident archive write (CSAMI_DeviceWrite, include/csa_mi355x.h) below the host planner: a task's
 // archive-block table, taken from the framed stream where it lies.  Compiles for the host (plain C++:
 // tests/test_archive_device_write_host.py runs tests/model/csa_dev_write_model.cpp with g++ and the sanitizers) and for the device
-// (k_block_table, csa_dev_kernels.hip), so the model runs the text the kernel runs.
+// (k_block_table, csa_dev_kernels.hip), so the model runs the text the kernel runs.  Its second half is the piece of
+// CSAMI_DeviceWriteSlices whose source is periodic (k_frag_rows; gather_reduce, gather_sum and their model are described there).
 //
 // What the reference does here: the encoder hands its output to AsyncArchiveWriter through ISeqOutStream::Write, and the writer
 // coalesces those calls into archive blocks (AsyncWriter::Write / flush, csa_io.h:145-201; Finish, :596-603):
@@ -104,6 +105,130 @@ CSADEV_FHD uint32_t block_table(Load ld, uint64_t produced, uint32_t bsize, uint
     *nblocks = co.n;
     if (status == kTableOk && co.full) status = kTableFull;
     return status;
+}
+
+// ---- entries gathered from strided slices of the caller's buffers (CSAMI_DeviceWriteSlices): the transpose of slice_sum ----
+//
+// An entry's bytes are what a checked Slice selects of a buffer, packed row after row: packed byte p lies at buffer offset
+// offset + (p / run) * stride + p % run.  The pieces of a fragment stay on the fixed kFragPiece grid of the PACKED fragment
+// (fold_pieces needs it), so a piece's destination is contiguous and its source is the tail of one run, a gap and the head of the
+// next -- or, where run is small, many of them.  gather_whole and gather_reduce are the host planner's; gather_sum is the
+// workgroup's (tests/model/csa_dev_gather_model.cpp is their model).  With run < 16 every 16-byte unit crosses a run border and is
+// assembled byte by byte: that is the slow path, and no rate is promised for it.
+
+enum GatherPlant {
+    kGPlantNone = 0, kGPlantBorderLate = 1, kGPlantPhaseDropped = 2, kGPlantStraddleContiguous = 3, kGPlantRowNotAdvanced = 4,
+    kGPlantWindowPastHull = 5
+};
+
+struct GatherPiece {       // one workgroup of k_frag_rows
+    const uint8_t *src;    // stride == 0: the piece's one contiguous source (copy_sum<true, true>, as a CopyPiece);
+                           // else the address of period position 0, inside the hull (what lies in front of `phase` is not loaded)
+    uint8_t *dst;          // the piece's contiguous destination
+    uint64_t stride;       // periodic: the address step from one run to the next, >= run
+    uint32_t len;          // <= kFragPiece
+    uint32_t phase;        // periodic: byte i of the piece is period position pos = phase + i; row = pos / run, r = pos % run; it lies
+    uint32_t run;          //           at src + row * stride + r
+    uint32_t pad;
+    const uint8_t *lo, *hi;   // periodic: the slice's hull [lo, hi): all that a load window may touch
+};
+
+// The packed bytes [at, at + size), size > 0, of a checked slice (at + size <= run * count): true if they lie inside one run, and
+// *src is then the buffer offset of the first.  One division, no walk over the rows.
+CSADEV_FHD bool gather_whole(const Slice &s, uint64_t at, uint64_t size, uint64_t *src)
+{
+    const uint64_t k0 = at / s.run, r0 = at - k0 * s.run;
+    *src = s.offset + k0 * s.stride + r0;
+    return s.run - r0 >= size;
+}
+
+struct GatherCut { uint64_t src, stride; uint32_t phase, run; };
+
+// The piece [at, at + len) of the packed bytes, 0 < len <= kFragPiece, under a checked slice: true if it lies inside one run (c.src
+// is the buffer offset of its first byte, the rest of c is 0).  Else c is the GatherPiece's phase, run and stride, and c.src the
+// buffer offset of period position 0.  A piece sees at most kFragPiece packed bytes, so whatever the 64-bit run is it sees the same
+// as under a run cut to kFragPiece -- the run it begins in from its front, since what lies before the piece is not seen, the next
+// one from its back: run' = min(run, kFragPiece) and stride' = stride - (run - run'), so phase + len < 2^16 and every division of
+// gather_sum is one of 32-bit quantities.  The stride is an address step and stays 64-bit.  Patterns that fit are left as they are.
+CSADEV_FHD bool gather_reduce(const Slice &s, uint64_t at, uint32_t len, GatherCut &c)
+{
+    c = GatherCut{0, 0, 0, 0};
+    if (gather_whole(s, at, len, &c.src)) return true;
+    const uint64_t k0 = at / s.run, r0 = at - k0 * s.run;
+    const uint64_t cut = s.run > kFragPiece ? s.run - kFragPiece : 0;        // (r0 > cut: fewer than len bytes are left of the run)
+    c.src = s.offset + k0 * s.stride + cut;
+    c.stride = s.stride - cut;
+    c.run = (uint32_t)(s.run - cut);
+    c.phase = (uint32_t)(r0 - cut);
+    return false;
+}
+
+// The 16 bytes at p, of any alignment, all inside the hull [lo, hi): one aligned 16-byte load; or two of them, funnel-shifted into
+// place, as load_unit; or, where that 32-byte window would leave the hull, the 16 bytes one by one.
+template <bool END_UNCHECKED = false>
+CSADEV_FHD Vec16 load_window(const uint8_t *p, const uint8_t *lo, const uint8_t *hi)
+{
+    const uint32_t m = (uint32_t)(uintptr_t)p & 15u;
+    const uintptr_t base = (uintptr_t)p - m;
+    if (m == 0) return *(const Vec16 *)base;
+    if (base >= (uintptr_t)lo && (END_UNCHECKED || base + 32 <= (uintptr_t)hi)) return funnel16(*(const Vec16 *)base, *(const Vec16 *)(base + 16), m);
+    return load_bytes16(p);
+}
+
+// Thread `tid` of `nthreads`: its share of a periodic piece.  The anchor is the destination: up to 15 head bytes bring it to a
+// 16-byte line and up to 15 tail bytes end the piece, byte by byte; between them every unit is one aligned 16-byte store.  A unit
+// whose 16 packed bytes lie inside one run is loaded as load_unit loads (load_window: the window is checked against the HULL, so gap
+// bytes may be loaded; they are never summed and never stored); a unit across a run border is assembled row segment by row
+// segment, byte by byte.  The sums are over packed positions, as one piece of len bytes: exactly copy_sum<true, true>'s over the
+// packed bytes.  No division in the unit loop: a thread's (row, r) advances by the workgroup's step, 16 * nthreads packed
+// positions, with one carry.
+template <int PLANT = kGPlantNone>
+CSADEV_FHD void gather_sum(const GatherPiece &pc, uint32_t tid, uint32_t nthreads, uint64_t &a, uint64_t &b)
+{
+    const uint8_t *src = pc.src;
+    uint8_t *dst = pc.dst;
+    const uint32_t n = pc.len, run = pc.run;
+    const uint64_t stride = pc.stride;
+    uint32_t head = (0u - (uint32_t)(uintptr_t)dst) & 15u;
+    if (head > n) head = n;
+    const uint32_t units = (n - head) >> 4, tail = (n - head) & 15u;
+    auto one = [&](uint32_t idx) {
+        const uint32_t pos = pc.phase + idx, row = pos / run, r = pos - row * run;
+        const uint32_t v = src[row * stride + r];
+        dst[idx] = (uint8_t)v;
+        a += v;
+        b += (uint64_t)(n - idx) * v;
+    };
+    if (tid < head) one(tid);
+    if (nthreads - 1 - tid < tail) one(head + 16 * units + (nthreads - 1 - tid));
+    if (tid >= units) return;
+    const uint32_t step = 16 * nthreads, srow = step / run, sr = step - srow * run;
+    const uint32_t border = PLANT == kGPlantBorderLate ? run + 1 : run;              // r == border: the next row begins
+    const uint32_t pos = (PLANT == kGPlantPhaseDropped ? 0u : pc.phase) + head + 16 * tid;
+    uint32_t row = pos / run, r = pos - row * run;
+    for (uint32_t i = tid; i < units; i += nthreads) {
+        const uint32_t i0 = head + 16 * i;
+        const uint8_t *p = src + row * stride + r;
+        Vec16 o;
+        if (PLANT == kGPlantStraddleContiguous || r + 16 <= run) {
+            o = load_window<PLANT == kGPlantWindowPastHull>(p, pc.lo, pc.hi);
+        } else {
+            o = Vec16{{0, 0, 0, 0}};
+            uint32_t r1 = r;
+            for (uint32_t j = 0; j < 16; j++) {
+                o.w[j >> 2] |= (uint32_t)*p++ << (8 * (j & 3u));
+                if (++r1 == border) { r1 = 0; p += stride - run; }
+            }
+        }
+        *(Vec16 *)(dst + i0) = o;
+        sum_word(o.w[0], i0, n, a, b);
+        sum_word(o.w[1], i0 + 4, n, a, b);
+        sum_word(o.w[2], i0 + 8, n, a, b);
+        sum_word(o.w[3], i0 + 12, n, a, b);
+        r += sr;
+        row += srow;
+        if (r >= run) { r -= run; if (PLANT != kGPlantRowNotAdvanced) row++; }
+    }
 }
 
 }  // namespace csadev

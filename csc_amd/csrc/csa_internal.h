@@ -18,6 +18,7 @@ void launch_gather_extents(const void *pieces, uint32_t npieces, hipStream_t st)
 void launch_frag_pieces(const void *pieces, void *sums, uint32_t npieces, bool store, hipStream_t st);
 void launch_frag_compare(const void *pieces, void *sums, void *firsts, uint32_t npieces, hipStream_t st);
 void launch_frag_slices(const void *pieces, void *sums, uint32_t npieces, hipStream_t st);
+void launch_frag_rows(const void *pieces, void *sums, uint32_t npieces, hipStream_t st);
 void launch_frag_fold(const void *frags, const void *sums, void *out, uint32_t nfrags, hipStream_t st);
 void launch_frag_fold_diff(const void *frags, const void *sums, const void *firsts, void *out, uint32_t nfrags, hipStream_t st);
 void launch_block_table(const void *jobs, uint32_t njobs, void *scratch, void *res, void *sizes, hipStream_t st);

@@ -328,7 +328,7 @@ int CSAMI_DeviceWritePlan(const CSADevFile *files, uint32_t n_files, const char 
                           uint32_t *n_tasks, uint32_t *max_frags, uint64_t *raw_bytes);
 int CSAMI_DeviceWrite(const void *src_dev, uint64_t src_size, CSADevFile *files, uint32_t n_files, const char *arcname,
                       void *arc_dev, uint64_t arc_cap, const CSAOptions *o, CSADevWriteStats *st);
-/* HIP-event milliseconds of this thread's last CSAMI_DeviceWrite by kernel: [0] k_frag_pieces, [1] k_frag_fold, [2] k_block_table,
+/* HIP-event milliseconds of this thread's last CSAMI_DeviceWrite by kernel: [0] k_frag_pieces (or k_frag_rows), [1] k_frag_fold, [2] k_block_table,
  * [3] k_gather_extents (placement) */
 void CSAMI_DeviceWriteKernelMs(double ms[4]);
 
@@ -429,7 +429,7 @@ int CSAMI_DeviceCompare(CSADevArchive *a, const char *const *names, int nnames, 
  * a 16-byte unit inside one run stored as 16 bytes, a unit across a run border byte by byte.  Its table entry holds 32-bit
  * quantities whatever run and stride are.  Nothing outside a fragment's decoded bytes is loaded, not even by an aligned 16-byte
  * window, and nothing but the selected bytes' destinations is stored.
- * Out of scope: stopping inside a fragment, CSAMI_DeviceCompare against a slice, writing or updating a slice, and the host paths
+ * Out of scope: stopping inside a fragment, CSAMI_DeviceCompare against a slice, updating a slice, and the host paths
  * (CSA_Extract / CSA_Test). */
 typedef struct CSADevSlice { uint64_t offset, run, stride, count; } CSADevSlice;
 typedef struct CSADevSliceStats {
@@ -454,6 +454,55 @@ int CSAMI_DeviceReadSlices(CSADevArchive *a, const char *const *names, int nname
 int CSAMI_PlanDeviceSlices(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const char *const *names, int nnames,
                            const CSADevSlice *slices, uint32_t n, uint64_t *bids, uint64_t *stops, uint64_t *raws, uint32_t cap,
                            uint32_t *n_tasks, uint32_t *n_touched);
+
+/* ---- entries gathered from strided slices of the caller's buffers: a write that takes its bytes where they lie; not in the reference ----
+ *
+ * CSAMI_DeviceWriteFrom wants every entry as one contiguous range.  Here entry i's bytes are the bytes that slices[i] -- a
+ * CSADevSlice exactly as CSAMI_DeviceReadSlices defines it: offset, run, stride, count; with count == 1 the stride is ignored --
+ * selects out of the caller's buffer ptrs[i][0, sizes[i]), packed row after row: a rank that holds a full row-major matrix archives
+ * its block of columns, one run out of every row, without a contiguous copy of it.  The archive is byte for byte what CSA_Add and
+ * CSAMI_DeviceWriteFrom write for the packed bytes and the same options; the plan depends on sizes alone, so CSAMI_DeviceWritePlan
+ * serves unchanged.  There is one write path: CSAMI_DeviceWriteFrom is this call with slices[i] = {0, esize_i, esize_i, 1} and
+ * sizes[i] = esize_i.
+ *
+ * Refused with -1, nothing launched and *st and *gather_stats (each may be NULL) zeroed: everything CSAMI_DeviceWriteFrom refuses in
+ * a table; slices == NULL or sizes == NULL with n_files > 0; a slice that the read refuses in an entry of sizes[i] bytes (run == 0
+ * with count > 0, stride < run with count > 1, any product or sum that wraps, a last selected byte at or behind sizes[i]);
+ * files[i].esize != run * count -- so count == 0 goes with esize == 0 and with nothing else, and ptrs[i] may be NULL there; a NULL
+ * ptrs[i] with count > 0; and whatever CSAMI_CheckBuffers refuses over the HULLS [ptrs[i] + offset, + (count - 1) * stride + run)
+ * against [arc, arc + arc_cap) with disjoint == 0.  Hulls may alias each other.  The other return values are CSAMI_DeviceWriteFrom's:
+ * WRITE_ERROR for an archive that does not fit, CSA_TOO_MANY_FRAGMENTS, and CSCMI_DEVICE_ERROR without a visible device -- decided
+ * before any argument is looked at, with nothing touched.
+ *
+ * Where a task is encoded.  A task that is one non-empty range of one entry, and whose range lies inside ONE RUN of that entry's
+ * slice, is encoded where it lies (gather_stats->inplace_tasks); every other task with a byte in it is gathered into scratch of this
+ * layer (gathered_tasks) -- decided with one division a range, not by walking rows.  The pieces of a fragment lie on the fixed
+ * 16 KiB grid of the PACKED fragment.  A wave stays at most five launches of this layer, st->launches <= 5 * st->waves + 2: in a
+ * wave with at least one piece gathered across a run border (periodic_pieces) the stored pieces, those of one contiguous source
+ * included, go through k_frag_rows with one table of 56 bytes a piece; a wave without one runs k_frag_pieces over 24-byte pieces
+ * exactly as CSAMI_DeviceWriteFrom always did.  st->upload_bytes counts whatever table was sent, and slot [0] of
+ * CSAMI_DeviceWriteKernelMs holds the gather's time either way.  A periodic piece's table entry holds 32-bit quantities whatever
+ * the run is; the stride is an address step and stays 64-bit.  A 16-byte unit of it whose packed bytes lie inside one run is two
+ * aligned 16-byte loads funnel-shifted into one aligned 16-byte store; a unit across a run border is assembled byte by byte.  With
+ * run < 16 every unit crosses a border: that is the slow path (profiles/archive_device_write_slices.md has its measured rate), and
+ * no rate is promised for it.
+ *
+ * Safety contract.  Nothing outside an entry's hull is loaded, not even by an aligned 16-byte window.  Gap bytes inside the hull may
+ * be loaded; they are never summed and never stored.  Nothing of the caller's is written.  The bus contract is CSAMI_DeviceWrite's,
+ * with 56 bytes in the place of 24 for a stored piece of a wave that runs k_frag_rows: no file byte and no stream byte crosses.
+ * Out of scope: delivering a read into a strided destination, CSAMI_DeviceCompare against a slice, updating part of an existing
+ * archive, and the host paths (CSA_Add). */
+typedef struct CSADevGatherStats {
+    uint64_t selected_bytes;    /* sum of run * count: the entries' bytes */
+    uint64_t hull_bytes;        /* sum of the slices' hulls: (count - 1) * stride + run */
+    uint64_t periodic_pieces;   /* pieces gathered across a run border */
+    uint64_t plain_pieces;      /* pieces whose source is one contiguous range: gathered so, or summed where they lie */
+    uint64_t gathered_tasks, inplace_tasks;   /* tasks with a byte in them: gathered into scratch / encoded where they lie */
+} CSADevGatherStats;
+int CSAMI_DeviceWriteSlices(const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices,
+                            CSADevFile *files, uint32_t n_files, const char *arcname,
+                            void *arc_dev, uint64_t arc_cap, const CSAOptions *o,
+                            CSADevWriteStats *st, CSADevGatherStats *gather_stats);
 
 /* YYYYMMDDHHMMSS <-> time_t, csa_common.cpp:3-39 */
 int64_t CSA_DecimalTime(int64_t unix_seconds);
