@@ -95,6 +95,13 @@ class CSADevGatherStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CSADevSpreadStats(C.Structure):
+    _fields_ = [("selected_bytes", C.c_uint64), ("hull_bytes", C.c_uint64), ("periodic_pieces", C.c_uint64), ("plain_pieces", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 LIST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(CSAFrag))
 
 SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", "CSA_ReadIndex",
@@ -104,7 +111,8 @@ SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", 
            "CSAMI_DeviceReadStop", "CSAMI_PlanDeviceStops",
            "CSAMI_DeviceWritePlan", "CSAMI_DeviceWrite", "CSAMI_DeviceWriteKernelMs",
            "CSAMI_CheckBuffers", "CSAMI_DeviceWriteFrom", "CSAMI_DeviceReadInto", "CSAMI_DeviceCompare",
-           "CSAMI_DeviceReadSlices", "CSAMI_PlanDeviceSlices", "CSAMI_DeviceWriteSlices"]
+           "CSAMI_DeviceReadSlices", "CSAMI_PlanDeviceSlices", "CSAMI_DeviceWriteSlices",
+           "CSAMI_CheckSlices", "CSAMI_DeviceReadIntoSlices", "CSAMI_DeviceCompareSlices"]
 
 CSA_MAX_FRAGMENTS = 127
 CSA_TOO_MANY_FRAGMENTS = -94
@@ -201,6 +209,15 @@ def lib():
         L.CSAMI_PlanDeviceSlices.restype = C.c_int
         L.CSAMI_DeviceWriteSlices.argtypes = [ptrs, u64s, slices] + L.CSAMI_DeviceWrite.argtypes[2:] + [C.POINTER(CSADevGatherStats)]
         L.CSAMI_DeviceWriteSlices.restype = C.c_int
+        L.CSAMI_CheckSlices.argtypes = [ptrs, u64s, slices, C.c_uint32, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint32)]
+        L.CSAMI_CheckSlices.restype = C.c_int
+        L.CSAMI_DeviceReadIntoSlices.argtypes = [C.c_void_p, names, C.c_int, ptrs, u64s, slices, C.c_uint32, C.c_uint32, C.POINTER(CSAOptions), files,
+                                                 C.POINTER(CSADevReadStats), C.POINTER(CSADevStopStats), C.POINTER(CSADevSpreadStats)]
+        L.CSAMI_DeviceReadIntoSlices.restype = C.c_int
+        L.CSAMI_DeviceCompareSlices.argtypes = [C.c_void_p, names, C.c_int, ptrs, u64s, slices, C.c_uint32, C.c_uint32, C.POINTER(CSAOptions), files,
+                                                C.POINTER(CSADevDiff), C.POINTER(CSADevReadStats), C.POINTER(CSADevStopStats),
+                                                C.POINTER(CSADevSpreadStats)]
+        L.CSAMI_DeviceCompareSlices.restype = C.c_int
         _lib = L
     return _lib
 
@@ -499,6 +516,20 @@ def check_buffers(ptrs: Sequence[int], sizes: Sequence[int], excl=(0, 0), disjoi
     return rc, (int(bad.value) if rc != 0 else None)
 
 
+def check_slices(ptrs: Sequence[int], sizes: Sequence[int], slices, excl=(0, 0), disjoint: bool = False):
+    """CSAMI_CheckSlices (host only): the address checks extract_into_slices (disjoint) and compare_slices make before anything is
+    launched.  ptrs, sizes: addresses and byte counts of the buffers; slices: (offset, run, stride, count) into each; excl: (address,
+    size) of the range no hull may overlap -> (rc, lowest refused index or None)"""
+    n = len(ptrs)
+    pa, sa = (C.c_void_p * max(n, 1))(*ptrs), (C.c_uint64 * max(n, 1))(*sizes)
+    sl = (CSADevSlice * max(n, 1))()
+    for a, s in zip(sl, slices):
+        a.offset, a.run, a.stride, a.count = s
+    bad = C.c_uint32(0xFFFFFFFF)
+    rc = lib().CSAMI_CheckSlices(pa, sa, sl, n, C.c_void_p(excl[0]), excl[1], int(disjoint), C.byref(bad))
+    return rc, (int(bad.value) if rc != 0 else None)
+
+
 def _is_bytes_tensor(t) -> bool:
     import torch
     return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.dim() == 1
@@ -784,9 +815,79 @@ class DeviceArchive:
         out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(table, files)]
         return rc, {f["name"]: d.as_dict() for f, d in zip(files, diffs)}, out
 
+    def _by_slice(self, bufs, names):
+        """the selection's files table and, per entry of it, the caller's base buffer and the slice of it (None, count 0: verified
+        only).  bufs: {stored name: (1-d contiguous torch.uint8 CUDA base tensor, (offset, length) | (offset, run, stride, count)) |
+        any CUDA tensor tensor_slice takes | None}.  KeyError for a key that is no selected entry."""
+        import torch
+        files = self.plan(names)[0]
+        bufs = dict(bufs)
+        unknown = set(bufs) - {f["name"] for f in files}
+        if unknown:
+            raise KeyError(sorted(unknown)[0])
+        live, table = [], (CSADevSlice * max(len(files), 1))()
+        for a, f in zip(table, files):
+            b = bufs.get(f["name"])
+            if isinstance(b, torch.Tensor):
+                b = tensor_slice(b)
+            if b is not None:
+                t, s = b
+                if not _is_bytes_tensor(t):
+                    raise TypeError("a CUDA tensor, or (a contiguous 1-d torch.uint8 CUDA tensor, slice), or None")
+                a.offset, a.run, a.stride, a.count = (s[0], s[1], s[1], 1 if s[1] else 0) if len(s) == 2 else s
+                b = t
+            live.append(b)
+        ptrs = (C.c_void_p * max(len(live), 1))(*[None if t is None else (t.data_ptr() or self._arc.data_ptr()) for t in live])
+        sizes = (C.c_uint64 * max(len(live), 1))(*[0 if t is None else int(t.numel()) for t in live])
+        return files, live, ptrs, sizes, table
+
+    def extract_into_slices(self, dsts, names: Sequence[str] = (), stop_early=False, **opts):
+        """`csarc x` into strided slices of buffers of the caller's (CSAMI_DeviceReadIntoSlices), the way back of write_slices ->
+        (rc, stats dict); stats["files"] as in extract, and the spread statistics beside the read's.  dsts: {stored name: (base
+        tensor, slice) as write_slices takes them | a CUDA tensor of any dtype that tensor_slice takes -- contiguous, or a view such
+        as t2d[:, c0:c1] | None}; a selected entry that is absent or None is verified only.  The entry's packed bytes go to the bytes
+        the slice selects, which must be at least the entry's size; nothing else of the buffer is stored to.  The selections must not
+        meet each other -- their hulls may interleave, as the column blocks of one matrix do -- and no hull may overlap the archive."""
+        import torch
+        files, live, ptrs, sizes, slices = self._by_slice(dsts, names)
+        arr, n = _names(names)
+        table, st, ss, sp, o = (CSADevFile * max(len(files), 1))(), CSADevReadStats(), CSADevStopStats(), CSADevSpreadStats(), options(**opts)
+        torch.cuda.synchronize()
+        rc = lib().CSAMI_DeviceReadIntoSlices(self._h, arr, n, ptrs, sizes, slices, len(files), CSAMI_DEV_STOP_EARLY if stop_early else 0,
+                                              C.byref(o), table, C.byref(st), C.byref(ss), C.byref(sp))
+        del live
+        out = st.as_dict()
+        if stop_early:
+            out.update(ss.as_dict())
+        out.update(sp.as_dict())
+        out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(table, files)]
+        return rc, out
+
+    def compare_slices(self, srcs, names: Sequence[str] = (), stop_early=False, **opts):
+        """compare against strided slices of buffers of the caller's (CSAMI_DeviceCompareSlices) -> (rc, diffs, stats dict), shaped as
+        compare returns them, with the spread statistics beside the read's.  srcs: as dsts of extract_into_slices; the buffers are only
+        read and may alias each other.  CSA_DIFF_SIZE: the slice does not select exactly the entry's size; first_diff is a packed
+        offset in the entry."""
+        import torch
+        files, live, ptrs, sizes, slices = self._by_slice(srcs, names)
+        arr, n = _names(names)
+        table, st, ss, sp, o = (CSADevFile * max(len(files), 1))(), CSADevReadStats(), CSADevStopStats(), CSADevSpreadStats(), options(**opts)
+        diffs = (CSADevDiff * max(len(files), 1))()
+        torch.cuda.synchronize()
+        rc = lib().CSAMI_DeviceCompareSlices(self._h, arr, n, ptrs, sizes, slices, len(files), CSAMI_DEV_STOP_EARLY if stop_early else 0,
+                                             C.byref(o), table, diffs, C.byref(st), C.byref(ss), C.byref(sp))
+        del live
+        out = st.as_dict()
+        if stop_early:
+            out.update(ss.as_dict())
+        out.update(sp.as_dict())
+        out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(table, files)]
+        return rc, {f["name"]: d.as_dict() for f, d in zip(files, diffs)}, out
+
     def kernel_ms(self):
         """HIP-event milliseconds of the last extract / test by kernel: (k_gather_extents, k_frag_pieces, k_frag_fold); after compare:
-        (k_gather_extents, k_frag_compare, k_frag_fold_diff)"""
+        (k_gather_extents, k_frag_compare, k_frag_fold_diff); k_frag_spread / k_frag_compare_rows in slot [1] where a wave of
+        extract_into_slices / compare_slices ran them"""
         ms = (C.c_double * 3)()
         lib().CSAMI_DeviceKernelMs(self._h, ms)
         return tuple(ms)

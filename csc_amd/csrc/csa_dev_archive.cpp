@@ -27,6 +27,8 @@ using namespace csa;
 // per entry (ReadBufs, dev_read_run): CSAMI_DeviceReadInto hands the caller's pointers in, CSAMI_DeviceRead / ReadStop the layout's
 // offsets into dst, and CSAMI_DeviceCompare the caller's pointers to be compared with instead of stored to.  CSAMI_DeviceReadSlices
 // is that path over a layout that holds only the fragments its slices touch (dev_layout), with k_frag_slices as the middle kernel.
+// The caller's side of an entry is a slice of a buffer (CSAMI_DeviceReadIntoSlices, CSAMI_DeviceCompareSlices; a whole buffer in the
+// other calls): a wave in which a piece's side is the runs of a periodic pattern runs k_frag_spread / k_frag_compare_rows.
 // ---------------------------------------------------------------------------------------------
 struct CSADevArchive {
     const uint8_t *arc = nullptr;
@@ -254,15 +256,55 @@ struct FragTables {
         for (const csadev::GatherPiece &g : gpieces) pieces.push_back(csadev::CopyPiece{g.src, g.dst, g.len, 0});
         gpieces.clear();
     }
+    // The read paths over the caller's buffers, in the place of add() and `pieces`: the fragment's delivered bytes are the packed
+    // bytes [posfile, posfile + size) of its entry, whose side in the caller's buffer `buf` (NULL: none) is what the (checked) slice sl
+    // selects of it.  The leading `use` <= size bytes have that side -- all of them where they are stored, the compared ones with
+    // `compare` -- and the rest is summed only.  Each 16 KiB cell is planned as the write plans it (gather_reduce).
+    std::vector<csadev::SpreadPiece> xpieces;
+    uint64_t xperiodic = 0;
+    bool add_spread(const uint8_t *src, uint8_t *buf, const csadev::Slice &sl, uint64_t posfile, uint64_t size, uint32_t checksum,
+                    uint64_t use, bool compare, CSADevSpreadStats &X)
+    {
+        using namespace csadev;
+        const uint64_t np = piece_count(size, kFragPiece);
+        if (xpieces.size() + np > 0x7FFFFFFFull) return false;
+        frags.push_back(FragFold{size, (uint32_t)xpieces.size(), (uint32_t)np, checksum, 0});
+        if (!buf) use = 0;
+        const uint8_t *lo = use ? buf + sl.offset : nullptr, *hi = use ? lo + (sl.count - 1) * sl.stride + sl.run : nullptr;
+        for (uint64_t off = 0; off < size; off += kFragPiece) {
+            const uint32_t len = (uint32_t)std::min<uint64_t>(size - off, kFragPiece);
+            const uint32_t u = (uint32_t)(use > off ? std::min<uint64_t>(use - off, len) : 0);
+            SpreadPiece sp = {src + off, nullptr, 0, len, 0, 0, 0, nullptr, nullptr};
+            if (u) {
+                GatherCut c;
+                const bool whole = gather_reduce(sl, posfile + off, u, c);
+                sp.dst = buf + c.src;
+                sp.cmp = compare ? u : 0;
+                if (!whole) { sp.stride = c.stride; sp.phase = c.phase; sp.run = c.run; sp.lo = lo; sp.hi = hi; xperiodic++; }
+            }
+            (sp.stride ? X.periodic_pieces : X.plain_pieces)++;
+            xpieces.push_back(sp);
+        }
+        return true;
+    }
+    // no piece of `xpieces` is periodic: they become the CopyPieces they are, for k_frag_pieces / k_frag_compare
+    void spread_as_plain()
+    {
+        pieces.reserve(xpieces.size());
+        for (const csadev::SpreadPiece &x : xpieces) pieces.push_back(csadev::CopyPiece{x.src, x.dst, x.len, x.cmp});
+        xpieces.clear();
+    }
     uint64_t upload_bytes() const
     {
-        return gpieces.size() * sizeof(csadev::GatherPiece) + pieces.size() * sizeof(csadev::CopyPiece) + frags.size() * sizeof(csadev::FragFold);
+        return gpieces.size() * sizeof(csadev::GatherPiece) + xpieces.size() * sizeof(csadev::SpreadPiece) + pieces.size() * sizeof(csadev::CopyPiece)
+               + frags.size() * sizeof(csadev::FragFold);
     }
     bool upload(bool compare = false)
     {
-        const size_t np = pieces.size() + spieces.size() + gpieces.size();   // (spieces, or pieces with gpieces in front of them)
-        return (spieces.empty() ? d_pieces.upload(pieces.data(), pieces.size() * sizeof(csadev::CopyPiece))
-                                : d_pieces.upload(spieces.data(), spieces.size() * sizeof(csadev::SlicePiece)))
+        const size_t np = pieces.size() + spieces.size() + gpieces.size() + xpieces.size();   // (spieces, or xpieces, or pieces with gpieces in front of them)
+        return (!xpieces.empty() ? d_pieces.upload(xpieces.data(), xpieces.size() * sizeof(csadev::SpreadPiece))
+                : spieces.empty() ? d_pieces.upload(pieces.data(), pieces.size() * sizeof(csadev::CopyPiece))
+                                  : d_pieces.upload(spieces.data(), spieces.size() * sizeof(csadev::SlicePiece)))
                && (gpieces.empty() || d_gpieces.upload(gpieces.data(), gpieces.size() * sizeof(csadev::GatherPiece)))
                && d_frags.upload(frags.data(), frags.size() * sizeof(csadev::FragFold))
                && d_sums.alloc(np * sizeof(csadev::PieceSums))
@@ -291,6 +333,9 @@ struct ReadBufs {
     const uint64_t *lim = nullptr;             // compare: per entry, the bytes that are compared -- min(the entry's size, the caller's)
     CSADevDiff *diffs = nullptr;               // compare: per entry; first_diff, CSA_DIFF_BYTES and CSA_DIFF_SHORT are added here
     CSADevSliceStats *slice_stats = nullptr;   // slices (a layout with L.sliced, never null there): ptrs[i] takes entry i's packed slice, and the piece counts are added here
+    const csadev::Slice *bslices = nullptr;    // per entry, checked: what of the caller's buffer ptrs[i][0, bsizes[i]) is the entry's side -- the packed bytes it
+    const uint64_t *bsizes = nullptr;          // selects take the entry (a layout with L.sliced: its packed slice); count 0: nothing, as where ptrs[i] is NULL
+    CSADevSpreadStats *spread = nullptr;       // never null without L.sliced: the piece counts are added here
     uint8_t *at(uint32_t file) const { return ptrs ? ptrs[file] : nullptr; }
 };
 
@@ -410,18 +455,25 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
             if (!n) continue;
             const uint8_t *src = (const uint8_t *)d_raw.p + raw_off[k] + f.posblock;
             if (!(L.sliced ? T.add_sliced(src, p, L.slices[f.file], f.posfile, n, f.checksum, *B.slice_stats)
-                           : T.add(src, p ? p + f.posfile : nullptr, n, f.checksum, cmp))) return CSCMI_DEVICE_ERROR;
+                           : T.add_spread(src, p, B.bslices[f.file], f.posfile, n, f.checksum, B.diffs ? cmp : n, B.diffs != nullptr, *B.spread)))
+                return CSCMI_DEVICE_ERROR;
             ff_file.push_back(f.file);
             ff_posfile.push_back(f.posfile);
             store = store || p;
         }
     }
     // (both launches even when no fragment was delivered: a wave is always the same three)
+    // a wave with a periodic piece sends all its pieces through k_frag_spread / k_frag_compare_rows with one table; any other runs
+    // k_frag_pieces / k_frag_compare over CopyPieces
+    const bool rows = T.xperiodic > 0;
+    if (!rows) T.spread_as_plain();
     std::vector<FragResult> res;
     if (B.diffs) {
         std::vector<FragDiff> rd;
         if (!T.upload(true)
-            || !tm.timed(&A.kernel_ms[1], S.launches, [&] { launch_frag_compare(T.d_pieces.p, T.d_sums.p, T.d_firsts.p, (uint32_t)T.pieces.size(), tm.st); })
+            || !tm.timed(&A.kernel_ms[1], S.launches, [&] {
+                   if (rows) launch_frag_compare_rows(T.d_pieces.p, T.d_sums.p, T.d_firsts.p, (uint32_t)T.xpieces.size(), tm.st);
+                   else launch_frag_compare(T.d_pieces.p, T.d_sums.p, T.d_firsts.p, (uint32_t)T.pieces.size(), tm.st); })
             || !T.fold_diff(tm, &A.kernel_ms[2], S.launches, rd)) return CSCMI_DEVICE_ERROR;
         S.readback_bytes += rd.size() * sizeof(FragDiff);
         for (size_t i = 0; i < rd.size(); i++) {
@@ -435,6 +487,7 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
         if (!T.upload()
             || !tm.timed(&A.kernel_ms[1], S.launches, [&] {
                    if (L.sliced) launch_frag_slices(T.d_pieces.p, T.d_sums.p, (uint32_t)T.spieces.size(), tm.st);
+                   else if (rows) launch_frag_spread(T.d_pieces.p, T.d_sums.p, (uint32_t)T.xpieces.size(), tm.st);
                    else launch_frag_pieces(T.d_pieces.p, T.d_sums.p, (uint32_t)T.pieces.size(), store, tm.st); })
             || !T.fold(tm, &A.kernel_ms[2], S.launches, res)) return CSCMI_DEVICE_ERROR;
         S.readback_bytes += res.size() * sizeof(FragResult);
@@ -508,25 +561,35 @@ int CSAMI_DevicePlan(CSADevArchive *a, const char *const *names, int nnames,
 
 namespace {
 
-// false where CSAMI_CheckBuffers refuses the caller's buffers: sizes[i] bytes at B.ptrs[i], nothing where that is NULL
-bool dev_bufs_ok(const CSADevArchive *a, const DevLayout &L, const ReadBufs &B, const uint64_t *sizes, bool disjoint)
+// whole-buffer slices: entry i's side is all of a buffer of bytes[i] bytes
+void whole_slices(const uint64_t *bytes, size_t n, std::vector<csadev::Slice> &out)
 {
-    if (!B.ptrs) return true;
-    std::vector<uint64_t> touched(L.files.size());
-    for (size_t i = 0; i < L.files.size(); i++) touched[i] = B.ptrs[i] ? sizes[i] : 0;
-    return CSAMI_CheckBuffers((const void *const *)B.ptrs, touched.data(), (uint32_t)L.files.size(), a->arc, a->arc_size, disjoint, nullptr) == 0;
+    out.assign(n, csadev::Slice{0, 0, 0, 0});
+    for (size_t i = 0; i < n; i++)
+        if (bytes[i]) out[i] = csadev::Slice{0, bytes[i], bytes[i], 1};
 }
 
-// The one read path below CSAMI_DeviceReadInto, CSAMI_DeviceReadSlices, CSAMI_DeviceCompare, CSAMI_DeviceRead and CSAMI_DeviceReadStop: the address checks,
-// then the waves.  sizes[i] are the bytes of B.ptrs[i] that may be touched (ignored where that is NULL); `disjoint`: they are
-// written, so no two may overlap.  ss: stop every task behind its last selected byte, and add to *ss.  `failed` gets one count per
-// entry.  -1 with nothing launched where CSAMI_CheckBuffers refuses the buffers.
-int dev_read_run(CSADevArchive *a, const DevLayout &L, const ReadBufs &B, const uint64_t *sizes, bool disjoint, const CSAOptions *opt,
+// false where CSAMI_CheckSlices refuses the caller's buffers: the slice B.bslices[i] of B.ptrs[i], nothing where that is NULL
+bool dev_bufs_ok(const CSADevArchive *a, const DevLayout &L, const ReadBufs &B, bool disjoint)
+{
+    if (!B.ptrs) return true;
+    std::vector<CSADevSlice> sl(L.files.size(), CSADevSlice{0, 0, 0, 0});
+    for (size_t i = 0; i < L.files.size(); i++)
+        if (B.ptrs[i]) sl[i] = CSADevSlice{B.bslices[i].offset, B.bslices[i].run, B.bslices[i].stride, B.bslices[i].count};
+    return CSAMI_CheckSlices((const void *const *)B.ptrs, B.bsizes, sl.data(), (uint32_t)L.files.size(), a->arc, a->arc_size, disjoint, nullptr) == 0;
+}
+
+// The one read path below CSAMI_DeviceReadIntoSlices, CSAMI_DeviceCompareSlices, CSAMI_DeviceReadInto, CSAMI_DeviceReadSlices, CSAMI_DeviceCompare,
+// CSAMI_DeviceRead and CSAMI_DeviceReadStop: the address checks, then the waves.  B.bslices[i] selects the bytes of B.ptrs[i] that
+// may be touched (ignored where that is NULL); `disjoint`: they are written, so no two selections may meet.  ss: stop every task
+// behind its last selected byte, and add to *ss.  `failed` gets one count per entry.  -1 with nothing launched where
+// CSAMI_CheckSlices refuses the buffers.
+int dev_read_run(CSADevArchive *a, const DevLayout &L, const ReadBufs &B, bool disjoint, const CSAOptions *opt,
                  std::vector<uint32_t> &failed, CSADevReadStats &S, CSADevStopStats *ss)
 {
     const double t0 = now_s();
     failed.assign(L.files.size(), 0);
-    if (!dev_bufs_ok(a, L, B, sizes, disjoint)) return -1;
+    if (!dev_bufs_ok(a, L, B, disjoint)) return -1;
     CSAOptions o;
     if (opt) o = *opt; else CSA_OptionsInit(&o);
     a->kernel_ms[0] = a->kernel_ms[1] = a->kernel_ms[2] = 0;
@@ -580,27 +643,87 @@ int dev_read(CSADevArchive *a, const char *const *names, int nnames, void *dst, 
     std::vector<uint8_t *> ptrs(L.files.size());
     std::vector<uint64_t> sizes(L.files.size());
     for (size_t i = 0; i < L.files.size(); i++) { ptrs[i] = dst ? (uint8_t *)dst + L.files[i].offset : nullptr; sizes[i] = L.files[i].size; }
+    std::vector<csadev::Slice> bs;
+    whole_slices(sizes.data(), sizes.size(), bs);
+    CSADevSpreadStats X;
+    memset(&X, 0, sizeof(X));
     ReadBufs B;
     if (dst) B.ptrs = ptrs.data();
+    B.bslices = bs.data(); B.bsizes = sizes.data(); B.spread = &X;
     std::vector<uint32_t> failed;
-    const int rc = dev_read_run(a, L, B, sizes.data(), true, opt, failed, S, ss);
+    const int rc = dev_read_run(a, L, B, true, opt, failed, S, ss);
     for (size_t i = 0; files && i < failed.size() && i < cap; i++) files[i].failed_frags = failed[i];
     if (st) *st = S;
     return rc;
 }
 
-// What CSAMI_DeviceReadInto and CSAMI_DeviceCompare share in front of dev_read_run: the refusal without a device, the zeroed
-// statistics, the layout, n, the files table with offset 0.  0 to go on.
-int dev_into_begin(CSADevArchive *a, const char *const *names, int nnames, uint32_t n, CSADevFile *files, CSADevReadStats *st,
-                   CSADevStopStats *stop_stats, DevLayout &L)
+// CSAMI_DeviceReadIntoSlices (diffs == nullptr) and CSAMI_DeviceCompareSlices (compare; diffs may still be NULL, which is refused):
+// the refusal without a device, the zeroed statistics, the layout, n, the files table with offset 0, the slices, dev_read_run.
+// `whole` (CSAMI_DeviceReadInto, CSAMI_DeviceCompare): `slices` is not looked at -- entry i's side is the first size_i bytes of a buffer
+// of sizes[i] (the read), or all sizes[i] bytes of it (the comparison).
+int dev_into(CSADevArchive *a, const char *const *names, int nnames, const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices,
+             bool whole, uint32_t n, uint32_t flags, const CSAOptions *opt, CSADevFile *files, bool compare, CSADevDiff *diffs, CSADevReadStats *st,
+             CSADevStopStats *stop_stats, CSADevSpreadStats *spread_stats)
 {
     if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;               // (before anything of the caller's is touched)
     if (st) memset(st, 0, sizeof(*st));
     if (stop_stats) memset(stop_stats, 0, sizeof(*stop_stats));
+    if (spread_stats) memset(spread_stats, 0, sizeof(*spread_stats));
+    DevLayout L;
     if (!a || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L) || L.files.size() != n) return -1;
     dev_fill_files(L, files, n);
     for (uint32_t i = 0; files && i < n; i++) files[i].offset = 0;
-    return 0;
+    if (n && ((!whole && (!slices || !sizes)) || (compare && (!diffs || (ptrs && !sizes))))) return -1;
+    // the slices, each inside its buffer; the bytes each selects
+    std::vector<csadev::Slice> bs(n, csadev::Slice{0, 0, 0, 0});
+    std::vector<uint64_t> bsz(n, 0), sel(n, 0), lim(n, 0);
+    CSADevSpreadStats X;
+    memset(&X, 0, sizeof(X));
+    for (uint32_t i = 0; i < n; i++) {
+        if (!ptrs || !ptrs[i]) continue;
+        const uint64_t size = L.files[i].size;
+        if (whole) {
+            if (!compare && (!sizes || sizes[i] < size)) return WRITE_ERROR;
+            bsz[i] = sizes[i];
+            sel[i] = compare ? sizes[i] : size;
+            if (sel[i]) bs[i] = csadev::Slice{0, sel[i], sel[i], 1};
+        } else {
+            bs[i] = csadev::Slice{slices[i].offset, slices[i].run, slices[i].stride, slices[i].count};
+            bsz[i] = sizes[i];
+            if (!csadev::slice_check(bs[i], bsz[i], &sel[i])) return -1;
+        }
+    }
+    for (uint32_t i = 0; i < n; i++) {
+        const bool have = ptrs && ptrs[i];
+        const uint64_t size = L.files[i].size;
+        if (have && !compare && sel[i] < size) return WRITE_ERROR;           // a destination too short for its entry
+        lim[i] = std::min(size, sel[i]);
+        const uint64_t hull = bs[i].count ? (bs[i].count - 1) * bs[i].stride + bs[i].run : 0;      // (checked by slice_check)
+        if (!add_ok(X.selected_bytes, lim[i], &X.selected_bytes)) X.selected_bytes = UINT64_MAX;      // (statistics only: they saturate)
+        if (!add_ok(X.hull_bytes, hull, &X.hull_bytes)) X.hull_bytes = UINT64_MAX;
+    }
+    for (uint32_t i = 0; compare && i < n; i++) {
+        const bool have = ptrs && ptrs[i];
+        diffs[i].first_diff = UINT64_MAX;
+        diffs[i].status = !have ? CSA_DIFF_SKIPPED : sel[i] != L.files[i].size ? CSA_DIFF_SIZE : 0u;
+        diffs[i].failed_frags = 0;
+    }
+    ReadBufs B;
+    B.ptrs = (uint8_t *const *)ptrs;                                       // (k_frag_compare / k_frag_compare_rows only load from them)
+    B.bslices = bs.data(); B.bsizes = bsz.data(); B.spread = &X;
+    if (compare) { B.lim = lim.data(); B.diffs = diffs; }
+    if (!dev_bufs_ok(a, L, B, !compare)) return -1;                         // (here too, so that a refusal leaves *spread_stats zeroed)
+    CSADevReadStats S;
+    CSADevStopStats SS;
+    memset(&S, 0, sizeof(S));
+    memset(&SS, 0, sizeof(SS));
+    std::vector<uint32_t> failed;
+    const int rc = dev_read_run(a, L, B, !compare, opt, failed, S, (flags & CSAMI_DEV_STOP_EARLY) ? &SS : nullptr);
+    for (uint32_t i = 0; i < n; i++) { if (compare) diffs[i].failed_frags = failed[i]; if (files) files[i].failed_frags = failed[i]; }
+    if (st) *st = S;
+    if (stop_stats) *stop_stats = SS;
+    if (spread_stats) *spread_stats = X;
+    return rc;
 }
 
 }   // namespace
@@ -652,62 +775,80 @@ int CSAMI_DeviceReadStop(CSADevArchive *a, const char *const *names, int nnames,
     return rc;
 }
 
+int CSAMI_CheckSlices(const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices, uint32_t n, const void *excl, uint64_t excl_size,
+                      int disjoint, uint32_t *bad)
+{
+    uint32_t worst = UINT32_MAX;
+    const uint64_t e0 = (uint64_t)(uintptr_t)excl;
+    struct H { uint64_t lo, hi, run, stride; uint32_t i; bool rows; };     // the hull [lo, hi]: hi is its last byte; rows: count > 1
+    std::vector<H> hs;
+    for (uint32_t i = 0; n && ptrs && sizes && slices && i < n; i++) {
+        csadev::Slice s = {slices[i].offset, slices[i].run, slices[i].stride, slices[i].count};
+        uint64_t bytes, lo;
+        if (!csadev::slice_check(s, sizes[i], &bytes)) { worst = std::min(worst, i); continue; }
+        if (!s.count) continue;
+        const uint64_t hull = (s.count - 1) * s.stride + s.run;           // (checked by slice_check)
+        if (!ptrs[i] || !add_ok((uint64_t)(uintptr_t)ptrs[i], s.offset, &lo)) { worst = std::min(worst, i); continue; }
+        const uint64_t hi = lo + (hull - 1);
+        const bool hits = excl_size && lo <= e0 + (excl_size - 1) && e0 <= hi;
+        if (hi < lo || hits) { worst = std::min(worst, i); continue; }
+        if (disjoint) hs.push_back(H{lo, hi, s.run, s.stride, i, s.count > 1});
+    }
+    if (n && (!ptrs || !sizes || !slices)) worst = 0;
+    // Two hulls that overlap are apart only where their selected bytes provably do not meet: under one stride S (a slice of one run
+    // takes the other's) A selects addresses of residues [a, a + run_A) and B of [a + d, a + d + run_B) modulo S, so d >= run_A and
+    // d + run_B <= S keeps them apart -- column blocks of one matrix, a byte range inside one gap.  No walk over the rows.
+    auto apart = [](const H &A, const H &B) {
+        if ((!A.rows && !B.rows) || (A.rows && B.rows && A.stride != B.stride)) return false;
+        const uint64_t S = A.rows ? A.stride : B.stride;
+        const uint64_t d = (B.lo - A.lo) % S;                              // (the sweep hands the hull with the lower start in as A)
+        return d >= A.run && B.run <= S && d <= S - B.run;
+    };
+    // hulls in address order; `open` holds those that reach the one at hand, each of which overlaps it: a hull is dropped from it
+    // once, and otherwise costs one look per overlapping pair
+    std::sort(hs.begin(), hs.end(), [](const H &a, const H &b) { return a.lo != b.lo ? a.lo < b.lo : a.i < b.i; });
+    std::vector<size_t> open;
+    for (size_t k = 0; k < hs.size(); k++) {
+        size_t w = 0;
+        for (size_t j : open) {
+            if (hs[j].hi < hs[k].lo) continue;
+            open[w++] = j;
+            if (!apart(hs[j], hs[k])) worst = std::min(worst, std::min(hs[j].i, hs[k].i));
+        }
+        open.resize(w);
+        open.push_back(k);
+    }
+    if (worst == UINT32_MAX) return 0;
+    if (bad) *bad = worst;
+    return -1;
+}
+
+int CSAMI_DeviceReadIntoSlices(CSADevArchive *a, const char *const *names, int nnames, void *const *ptrs, const uint64_t *sizes,
+                               const CSADevSlice *slices, uint32_t n, uint32_t flags, const CSAOptions *opt, CSADevFile *files,
+                               CSADevReadStats *st, CSADevStopStats *stop_stats, CSADevSpreadStats *spread_stats)
+{
+    return dev_into(a, names, nnames, (const void *const *)ptrs, sizes, slices, false, n, flags, opt, files, false, nullptr, st, stop_stats, spread_stats);
+}
+
+int CSAMI_DeviceCompareSlices(CSADevArchive *a, const char *const *names, int nnames, const void *const *ptrs, const uint64_t *sizes,
+                              const CSADevSlice *slices, uint32_t n, uint32_t flags, const CSAOptions *opt, CSADevFile *files,
+                              CSADevDiff *diffs, CSADevReadStats *st, CSADevStopStats *stop_stats, CSADevSpreadStats *spread_stats)
+{
+    return dev_into(a, names, nnames, ptrs, sizes, slices, false, n, flags, opt, files, true, diffs, st, stop_stats, spread_stats);
+}
+
+// the two calls above with whole-buffer slices
 int CSAMI_DeviceReadInto(CSADevArchive *a, const char *const *names, int nnames, void *const *ptrs, const uint64_t *caps, uint32_t n,
                          uint32_t flags, const CSAOptions *opt, CSADevFile *files, CSADevReadStats *st, CSADevStopStats *stop_stats)
 {
-    DevLayout L;
-    int rc = dev_into_begin(a, names, nnames, n, files, st, stop_stats, L);
-    if (rc) return rc;
-    std::vector<uint64_t> sizes(n);
-    for (uint32_t i = 0; i < n; i++) {
-        sizes[i] = L.files[i].size;
-        if (ptrs && ptrs[i] && (!caps || caps[i] < sizes[i])) return WRITE_ERROR;
-    }
-    ReadBufs B;
-    B.ptrs = (uint8_t *const *)ptrs;
-    CSADevReadStats S;
-    CSADevStopStats SS;
-    memset(&S, 0, sizeof(S));
-    memset(&SS, 0, sizeof(SS));
-    std::vector<uint32_t> failed;
-    rc = dev_read_run(a, L, B, sizes.data(), true, opt, failed, S, (flags & CSAMI_DEV_STOP_EARLY) ? &SS : nullptr);
-    for (uint32_t i = 0; files && i < n; i++) files[i].failed_frags = failed[i];
-    if (st) *st = S;
-    if (stop_stats) *stop_stats = SS;
-    return rc;
+    return dev_into(a, names, nnames, (const void *const *)ptrs, caps, nullptr, true, n, flags, opt, files, false, nullptr, st, stop_stats, nullptr);
 }
 
 int CSAMI_DeviceCompare(CSADevArchive *a, const char *const *names, int nnames, const void *const *ptrs, const uint64_t *sizes, uint32_t n,
                         uint32_t flags, const CSAOptions *opt, CSADevFile *files, CSADevDiff *diffs, CSADevReadStats *st,
                         CSADevStopStats *stop_stats)
 {
-    DevLayout L;
-    int rc = dev_into_begin(a, names, nnames, n, files, st, stop_stats, L);
-    if (rc) return rc;
-    if (n && (!diffs || (ptrs && !sizes))) return -1;
-    std::vector<uint64_t> lim(n), given(n);
-    for (uint32_t i = 0; i < n; i++) {
-        const bool have = ptrs && ptrs[i];
-        given[i] = have ? sizes[i] : 0;
-        lim[i] = std::min<uint64_t>(L.files[i].size, given[i]);
-        diffs[i].first_diff = UINT64_MAX;
-        diffs[i].status = !have ? CSA_DIFF_SKIPPED : given[i] != L.files[i].size ? CSA_DIFF_SIZE : 0u;
-        diffs[i].failed_frags = 0;
-    }
-    ReadBufs B;
-    B.ptrs = (uint8_t *const *)ptrs;                                       // (k_frag_compare only loads from them)
-    B.lim = lim.data();
-    B.diffs = diffs;
-    CSADevReadStats S;
-    CSADevStopStats SS;
-    memset(&S, 0, sizeof(S));
-    memset(&SS, 0, sizeof(SS));
-    std::vector<uint32_t> failed;
-    rc = dev_read_run(a, L, B, given.data(), false, opt, failed, S, (flags & CSAMI_DEV_STOP_EARLY) ? &SS : nullptr);
-    for (uint32_t i = 0; i < n; i++) { diffs[i].failed_frags = failed[i]; if (files) files[i].failed_frags = failed[i]; }
-    if (st) *st = S;
-    if (stop_stats) *stop_stats = SS;
-    return rc;
+    return dev_into(a, names, nnames, ptrs, sizes, nullptr, true, n, flags, opt, files, true, diffs, st, stop_stats, nullptr);
 }
 
 int CSAMI_DeviceReadSlices(CSADevArchive *a, const char *const *names, int nnames, const CSADevSlice *slices, void *const *ptrs,
@@ -730,16 +871,19 @@ int CSAMI_DeviceReadSlices(CSADevArchive *a, const char *const *names, int nname
         if (ptrs && ptrs[i] && (!caps || caps[i] < L.slice_bytes[i])) return WRITE_ERROR;
         if (!add_ok(SL.selected_bytes, L.slice_bytes[i], &SL.selected_bytes)) return -1;
     }
+    std::vector<csadev::Slice> bs;
+    whole_slices(L.slice_bytes.data(), L.slice_bytes.size(), bs);
     ReadBufs B;
     B.ptrs = (uint8_t *const *)ptrs;
+    B.bslices = bs.data(); B.bsizes = L.slice_bytes.data();
     B.slice_stats = &SL;
     CSADevReadStats S;
     CSADevStopStats SS;
     memset(&S, 0, sizeof(S));
     memset(&SS, 0, sizeof(SS));
     std::vector<uint32_t> failed;
-    if (!dev_bufs_ok(a, L, B, L.slice_bytes.data(), true)) return -1;      // (here too, so that a refusal leaves *slice_stats zeroed)
-    const int rc = dev_read_run(a, L, B, L.slice_bytes.data(), true, opt, failed, S, (flags & CSAMI_DEV_STOP_EARLY) ? &SS : nullptr);
+    if (!dev_bufs_ok(a, L, B, true)) return -1;      // (here too, so that a refusal leaves *slice_stats zeroed)
+    const int rc = dev_read_run(a, L, B, true, opt, failed, S, (flags & CSAMI_DEV_STOP_EARLY) ? &SS : nullptr);
     for (uint32_t i = 0; files && i < n; i++) files[i].failed_frags = failed[i];
     if (st) *st = S;
     if (stop_stats) *stop_stats = SS;

@@ -18,6 +18,9 @@
 //                         entry's slice selects -- all, none, or the runs of a periodic pattern -- go to their packed places
 //   k_frag_rows           k_frag_pieces<true> for CSAMI_DeviceWriteSlices, the transpose of k_frag_slices: a piece's destination is
 //                         contiguous and its source is the runs of a periodic pattern in the caller's buffer (or one range of it)
+//   k_frag_spread         k_frag_pieces<true> for CSAMI_DeviceReadIntoSlices, the transpose of k_frag_rows: a piece's source is contiguous
+//                         and its destination is the runs of a periodic pattern in the caller's buffer (or one range of it, or none)
+//   k_frag_compare_rows   k_frag_compare for CSAMI_DeviceCompareSlices: the piece against such rows instead of one range
 //   k_block_table         one lane per task stream of a wave (write only): the archive-block table AsyncWriter would have made of
 //                         the encoder's Write calls (csa_io.h:145-201), read off the stream's framing (csa_dev_write.h)
 //
@@ -68,15 +71,9 @@ __global__ __launch_bounds__(kThreads) void k_frag_pieces(const CopyPiece *piece
     store_sums(a, b, out + blockIdx.x);
 }
 
-// k_frag_pieces<true> with two loads in the place of a load and a store: the piece's first `cmp` bytes against the caller's
-// (compare_piece, csa_dev_read.h), and the smallest differing index of the workgroup reduced the way the sums are
-__global__ __launch_bounds__(kThreads) void k_frag_compare(const CopyPiece *pieces, PieceSums *out, uint32_t *first_out, uint32_t npieces)
+// the workgroup's a and b added up, and its smallest differing index, stored as its piece's (len: the piece's, where no thread saw one)
+__device__ inline void store_sums_first(uint64_t a, uint64_t b, uint32_t first, uint32_t len, PieceSums *out, uint32_t *first_out)
 {
-    if (blockIdx.x >= npieces) return;
-    const CopyPiece pc = pieces[blockIdx.x];
-    uint64_t a = 0, b = 0;
-    uint32_t first;
-    compare_piece(pc.src, pc.dst, pc.len, pc.dst ? pc.cmp : 0u, threadIdx.x, kThreads, a, b, first);
     for (int off = 32; off > 0; off >>= 1) {
         a += __shfl_down(a, off, 64);
         b += __shfl_down(b, off, 64);
@@ -90,11 +87,23 @@ __global__ __launch_bounds__(kThreads) void k_frag_compare(const CopyPiece *piec
     __syncthreads();
     if (threadIdx.x == 0) {
         PieceSums s = {0, 0};
-        uint32_t f = pc.len;
+        uint32_t f = len;
         for (uint32_t w = 0; w < kThreads / 64; w++) { s.a += red[2 * w]; s.b += red[2 * w + 1]; f = redf[w] < f ? redf[w] : f; }
-        out[blockIdx.x] = s;
-        first_out[blockIdx.x] = f;
+        *out = s;
+        *first_out = f;
     }
+}
+
+// k_frag_pieces<true> with two loads in the place of a load and a store: the piece's first `cmp` bytes against the caller's
+// (compare_piece, csa_dev_read.h), and the smallest differing index of the workgroup reduced the way the sums are
+__global__ __launch_bounds__(kThreads) void k_frag_compare(const CopyPiece *pieces, PieceSums *out, uint32_t *first_out, uint32_t npieces)
+{
+    if (blockIdx.x >= npieces) return;
+    const CopyPiece pc = pieces[blockIdx.x];
+    uint64_t a = 0, b = 0;
+    uint32_t first;
+    compare_piece(pc.src, pc.dst, pc.len, pc.dst ? pc.cmp : 0u, threadIdx.x, kThreads, a, b, first);
+    store_sums_first(a, b, first, pc.len, out + blockIdx.x, first_out + blockIdx.x);
 }
 
 // k_frag_pieces<true> for CSAMI_DeviceReadSlices: a piece that lies inside one run of its entry's slice, or holds no selected byte, is
@@ -122,6 +131,33 @@ __global__ __launch_bounds__(kThreads) void k_frag_rows(const GatherPiece *piece
     if (pc.stride) gather_sum(pc, threadIdx.x, kThreads, a, b);
     else copy_sum<true, true>(pc.dst, pc.src, pc.len, threadIdx.x, kThreads, a, b);
     store_sums(a, b, out + blockIdx.x);
+}
+
+// k_frag_pieces<true> for CSAMI_DeviceReadIntoSlices: a piece whose packed bytes go to one range of the caller's buffer, or to none, is
+// copy_sum's as there; any other is spread across the run borders (spread_sum, csa_dev_read.h).  Which of the three: the same for
+// the whole workgroup.
+__global__ __launch_bounds__(kThreads) void k_frag_spread(const SpreadPiece *pieces, PieceSums *out, uint32_t npieces)
+{
+    if (blockIdx.x >= npieces) return;
+    const SpreadPiece pc = pieces[blockIdx.x];
+    uint64_t a = 0, b = 0;
+    if (pc.stride) spread_sum(pc, threadIdx.x, kThreads, a, b);
+    else if (pc.dst == nullptr) copy_sum<false, true>(nullptr, pc.src, pc.len, threadIdx.x, kThreads, a, b);
+    else copy_sum<true, true>(pc.dst, pc.src, pc.len, threadIdx.x, kThreads, a, b);
+    store_sums(a, b, out + blockIdx.x);
+}
+
+// k_frag_compare for CSAMI_DeviceCompareSlices: a piece whose compared bytes lie in one range of the caller's buffer, or that is
+// summed only, is compare_piece's as there; any other is compared across the run borders (compare_rows, csa_dev_read.h).
+__global__ __launch_bounds__(kThreads) void k_frag_compare_rows(const SpreadPiece *pieces, PieceSums *out, uint32_t *first_out, uint32_t npieces)
+{
+    if (blockIdx.x >= npieces) return;
+    const SpreadPiece pc = pieces[blockIdx.x];
+    uint64_t a = 0, b = 0;
+    uint32_t first;
+    if (pc.stride) compare_rows(pc, threadIdx.x, kThreads, a, b, first);
+    else compare_piece(pc.src, pc.dst, pc.len, pc.dst ? pc.cmp : 0u, threadIdx.x, kThreads, a, b, first);
+    store_sums_first(a, b, first, pc.len, out + blockIdx.x, first_out + blockIdx.x);
 }
 
 __global__ __launch_bounds__(kThreads) void k_frag_fold(const FragFold *frags, const PieceSums *sums, FragResult *out, uint32_t nfrags)
@@ -176,6 +212,16 @@ void launch_frag_slices(const void *pieces, void *sums, uint32_t npieces, hipStr
 void launch_frag_rows(const void *pieces, void *sums, uint32_t npieces, hipStream_t st)
 {
     hipLaunchKernelGGL(k_frag_rows, dim3(npieces ? npieces : 1), dim3(kThreads), 0, st, (const GatherPiece *)pieces, (PieceSums *)sums, npieces);
+}
+
+void launch_frag_spread(const void *pieces, void *sums, uint32_t npieces, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_frag_spread, dim3(npieces ? npieces : 1), dim3(kThreads), 0, st, (const SpreadPiece *)pieces, (PieceSums *)sums, npieces);
+}
+
+void launch_frag_compare_rows(const void *pieces, void *sums, void *firsts, uint32_t npieces, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_frag_compare_rows, dim3(npieces ? npieces : 1), dim3(kThreads), 0, st, (const SpreadPiece *)pieces, (PieceSums *)sums, (uint32_t *)firsts, npieces);
 }
 
 void launch_frag_fold(const void *frags, const void *sums, void *out, uint32_t nfrags, hipStream_t st)

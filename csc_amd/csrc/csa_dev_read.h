@@ -19,6 +19,10 @@
 // CSAMI_DeviceReadSlices runs them with k_frag_slices in the middle: slice_check / slice_next / slice_reduce are its planner's,
 // slice_sum the piece that is summed whole and stored in part (tests/model/csa_dev_slice_model.cpp is their model).
 //
+// CSAMI_DeviceReadIntoSlices and CSAMI_DeviceCompareSlices run them with k_frag_spread / k_frag_compare_rows in the middle wherever a
+// piece's side in the caller's buffer is the runs of a periodic pattern: spread_sum is gather_sum (csa_dev_write.h) with source and
+// destination exchanged, compare_rows is compare_piece against such rows (tests/model/csa_dev_spread_model.cpp is their model).
+//
 // The template parameter PLANT switches one deliberate mistake on (0: none).  The product instantiates 0 only; the models run each
 // of the others and have to see it caught by a named case.
 #pragma once
@@ -42,7 +46,10 @@ enum Plant {
     // compare_sum and fold_first (tests/model/csa_dev_compare_model.cpp)
     kPlantCmpHeadNotCompared = 5, kPlantCmpUnitWithoutHead = 6, kPlantCmpWindowPastEnd = 7, kPlantFirstPieceIndex = 8,
     // slice_sum (tests/model/csa_dev_slice_model.cpp)
-    kPlantSliceBorderLate = 9, kPlantSlicePhaseDropped = 10, kPlantSliceStraddleWhole = 11, kPlantSliceRowNotAdvanced = 12
+    kPlantSliceBorderLate = 9, kPlantSlicePhaseDropped = 10, kPlantSliceStraddleWhole = 11, kPlantSliceRowNotAdvanced = 12,
+    // spread_sum and compare_rows (tests/model/csa_dev_spread_model.cpp)
+    kPlantSpreadBorderLate = 13, kPlantSpreadPhaseDropped = 14, kPlantSpreadStraddleWhole = 15, kPlantSpreadRowNotAdvanced = 16,
+    kPlantRowsWindowPastHull = 17, kPlantRowsHeadNotCompared = 18
 };
 
 struct CopyPiece {         // one workgroup of k_gather_extents / k_frag_pieces / k_frag_compare
@@ -136,6 +143,18 @@ CSADEV_FHD Vec16 load_unit(const uint8_t *s0, uint32_t head, uint32_t n, uint32_
     if (WINDOW_UNCHECKED || (head + 16 * i >= m && head + 16 * i + 32 <= n + m))    // the window [16 i - m, 16 i - m + 32) of s0 lies in r[0, n)
         return funnel16(*(const Vec16 *)(base + 16ull * i), *(const Vec16 *)(base + 16ull * i + 16), m);
     return load_bytes16(s0 + 16 * i);
+}
+
+// The 16 bytes at p, of any alignment, all inside the hull [lo, hi): one aligned 16-byte load; or two of them, funnel-shifted into
+// place, as load_unit; or, where that 32-byte window would leave the hull, the 16 bytes one by one.
+template <bool END_UNCHECKED = false>
+CSADEV_FHD Vec16 load_window(const uint8_t *p, const uint8_t *lo, const uint8_t *hi)
+{
+    const uint32_t m = (uint32_t)(uintptr_t)p & 15u;
+    const uintptr_t base = (uintptr_t)p - m;
+    if (m == 0) return *(const Vec16 *)base;
+    if (base >= (uintptr_t)lo && (END_UNCHECKED || base + 32 <= (uintptr_t)hi)) return funnel16(*(const Vec16 *)base, *(const Vec16 *)(base + 16), m);
+    return load_bytes16(p);
 }
 
 // Thread `tid` of `nthreads`: its share of src[0, n) -- copied to dst[0, n) (STORE) and/or summed into a, b as one piece of n bytes
@@ -399,6 +418,154 @@ CSADEV_FHD void slice_sum(const SlicePiece &pc, uint32_t tid, uint32_t nthreads,
         row += srow;
         if (r >= stride) { r -= stride; if (PLANT != kPlantSliceRowNotAdvanced) row++; }
     }
+}
+
+// ---- a fragment's piece against a strided slice of the caller's buffer (CSAMI_DeviceReadIntoSlices, CSAMI_DeviceCompareSlices) ----
+//
+// The caller's side of entry i is what a checked Slice selects of a buffer: packed byte p of the entry lies at buffer offset
+// offset + (p / run) * stride + p % run.  The pieces stay on the fixed kFragPiece grid of the decoded (packed) fragment, so a
+// piece's source is contiguous and its side in the buffer is the tail of one run, a gap and the head of the next -- or, where run
+// is small, many of them.  The host plans a piece with gather_whole / gather_reduce (csa_dev_write.h), as the write does; spread_sum
+// and compare_rows are the workgroup's.  With run < 16 every 16-byte unit crosses a run border and goes byte by byte: that is the
+// slow path, and no rate is promised for it.
+
+struct SpreadPiece {       // one workgroup of k_frag_spread / k_frag_compare_rows: a GatherPiece with src and dst exchanged
+    const uint8_t *src;    // the piece of the decoded fragment, contiguous
+    uint8_t *dst;          // stride == 0: the piece's one contiguous range in the caller's buffer (as a CopyPiece: NULL = summed only);
+                           // else the address of period position 0, inside the hull (what lies in front of `phase` is not touched).
+                           // k_frag_compare_rows only loads from it
+    uint64_t stride;       // periodic: the address step from one run to the next, >= run
+    uint32_t len;          // <= kFragPiece
+    uint32_t phase;        // periodic: byte i of the piece is period position pos = phase + i; row = pos / run, r = pos % run; its
+    uint32_t run;          //           place is dst + row * stride + r
+    uint32_t cmp;          // k_frag_compare_rows: the leading bytes that are compared, <= len (periodic: > 0); k_frag_spread: 0, unused
+    const uint8_t *lo, *hi;   // periodic: the slice's hull [lo, hi): all that a load window of k_frag_compare_rows may touch
+};
+
+// Thread `tid` of `nthreads`: its share of a periodic piece, the transpose of gather_sum.  The anchor is the SOURCE, as in slice_sum:
+// up to 15 head bytes bring it to a 16-byte line and up to 15 tail bytes end the piece, byte by byte; between them every unit is
+// one aligned 16-byte load, so no load window ever leaves src[0, len).  Every byte is loaded once and summed as one piece of len
+// bytes: exactly copy_sum<false, true>'s sums.  A unit whose 16 packed bytes fall in one run goes out as 16 bytes -- one store,
+// four, or sixteen, as its destination's alignment allows; a unit across a run border goes out byte by byte, row segment by row
+// segment.  Nothing but the places of the piece's bytes is stored to: no gap byte, nothing outside the hull.  No division in the
+// unit loop: a thread's (row, r) advances by the workgroup's step, 16 * nthreads packed positions, with one carry.
+template <int PLANT = kPlantNone>
+CSADEV_FHD void spread_sum(const SpreadPiece &pc, uint32_t tid, uint32_t nthreads, uint64_t &a, uint64_t &b)
+{
+    const uint8_t *src = pc.src;
+    uint8_t *dst = pc.dst;
+    const uint32_t n = pc.len, run = pc.run;
+    const uint64_t stride = pc.stride;
+    uint32_t head = (0u - (uint32_t)(uintptr_t)src) & 15u;
+    if (head > n) head = n;
+    const uint32_t units = (n - head) >> 4, tail = (n - head) & 15u;
+    auto one = [&](uint32_t idx) {
+        const uint32_t v = src[idx];
+        const uint32_t pos = pc.phase + idx, row = pos / run, r = pos - row * run;
+        dst[row * stride + r] = (uint8_t)v;
+        a += v;
+        b += (uint64_t)(n - idx) * v;
+    };
+    if (tid < head) one(tid);
+    if (nthreads - 1 - tid < tail) one(head + 16 * units + (nthreads - 1 - tid));
+    if (tid >= units) return;
+    const uint32_t step = 16 * nthreads, srow = step / run, sr = step - srow * run;
+    const uint32_t border = PLANT == kPlantSpreadBorderLate ? run + 1 : run;         // r == border: the next row begins
+    const uint32_t pos = (PLANT == kPlantSpreadPhaseDropped ? 0u : pc.phase) + head + 16 * tid;
+    uint32_t row = pos / run, r = pos - row * run;
+    for (uint32_t i = tid; i < units; i += nthreads) {
+        const uint32_t i0 = head + 16 * i;
+        const Vec16 o = *(const Vec16 *)(src + i0);                   // (aligned: the anchor is src)
+        sum_word(o.w[0], i0, n, a, b);
+        sum_word(o.w[1], i0 + 4, n, a, b);
+        sum_word(o.w[2], i0 + 8, n, a, b);
+        sum_word(o.w[3], i0 + 12, n, a, b);
+        uint8_t *d = dst + row * stride + r;
+        if (PLANT == kPlantSpreadStraddleWhole ? r < run : r + 16 <= run) {
+            if (!((uintptr_t)d & 15u)) {
+                *(Vec16 *)d = o;
+            } else if (!((uintptr_t)d & 3u)) {
+                for (uint32_t j = 0; j < 4; j++) ((uint32_t *)d)[j] = o.w[j];
+            } else {
+                for (uint32_t j = 0; j < 16; j++) d[j] = (uint8_t)(o.w[j >> 2] >> (8 * (j & 3u)));
+            }
+        } else {
+            uint32_t r1 = r;
+            for (uint32_t j = 0; j < 16; j++) {
+                *d++ = (uint8_t)(o.w[j >> 2] >> (8 * (j & 3u)));
+                if (++r1 == border) { r1 = 0; d += stride - run; }
+            }
+        }
+        r += sr;
+        row += srow;
+        if (r >= run) { r -= run; if (PLANT != kPlantSpreadRowNotAdvanced) row++; }
+    }
+}
+
+// Thread `tid` of `nthreads`: its share of a periodic piece of k_frag_compare_rows.  x = pc.src, the fragment's piece, is the anchor,
+// as in compare_sum; its first pc.cmp bytes are compared with the rows of the caller's buffer and the rest summed only, the two
+// parts' sums joined as compare_piece joins them.  A unit whose 16 packed bytes fall in one run loads the caller's 16 bytes with
+// load_window, checked against the HULL -- gap bytes may be loaded; they are never compared -- and a unit across a run border takes
+// them byte by byte, row segment by row segment.  The first differing byte of a unit comes off the XOR of its words.  `first`: the
+// smallest index below cmp at which THIS thread saw a difference, else len.  Nothing outside the hull is loaded, not even by an
+// aligned 16-byte window, and nothing is stored.
+template <int PLANT = kPlantNone>
+CSADEV_FHD void compare_rows(const SpreadPiece &pc, uint32_t tid, uint32_t nthreads, uint64_t &a, uint64_t &b, uint32_t &first)
+{
+    const uint8_t *x = pc.src, *y = pc.dst;
+    const uint32_t n = pc.cmp, run = pc.run;
+    const uint64_t stride = pc.stride;
+    uint32_t head = (0u - (uint32_t)(uintptr_t)x) & 15u;
+    if (head > n) head = n;
+    const uint32_t units = (n - head) >> 4, tail = (n - head) & 15u;
+    uint64_t fa = 0, fb = 0;
+    uint32_t f = n;
+    auto one = [&](uint32_t idx, bool compared) {
+        const uint32_t v = x[idx];
+        const uint32_t pos = pc.phase + idx, row = pos / run, r = pos - row * run;
+        if (compared && v != y[row * stride + r] && idx < f) f = idx;
+        fa += v;
+        fb += (uint64_t)(n - idx) * v;
+    };
+    if (tid < head) one(tid, PLANT != kPlantRowsHeadNotCompared);
+    if (nthreads - 1 - tid < tail) one(head + 16 * units + (nthreads - 1 - tid), true);
+    if (tid < units) {
+        const uint32_t step = 16 * nthreads, srow = step / run, sr = step - srow * run;
+        const uint32_t pos = pc.phase + head + 16 * tid;
+        uint32_t row = pos / run, r = pos - row * run;
+        for (uint32_t i = tid; i < units; i += nthreads) {
+            const uint32_t i0 = head + 16 * i;
+            const Vec16 p = *(const Vec16 *)(x + i0);
+            const uint8_t *q0 = y + row * stride + r;
+            Vec16 q;
+            if (r + 16 <= run) {
+                q = load_window<PLANT == kPlantRowsWindowPastHull>(q0, pc.lo, pc.hi);
+            } else {
+                q = Vec16{{0, 0, 0, 0}};
+                uint32_t r1 = r;
+                for (uint32_t j = 0; j < 16; j++) {
+                    q.w[j >> 2] |= (uint32_t)*q0++ << (8 * (j & 3u));
+                    if (++r1 == run) { r1 = 0; q0 += stride - run; }
+                }
+            }
+            const uint64_t lo = ((uint64_t)(p.w[1] ^ q.w[1]) << 32) | (p.w[0] ^ q.w[0]), hi = ((uint64_t)(p.w[3] ^ q.w[3]) << 32) | (p.w[2] ^ q.w[2]);
+            if (lo | hi) {
+                const uint32_t at = i0 + (lo ? (uint32_t)__builtin_ctzll(lo) >> 3 : 8u + ((uint32_t)__builtin_ctzll(hi) >> 3));
+                if (at < f) f = at;
+            }
+            sum_word(p.w[0], i0, n, fa, fb);
+            sum_word(p.w[1], i0 + 4, n, fa, fb);
+            sum_word(p.w[2], i0 + 8, n, fa, fb);
+            sum_word(p.w[3], i0 + 12, n, fa, fb);
+            r += sr;
+            row += srow;
+            if (r >= run) { r -= run; row++; }
+        }
+    }
+    a += fa;
+    b += fb + (uint64_t)(pc.len - n) * fa;
+    first = f < n ? f : pc.len;
+    if (n < pc.len) copy_sum<false, true>(nullptr, x + n, pc.len - n, tid, nthreads, a, b);
 }
 
 // The first differing offset of a fragment of `size` delivered bytes from its pieces' `first` values (first(k): piece k's, its

@@ -163,18 +163,6 @@ CSADEV_FHD bool gather_reduce(const Slice &s, uint64_t at, uint32_t len, GatherC
     return false;
 }
 
-// The 16 bytes at p, of any alignment, all inside the hull [lo, hi): one aligned 16-byte load; or two of them, funnel-shifted into
-// place, as load_unit; or, where that 32-byte window would leave the hull, the 16 bytes one by one.
-template <bool END_UNCHECKED = false>
-CSADEV_FHD Vec16 load_window(const uint8_t *p, const uint8_t *lo, const uint8_t *hi)
-{
-    const uint32_t m = (uint32_t)(uintptr_t)p & 15u;
-    const uintptr_t base = (uintptr_t)p - m;
-    if (m == 0) return *(const Vec16 *)base;
-    if (base >= (uintptr_t)lo && (END_UNCHECKED || base + 32 <= (uintptr_t)hi)) return funnel16(*(const Vec16 *)base, *(const Vec16 *)(base + 16), m);
-    return load_bytes16(p);
-}
-
 // Thread `tid` of `nthreads`: its share of a periodic piece.  The anchor is the destination: up to 15 head bytes bring it to a
 // 16-byte line and up to 15 tail bytes end the piece, byte by byte; between them every unit is one aligned 16-byte store.  A unit
 // whose 16 packed bytes lie inside one run is loaded as load_unit loads (load_window: the window is checked against the HULL, so gap

@@ -19,6 +19,8 @@ void launch_frag_pieces(const void *pieces, void *sums, uint32_t npieces, bool s
 void launch_frag_compare(const void *pieces, void *sums, void *firsts, uint32_t npieces, hipStream_t st);
 void launch_frag_slices(const void *pieces, void *sums, uint32_t npieces, hipStream_t st);
 void launch_frag_rows(const void *pieces, void *sums, uint32_t npieces, hipStream_t st);
+void launch_frag_spread(const void *pieces, void *sums, uint32_t npieces, hipStream_t st);
+void launch_frag_compare_rows(const void *pieces, void *sums, void *firsts, uint32_t npieces, hipStream_t st);
 void launch_frag_fold(const void *frags, const void *sums, void *out, uint32_t nfrags, hipStream_t st);
 void launch_frag_fold_diff(const void *frags, const void *sums, const void *firsts, void *out, uint32_t nfrags, hipStream_t st);
 void launch_block_table(const void *jobs, uint32_t njobs, void *scratch, void *res, void *sizes, hipStream_t st);

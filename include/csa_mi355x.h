@@ -429,8 +429,8 @@ int CSAMI_DeviceCompare(CSADevArchive *a, const char *const *names, int nnames, 
  * a 16-byte unit inside one run stored as 16 bytes, a unit across a run border byte by byte.  Its table entry holds 32-bit
  * quantities whatever run and stride are.  Nothing outside a fragment's decoded bytes is loaded, not even by an aligned 16-byte
  * window, and nothing but the selected bytes' destinations is stored.
- * Out of scope: stopping inside a fragment, CSAMI_DeviceCompare against a slice, updating a slice, and the host paths
- * (CSA_Extract / CSA_Test). */
+ * Out of scope: stopping inside a fragment, a slice of an entry into a slice of a buffer in one call, updating a slice, and the host
+ * paths (CSA_Extract / CSA_Test). */
 typedef struct CSADevSlice { uint64_t offset, run, stride, count; } CSADevSlice;
 typedef struct CSADevSliceStats {
     uint64_t selected_bytes;    /* sum of run * count over the entries */
@@ -490,8 +490,8 @@ int CSAMI_PlanDeviceSlices(const uint8_t *raw_index, uint64_t raw_size, uint64_t
  * Safety contract.  Nothing outside an entry's hull is loaded, not even by an aligned 16-byte window.  Gap bytes inside the hull may
  * be loaded; they are never summed and never stored.  Nothing of the caller's is written.  The bus contract is CSAMI_DeviceWrite's,
  * with 56 bytes in the place of 24 for a stored piece of a wave that runs k_frag_rows: no file byte and no stream byte crosses.
- * Out of scope: delivering a read into a strided destination, CSAMI_DeviceCompare against a slice, updating part of an existing
- * archive, and the host paths (CSA_Add). */
+ * Out of scope: updating part of an existing archive, and the host paths (CSA_Add).  The way back -- a read into, and a comparison
+ * against, a slice of a buffer -- is the next section. */
 typedef struct CSADevGatherStats {
     uint64_t selected_bytes;    /* sum of run * count: the entries' bytes */
     uint64_t hull_bytes;        /* sum of the slices' hulls: (count - 1) * stride + run */
@@ -503,6 +503,71 @@ int CSAMI_DeviceWriteSlices(const void *const *ptrs, const uint64_t *sizes, cons
                             CSADevFile *files, uint32_t n_files, const char *arcname,
                             void *arc_dev, uint64_t arc_cap, const CSAOptions *o,
                             CSADevWriteStats *st, CSADevGatherStats *gather_stats);
+
+/* ---- read into and compare against strided slices of the caller's buffers: the way back of CSAMI_DeviceWriteSlices; not in the reference ----
+ *
+ * CSAMI_DeviceReadInto and CSAMI_DeviceCompare want contiguous bytes on the caller's side.  Here the caller's side of entry i -- in the
+ * order CSAMI_DevicePlan lists the entries -- is what slices[i], a CSADevSlice exactly as CSAMI_DeviceWriteSlices reads it, selects of
+ * the caller's buffer ptrs[i][0, sizes[i]): packed byte p of the entry lives at buffer offset offset + (p / run) * stride + p % run;
+ * with count == 1 the stride is ignored.  It is a slice of the BUFFER, not of the entry.  So a block of columns written from
+ * t[:, c0:c1] is restored into, or verified against, t[:, c0:c1] where it lies, without a packed scratch copy and a second pass, and
+ * eight ranks' column blocks are read into one full matrix by ONE call, through eight slices whose hulls interleave.  There is one
+ * read path: CSAMI_DeviceReadInto is CSAMI_DeviceReadIntoSlices with slices[i] = {0, size_i, size_i, 1} and sizes[i] = caps[i], and
+ * CSAMI_DeviceCompare is CSAMI_DeviceCompareSlices with slices[i] = {0, sizes[i], sizes[i], 1}.
+ *
+ * Reading.  Every sentence documented at CSAMI_DeviceReadInto and CSAMI_DeviceReadStop that does not speak of caps or of the
+ * destination's shape holds: which tasks are decoded and how far (CSAMI_DEV_STOP_EARLY), that every selected fragment is summed
+ * whole and verified, the return value, the clipping of a fragment to what its task produced, failed_frags, st->launches ==
+ * 3 * st->waves and the read-back bound.  ptrs[i] == NULL (or ptrs == NULL: all of them): the entry is verified only and its slice
+ * is not looked at.  run * count > size_i is allowed: the entry fills the first size_i packed positions and the rest is untouched.
+ * run * count < size_i with a non-NULL pointer: WRITE_ERROR, nothing launched.  Gap bytes are never stored to, nor are bytes of
+ * the hull behind packed position size_i, bytes that no delivered fragment covers, or anything outside the hull.
+ * Refused with -1, nothing launched and *st, *stop_stats and *spread_stats (each may be NULL) zeroed: slices == NULL or sizes == NULL
+ * with n > 0; n other than the plan's *n_files; for a non-NULL ptrs[i], a slice that the read refuses in an entry of sizes[i] bytes
+ * (run == 0 with count > 0, stride < run with count > 1, any product or sum that wraps, a last selected byte at or behind sizes[i]);
+ * and whatever CSAMI_CheckSlices(ptrs, sizes, slices, n, arc, arc_size, 1) refuses.  Without a visible device CSCMI_DEVICE_ERROR is
+ * returned before any argument is looked at, with nothing touched.
+ *
+ * Comparing.  CSAMI_DeviceCompareSlices is CSAMI_DeviceCompare with entry i compared against the packed bytes of slices[i]:
+ * CSA_DIFF_SIZE is set when run * count != size_i, and the compared size is then the smaller of the two; first_diff is a packed offset
+ * in the entry; gap bytes are never compared and nothing of the caller's is written.  Hulls may alias each other, not the archive:
+ * the check is CSAMI_CheckSlices with disjoint == 0.
+ *
+ * Kernels.  A fragment's pieces stay on the fixed 16 KiB grid of the decoded (packed) fragment, and a piece is planned as
+ * CSAMI_DeviceWriteSlices plans it, with the roles of source and destination exchanged.  A wave stays three launches.  In a wave
+ * with at least one piece whose side in the buffer crosses a run border (spread_stats->periodic_pieces) all pieces go through
+ * k_frag_spread (k_frag_compare_rows when comparing) with one table of 56 bytes a piece; a wave without one runs k_frag_pieces
+ * (k_frag_compare) over 24-byte pieces exactly as CSAMI_DeviceReadInto (CSAMI_DeviceCompare) always did.  Slot [1] of
+ * CSAMI_DeviceKernelMs holds the time either way.  Every byte of the fragment is loaded once, in aligned 16-byte units, and summed as
+ * k_frag_pieces sums it.  A unit whose 16 packed bytes fall in one run is stored as 16 bytes -- one store, four or sixteen, as the
+ * destination's alignment allows -- or compared with two aligned 16-byte loads of the caller's, funnel-shifted, whose window is
+ * checked against the hull: gap bytes may be loaded by the comparison; they are never compared.  A unit across a run border goes
+ * byte by byte.  With run < 16 every unit crosses a border: that is the slow path (profiles/archive_device_spread.md), and no
+ * rate is promised for it.  Nothing outside a hull is loaded or stored, not even by an aligned 16-byte window.
+ * Out of scope: a slice of an entry into a slice of a buffer in one call, updating an archive in place, and the host paths. */
+typedef struct CSADevSpreadStats {
+    uint64_t selected_bytes;    /* sum over the entries of the bytes delivered / compared: min(size_i, run * count) */
+    uint64_t hull_bytes;        /* sum of the slices' hulls: (count - 1) * stride + run */
+    uint64_t periodic_pieces;   /* pieces spread (or compared) across a run border */
+    uint64_t plain_pieces;      /* pieces whose buffer side is one contiguous range, or that are summed only */
+} CSADevSpreadStats;
+/* host only, no GPU: CSAMI_CheckBuffers over slices.  It refuses what CSAMI_CheckBuffers refuses, about each HULL
+ * [ptrs[i] + offset, + (count - 1) * stride + run) -- a hull that overlaps [excl, excl + excl_size) is refused even where only a gap
+ * byte overlaps, as the write refuses it -- and a slice that the read refuses in a buffer of sizes[i] bytes; count == 0 selects
+ * nothing and its pointer may be NULL.  *bad as there; ptrs, sizes or slices NULL with n > 0 refuses index 0.
+ * With disjoint != 0 two hulls that overlap are accepted only where their SELECTED bytes provably do not meet, decided without
+ * walking rows: both slices have the same stride S (a count == 1 slice takes the other's; two count == 1 slices that overlap are
+ * refused), d = (address of B's period position 0 - address of A's) mod S, and d >= run_A and d + run_B <= S -- column blocks of one
+ * matrix, a byte range inside one gap.  Any other overlapping pair refuses both indices.  The hulls are sorted by their start and
+ * swept: n log n plus the number of overlapping pairs.  With disjoint == 0 nothing is checked between entries. */
+int CSAMI_CheckSlices(const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices, uint32_t n,
+                      const void *excl, uint64_t excl_size, int disjoint, uint32_t *bad);
+int CSAMI_DeviceReadIntoSlices(CSADevArchive *a, const char *const *names, int nnames, void *const *ptrs, const uint64_t *sizes,
+                               const CSADevSlice *slices, uint32_t n, uint32_t flags, const CSAOptions *o, CSADevFile *files,
+                               CSADevReadStats *st, CSADevStopStats *stop_stats, CSADevSpreadStats *spread_stats);
+int CSAMI_DeviceCompareSlices(CSADevArchive *a, const char *const *names, int nnames, const void *const *ptrs, const uint64_t *sizes,
+                              const CSADevSlice *slices, uint32_t n, uint32_t flags, const CSAOptions *o, CSADevFile *files,
+                              CSADevDiff *diffs, CSADevReadStats *st, CSADevStopStats *stop_stats, CSADevSpreadStats *spread_stats);
 
 /* YYYYMMDDHHMMSS <-> time_t, csa_common.cpp:3-39 */
 int64_t CSA_DecimalTime(int64_t unix_seconds);
