@@ -102,6 +102,23 @@ class CSADevSpreadStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CSADevUpdateTask(C.Structure):
+    _fields_ = [("base_bid", C.c_uint64), ("status", C.c_uint32), ("reserved", C.c_uint32)]
+
+    def as_dict(self):
+        return {"base_bid": int(self.base_bid), "status": int(self.status)}
+
+
+class CSADevUpdateStats(C.Structure):
+    _fields_ = [("candidates", C.c_uint64), ("reused_tasks", C.c_uint64), ("encoded_tasks", C.c_uint64), ("reused_raw_bytes", C.c_uint64),
+                ("reused_stream_bytes", C.c_uint64), ("encoded_raw_bytes", C.c_uint64), ("checked_bytes", C.c_uint64),
+                ("decoded_bytes", C.c_uint64), ("check_waves", C.c_uint64), ("check_launches", C.c_uint64), ("decode_launches", C.c_uint64),
+                ("check_kernel_ms", C.c_double), ("seconds_check", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 LIST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(CSAFrag))
 
 SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", "CSA_ReadIndex",
@@ -112,7 +129,8 @@ SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", 
            "CSAMI_DeviceWritePlan", "CSAMI_DeviceWrite", "CSAMI_DeviceWriteKernelMs",
            "CSAMI_CheckBuffers", "CSAMI_DeviceWriteFrom", "CSAMI_DeviceReadInto", "CSAMI_DeviceCompare",
            "CSAMI_DeviceReadSlices", "CSAMI_PlanDeviceSlices", "CSAMI_DeviceWriteSlices",
-           "CSAMI_CheckSlices", "CSAMI_DeviceReadIntoSlices", "CSAMI_DeviceCompareSlices"]
+           "CSAMI_CheckSlices", "CSAMI_DeviceReadIntoSlices", "CSAMI_DeviceCompareSlices",
+           "CSAMI_DeviceUpdate", "CSAMI_PlanDeviceUpdate"]
 
 CSA_MAX_FRAGMENTS = 127
 CSA_TOO_MANY_FRAGMENTS = -94
@@ -121,6 +139,9 @@ CSCMI_DEVICE_ERROR = -95
 WRITE_ERROR = -97
 CSAMI_DEV_STOP_EARLY = 1
 CSA_DIFF_BYTES, CSA_DIFF_SIZE, CSA_DIFF_SKIPPED, CSA_DIFF_SHORT = 1, 2, 4, 8
+CSAMI_UPDATE_TRUST_SUMS = 1
+CSA_UPD_REUSED, CSA_UPD_NEW, CSA_UPD_PROPS, CSA_UPD_CHANGED, CSA_UPD_BASE_BAD = 0, 1, 2, 3, 4
+NO_BID = (1 << 64) - 1                     # CSADevUpdateTask.base_bid of a task that is no candidate
 NO_DIFF = (1 << 64) - 1                    # CSADevDiff.first_diff without CSA_DIFF_BYTES
 
 _lib = None
@@ -218,6 +239,13 @@ def lib():
                                                 C.POINTER(CSADevDiff), C.POINTER(CSADevReadStats), C.POINTER(CSADevStopStats),
                                                 C.POINTER(CSADevSpreadStats)]
         L.CSAMI_DeviceCompareSlices.restype = C.c_int
+        L.CSAMI_DeviceUpdate.argtypes = [C.c_void_p, ptrs, u64s, slices, files, C.c_uint32, C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint32,
+                                         C.POINTER(CSAOptions), C.POINTER(CSADevWriteStats), C.POINTER(CSADevGatherStats),
+                                         C.POINTER(CSADevUpdateStats), C.POINTER(CSADevUpdateTask), C.c_uint32]
+        L.CSAMI_DeviceUpdate.restype = C.c_int
+        L.CSAMI_PlanDeviceUpdate.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, files, C.c_uint32, C.POINTER(CSAOptions), u64s, C.c_uint32,
+                                             C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
+        L.CSAMI_PlanDeviceUpdate.restype = C.c_int
         _lib = L
     return _lib
 
@@ -498,6 +526,22 @@ def device_write_plan(files, arcname: str = "out.csa", **opts):
     return rc, int(nt.value), int(mf.value), int(raw.value)
 
 
+def plan_device_update(raw_index: bytes, arc_size: int, files, **opts):
+    """CSAMI_PlanDeviceUpdate (host only): the candidate step of DeviceArchive.update over these raw index bytes of the base and the
+    new table (dicts with name, esize, edate, eattr) -> (rc, [base bid of every task of the new plan, NO_BID where it is no
+    candidate], number of candidates)"""
+    buf = (C.c_uint8 * max(len(raw_index), 1)).from_buffer_copy(raw_index or b"\0")
+    arr, keep = _write_table(files)
+    o = options(**opts)
+    nt, nc = C.c_uint32(), C.c_uint32()
+    rc = lib().CSAMI_PlanDeviceUpdate(buf, len(raw_index), arc_size, arr, len(keep), C.byref(o), None, 0, C.byref(nt), C.byref(nc))
+    if rc != 0:
+        return rc, [], 0
+    bids = (C.c_uint64 * max(nt.value, 1))()
+    rc = lib().CSAMI_PlanDeviceUpdate(buf, len(raw_index), arc_size, arr, len(keep), C.byref(o), bids, nt.value, C.byref(nt), C.byref(nc))
+    return rc, [int(b) for b in bids[:nt.value]], int(nc.value)
+
+
 def device_write_kernel_ms():
     """HIP-event milliseconds of this thread's last DeviceArchive.write by kernel: (k_frag_pieces -- k_frag_rows in a wave of write_slices
     with a piece across a run border --, k_frag_fold, k_block_table, k_gather_extents)"""
@@ -533,6 +577,59 @@ def check_slices(ptrs: Sequence[int], sizes: Sequence[int], slices, excl=(0, 0),
 def _is_bytes_tensor(t) -> bool:
     import torch
     return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.dim() == 1
+
+
+def _write_slices(base, entries, arcname, arc, flags, whole_default, opts):
+    """DeviceArchive.write_slices (base None) and DeviceArchive.update: the table, the two capacities, and the call --
+    CSAMI_DeviceWriteSlices, or CSAMI_DeviceUpdate over the base.
+    whole_default: an entry without "slice" is its whole tensor (else: no bytes)"""
+    import torch
+    files, table = [], (CSADevSlice * max(len(entries), 1))()
+    for a, e in zip(table, entries):
+        t = e["tensor"]
+        if not (t is None or _is_bytes_tensor(t)):
+            raise TypeError("tensor: a contiguous 1-d torch.uint8 CUDA tensor, or None")
+        s = e.get("slice") or ((0, int(t.numel())) if whole_default and t is not None else (0, 0, 0, 0))
+        a.offset, a.run, a.stride, a.count = (s[0], s[1], s[1], 1 if s[1] else 0) if len(s) == 2 else s
+        files.append({"name": e["name"], "esize": a.run * a.count if a.count else 0, "edate": e["edate"], "eattr": e["eattr"]})
+    if not (arc is None or _is_bytes_tensor(arc)):
+        raise TypeError("arc: a contiguous 1-d torch.uint8 CUDA tensor")
+    live = [e["tensor"] for e in entries]                      # alive across the call
+    ptrs = (C.c_void_p * max(len(live), 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in live])
+    sizes = (C.c_uint64 * max(len(live), 1))(*[0 if t is None else int(t.numel()) for t in live])
+    device = arc.device if arc is not None else next((t.device for t in live if t is not None), "cuda")
+    o = options(**opts)
+    caps, nt = [None], None
+    if arc is None or base is not None:
+        rc, nt, _, raw = device_write_plan(files, arcname, **opts)
+        if rc != 0:
+            return rc, None, {"files": []}
+    if arc is None:
+        cap = 24 + raw + raw // 8 + (64 << 10) * (nt + 1) + (1 << 20)
+        caps = [cap, 2 * cap]
+    for cap in caps:
+        if cap is not None:
+            arc = torch.empty(cap, dtype=torch.uint8, device=device)
+        arr, keep = _write_table(files)
+        st, gs, us = CSADevWriteStats(), CSADevGatherStats(), CSADevUpdateStats()
+        tasks = (CSADevUpdateTask * max(nt or 0, 1))()
+        torch.cuda.synchronize()                   # the buffers were filled on torch's stream, the library launches on its own
+        where = (arcname.encode(), C.c_void_p(arc.data_ptr()) if arc.numel() else None, int(arc.numel()))
+        if base is None:
+            rc = lib().CSAMI_DeviceWriteSlices(ptrs, sizes, table, arr, len(keep), *where, C.byref(o), C.byref(st), C.byref(gs))
+        else:
+            rc = lib().CSAMI_DeviceUpdate(base._h, ptrs, sizes, table, arr, len(keep), *where, flags, C.byref(o), C.byref(st), C.byref(gs),
+                                          C.byref(us), tasks, nt)
+        if rc != WRITE_ERROR:
+            break
+    del live
+    d = st.as_dict()
+    d.update(gs.as_dict())
+    if base is not None:
+        d.update(us.as_dict())
+        d["tasks"] = [t.as_dict() for t in tasks[:min(nt, int(st.tasks))]]
+    d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
+    return rc, (arc[:st.archive_bytes] if rc == 0 else None), d
 
 
 class DeviceArchive:
@@ -694,45 +791,17 @@ class DeviceArchive:
         (offset, length) | (offset, run, stride, count) into it -- rows_slice makes one for a block of a row-major matrix,
         tensor_slice both for a strided view.  The entry's bytes are the selected ones, packed: esize = run * count.  The buffers
         are only read and may alias each other, not arc."""
-        import torch
-        files, table = [], (CSADevSlice * max(len(entries), 1))()
-        for a, e in zip(table, entries):
-            t = e["tensor"]
-            if not (t is None or _is_bytes_tensor(t)):
-                raise TypeError("tensor: a contiguous 1-d torch.uint8 CUDA tensor, or None")
-            s = e.get("slice") or (0, 0, 0, 0)
-            a.offset, a.run, a.stride, a.count = (s[0], s[1], s[1], 1 if s[1] else 0) if len(s) == 2 else s
-            files.append({"name": e["name"], "esize": a.run * a.count if a.count else 0, "edate": e["edate"], "eattr": e["eattr"]})
-        if not (arc is None or _is_bytes_tensor(arc)):
-            raise TypeError("arc: a contiguous 1-d torch.uint8 CUDA tensor")
-        live = [e["tensor"] for e in entries]                      # alive across the call
-        ptrs = (C.c_void_p * max(len(live), 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in live])
-        sizes = (C.c_uint64 * max(len(live), 1))(*[0 if t is None else int(t.numel()) for t in live])
-        device = arc.device if arc is not None else next((t.device for t in live if t is not None), "cuda")
-        o = options(**opts)
-        caps = [None]
-        if arc is None:
-            rc, nt, _, raw = device_write_plan(files, arcname, **opts)
-            if rc != 0:
-                return rc, None, {"files": []}
-            cap = 24 + raw + raw // 8 + (64 << 10) * (nt + 1) + (1 << 20)
-            caps = [cap, 2 * cap]
-        for cap in caps:
-            if cap is not None:
-                arc = torch.empty(cap, dtype=torch.uint8, device=device)
-            arr, keep = _write_table(files)
-            st, gs = CSADevWriteStats(), CSADevGatherStats()
-            torch.cuda.synchronize()                   # the buffers were filled on torch's stream, the library launches on its own
-            rc = lib().CSAMI_DeviceWriteSlices(ptrs, sizes, table, arr, len(keep), arcname.encode(),
-                                               C.c_void_p(arc.data_ptr()) if arc.numel() else None, int(arc.numel()), C.byref(o),
-                                               C.byref(st), C.byref(gs))
-            if rc != WRITE_ERROR:
-                break
-        del live
-        d = st.as_dict()
-        d.update(gs.as_dict())
-        d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
-        return rc, (arc[:st.archive_bytes] if rc == 0 else None), d
+        return _write_slices(None, entries, arcname, arc, 0, False, opts)
+
+    def update(self, entries, arcname: str = "out.csa", arc=None, trust_sums=False, **opts):
+        """write_slices of `entries` with this archive as the base (CSAMI_DeviceUpdate): a task of the new plan that has the
+        composition and the bytes of a task of this archive gets that task's stream copied, not encoded -> (rc, uint8 CUDA view of
+        the new archive, stats dict) as write_slices, with the update statistics merged in and stats["tasks"] = [{"base_bid",
+        "status"}] per task of the new plan.  entries: write_slices's; an entry without "slice" is its whole tensor.  The new
+        archive is byte for byte write_slices's as long as this archive was written at the same level.  trust_sums: nothing is
+        decoded -- a task is taken for unchanged when every fragment's adler32 equals this archive's index's, a 32-bit test that two
+        different contents can pass.  arc must not overlap this archive's tensor."""
+        return _write_slices(self, entries, arcname, arc, CSAMI_UPDATE_TRUST_SUMS if trust_sums else 0, True, opts)
 
     def _by_name(self, bufs, names):
         """the selection's files table and, per entry of it, the caller's tensor (None: verified only).  KeyError for a key that is

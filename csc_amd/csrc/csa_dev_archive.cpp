@@ -230,23 +230,26 @@ struct FragTables {
     }
     // CSAMI_DeviceWriteSlices, in front of `pieces`: a fragment of `size` > 0 bytes that is the packed bytes [at, at + size) of the
     // (checked) slice sl of the buffer `buf`, gathered to dst.  Each 16 KiB cell of the packed fragment is classified (gather_reduce).
-    // Its pieces and their sums come first: add() counts from behind them.
+    // Its pieces and their sums come first: add() counts from behind them.  dst == NULL (CSAMI_DeviceUpdate's check under
+    // CSAMI_UPDATE_TRUST_SUMS): the fragment is summed where it lies and folded against `checksum`.
     std::vector<csadev::GatherPiece> gpieces;
     DevBuf d_gpieces;
-    bool add_gathered(const uint8_t *buf, uint8_t *dst, const csadev::Slice &sl, uint64_t at, uint64_t size, CSADevGatherStats &G)
+    bool add_gathered(const uint8_t *buf, uint8_t *dst, const csadev::Slice &sl, uint64_t at, uint64_t size, CSADevGatherStats &G,
+                      uint32_t checksum = 0)
     {
         using namespace csadev;
         const uint64_t np = piece_count(size, kFragPiece);
         if (!pieces.empty() || gpieces.size() + np > 0x7FFFFFFFull) return false;
-        frags.push_back(FragFold{size, (uint32_t)gpieces.size(), (uint32_t)np, 0, 0});
+        frags.push_back(FragFold{size, (uint32_t)gpieces.size(), (uint32_t)np, checksum, 0});
         const uint8_t *lo = buf + sl.offset, *hi = lo + (sl.count - 1) * sl.stride + sl.run;
         for (uint64_t off = 0; off < size; off += kFragPiece) {
             GatherCut c;
             const uint32_t len = (uint32_t)std::min<uint64_t>(size - off, kFragPiece);
             const bool whole = gather_reduce(sl, at + off, len, c);
             (whole ? G.plain_pieces : G.periodic_pieces)++;
-            gpieces.push_back(whole ? GatherPiece{buf + c.src, dst + off, 0, len, 0, 0, 0, nullptr, nullptr}
-                                    : GatherPiece{buf + c.src, dst + off, c.stride, len, c.phase, c.run, 0, lo, hi});
+            uint8_t *d = dst ? dst + off : nullptr;
+            gpieces.push_back(whole ? GatherPiece{buf + c.src, d, 0, len, 0, 0, 0, nullptr, nullptr}
+                                    : GatherPiece{buf + c.src, d, c.stride, len, c.phase, c.run, 0, lo, hi});
         }
         return true;
     }
@@ -992,6 +995,8 @@ int CSAMI_PlanDeviceSlices(const uint8_t *raw_index, uint64_t raw_size, uint64_t
 // k_gather_extents; tables and walks: csa_dev_read.h, csa_dev_write.h) and in CSCMI_EncodeDeviceBatch.  All of them are one path
 // over a device pointer and a slice per entry (CSAMI_DeviceWriteSlices): CSAMI_DeviceWrite and CSAMI_DeviceWriteFrom hand in whole
 // entries; where a slice has rows, a task's fragments are gathered across the run borders by k_frag_rows.
+// CSAMI_DeviceUpdate is that path with a base archive: the tasks of the plan that are tasks of the base (update_candidates) and whose
+// bytes are still the base's (dev_check_wave) are placed from the base instead of encoded; CSAMI_DeviceWriteSlices is it without one.
 // ---------------------------------------------------------------------------------------------
 namespace {
 
@@ -1019,8 +1024,71 @@ int plan_write(AddPlan &P, const CSADevFile *files, uint32_t n_files, const CSAO
     return rc;
 }
 
+// CSAMI_DeviceUpdate: what the call knows of a task of the new plan
+struct UpdTask {
+    uint64_t base_bid = UINT64_MAX;
+    uint32_t status = CSA_UPD_NEW;
+    bool candidate = false;                    // the host step found its base task, and no later step has ruled it out yet
+    bool have_sums = false;                    // its fragments' checksums are the caller's bytes' (the check under TRUST_SUMS summed them)
+    std::vector<uint32_t> base_sums;           // candidate: the base index's checksum of each of its fragments, in the task's order
+    std::vector<Extent> ext;                   // candidate: the base stream's archive blocks, clipped to the base buffer
+    uint64_t stream = 0;                       //            and their bytes, the 10 property bytes included
+};
+struct UpdateCtx {
+    CSADevArchive *base = nullptr;
+    bool trust = false;
+    std::vector<UpdTask> tasks;
+    CSADevUpdateStats U;
+    double ms = 0;                             // HIP-event time of the check waves' launches
+    bool reused(size_t task) const { return tasks[task].status == CSA_UPD_REUSED; }
+};
+
+// The candidates of CSAMI_DeviceUpdate / CSAMI_PlanDeviceUpdate (host): task i of the plan is a candidate for base task bids[i] when
+// it holds a byte and the set of its fragments (name, offset in the entry, size, posblock) is the set of ALL fragments of the base
+// index with that bid; UINT64_MAX where there is none.  One map from (name, offset) to the base's fragments there, one look per
+// fragment of the plan: no task is compared with another.  Sets posblock of every fragment of the plan (csa_io.h:239); sums[i]
+// gets the base's checksums of a candidate's fragments, in the task's order.  Returns the number of candidates.
+uint32_t update_candidates(const Index &base, AddPlan &P, std::vector<uint64_t> &bids, std::vector<std::vector<uint32_t>> &sums)
+{
+    struct BaseFrag { uint64_t bid, size, posblock; uint32_t checksum; };
+    std::map<std::pair<std::string, uint64_t>, std::vector<BaseFrag>> where;
+    std::map<uint64_t, uint64_t> nfrags;
+    for (const auto &kv : base)
+        for (const CSAFrag &f : kv.second.frags) {
+            where[std::make_pair(kv.first, (uint64_t)f.posfile)].push_back(BaseFrag{f.bid, f.size, f.posblock, f.checksum});
+            nfrags[f.bid]++;
+        }
+    bids.assign(P.tasks.size(), UINT64_MAX);
+    sums.assign(P.tasks.size(), std::vector<uint32_t>());
+    uint32_t n = 0;
+    for (size_t ti = 0; ti < P.tasks.size(); ti++) {
+        Task &t = P.tasks[ti];
+        uint64_t cum = 0;
+        for (FilePiece &f : t.files) { f.posblock = cum; cum += f.size; }
+        if (!t.total) continue;
+        uint64_t bid = UINT64_MAX;
+        std::vector<uint32_t> cs;
+        for (const FilePiece &f : t.files) {
+            const BaseFrag *hit = nullptr;
+            auto w = where.find(std::make_pair(f.it->first, f.off));
+            if (w != where.end())
+                for (const BaseFrag &b : w->second)
+                    if (b.size == f.size && b.posblock == f.posblock && (bid == UINT64_MAX || b.bid == bid)) { hit = &b; break; }
+            if (!hit) break;
+            bid = hit->bid;
+            cs.push_back(hit->checksum);
+        }
+        if (cs.size() != t.files.size() || nfrags[bid] != t.files.size()) continue;
+        bids[ti] = bid;
+        sums[ti].swap(cs);
+        n++;
+    }
+    return n;
+}
+
 struct WriteCtx {
-    const void *const *ptrs = nullptr;         // entry `row` of the caller's table: the bytes that slices[row], checked, selects of
+    UpdateCtx *upd = nullptr;                  // CSAMI_DeviceUpdate with a base: the tasks whose streams are copied, not encoded
+    const void *const *ptrs = nullptr;        // entry `row` of the caller's table: the bytes that slices[row], checked, selects of
     const csadev::Slice *slices = nullptr;     // the buffer at ptrs[row], packed row after row
     uint8_t *arc = nullptr;
     uint64_t arc_cap = 0, arc_end = kHeaderSize;
@@ -1071,33 +1139,51 @@ int dev_encode(WriteCtx &W, std::vector<CSCMIDevEncode> &jobs, std::list<DevBuf>
     return rc;
 }
 
-// The property bytes and the stream of every job to arc + arc_end, in order, with one launch; `hdr` (NULL, or the 24 header bytes)
-// goes to arc + 0 with it.  WRITE_ERROR, with nothing launched, if it would pass arc_cap.
-int dev_place(WriteCtx &W, const std::vector<CSCMIDevEncode> &jobs, const uint8_t *hdr)
+// One stream to place: an encoded one (job: its property bytes come from the host, its stream lies in scratch), or one of the base
+// archive of CSAMI_DeviceUpdate (ext: its archive blocks in `base`, the 10 property bytes in front of the first; stream: their bytes)
+struct Placed {
+    const CSCMIDevEncode *job;
+    const std::vector<Extent> *ext;
+    const uint8_t *base;
+    uint64_t stream;
+    uint64_t bytes() const { return job ? CSC_PROP_SIZE + (uint64_t)job->produced : stream; }
+};
+
+// Every stream of `items` to arc + arc_end, in order, with one launch; `hdr` (NULL, or the 24 header bytes) goes to arc + 0 with it.
+// at[k]: where stream k begins.  WRITE_ERROR, with nothing launched, if it would pass arc_cap.
+int dev_place(WriteCtx &W, const std::vector<Placed> &items, const uint8_t *hdr, std::vector<uint64_t> *at = nullptr)
 {
     using namespace csadev;
     const uint64_t lead = hdr ? kHeaderSize : 0;
     uint64_t end = W.arc_end;
-    for (const CSCMIDevEncode &j : jobs)
-        if (!add_ok(end, CSC_PROP_SIZE + (uint64_t)j.produced, &end)) return WRITE_ERROR;
+    for (const Placed &it : items)
+        if (!add_ok(end, it.bytes(), &end)) return WRITE_ERROR;
     if (end > W.arc_cap) return WRITE_ERROR;
-    // the bytes that come from the host: [the header] and the property bytes of every job
+    // the bytes that come from the host: [the header] and the property bytes of every encoded stream
     std::vector<uint8_t> host(hdr, hdr + lead);
-    for (const CSCMIDevEncode &j : jobs) {
+    for (const Placed &it : items) {
+        if (!it.job) continue;
         uint8_t props[CSC_PROP_SIZE];
-        CSCEnc_WriteProperties(&j.props, props, 0);                          // csa_worker.cpp:38-42
+        CSCEnc_WriteProperties(&it.job->props, props, 0);                    // csa_worker.cpp:38-42
         host.insert(host.end(), props, props + CSC_PROP_SIZE);
     }
     DevBuf d_host, d_gp;
     if (!dev_upload(W, d_host, host.data(), host.size())) return CSCMI_DEVICE_ERROR;
     std::vector<CopyPiece> gp;
     if (hdr) gp.push_back(CopyPiece{(const uint8_t *)d_host.p, W.arc, (uint32_t)kHeaderSize, 0});
-    uint64_t pos = W.arc_end;
-    for (size_t k = 0; k < jobs.size(); k++) {
-        gp.push_back(CopyPiece{(const uint8_t *)d_host.p + lead + CSC_PROP_SIZE * k, W.arc + pos, CSC_PROP_SIZE, 0});
-        piece_split((const uint8_t *)jobs[k].dst, W.arc + pos + CSC_PROP_SIZE, jobs[k].produced, kGatherPiece,
-                    [&](uint64_t, const CopyPiece &p) { gp.push_back(p); });
-        pos += CSC_PROP_SIZE + jobs[k].produced;
+    uint64_t pos = W.arc_end, hp = lead;
+    auto put = [&](uint64_t, const CopyPiece &p) { gp.push_back(p); };
+    if (at) at->clear();
+    for (const Placed &it : items) {
+        if (at) at->push_back(pos);
+        if (it.job) {
+            gp.push_back(CopyPiece{(const uint8_t *)d_host.p + hp, W.arc + pos, CSC_PROP_SIZE, 0});
+            piece_split((const uint8_t *)it.job->dst, W.arc + pos + CSC_PROP_SIZE, it.job->produced, kGatherPiece, put);
+            hp += CSC_PROP_SIZE;
+            pos += it.bytes();
+        } else {
+            for (const Extent &x : *it.ext) { piece_split(it.base + x.off, W.arc + pos, x.size, kGatherPiece, put); pos += x.size; }
+        }
     }
     if (gp.size() > 0x7FFFFFFFull || !dev_upload(W, d_gp, gp.data(), gp.size() * sizeof(CopyPiece))) return CSCMI_DEVICE_ERROR;
     if (!W.tm.timed(&g_write_ms[3], W.S.launches, [&] { launch_gather_extents(d_gp.p, (uint32_t)gp.size(), W.tm.st); })) return CSCMI_DEVICE_ERROR;
@@ -1105,10 +1191,13 @@ int dev_place(WriteCtx &W, const std::vector<CSCMIDevEncode> &jobs, const uint8_
     return 0;
 }
 
-// One wave: tasks [first, first + count) of the plan.  0, WRITE_ERROR or CSCMI_DEVICE_ERROR.
+// One wave: tasks [first, first + count) of the plan.  0, WRITE_ERROR, CSCMI_DEVICE_ERROR, or -1 (CSAMI_DeviceUpdate: a reused
+// stream does not end at its length).  A task CSAMI_DeviceUpdate reuses is neither gathered nor summed nor encoded: its stream is
+// placed from the base archive beside the encoded ones, and its block table taken where it was placed.
 int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
 {
     using namespace csadev;
+    auto reused = [&](size_t k) { return W.upd && W.upd->reused(first + k); };
     // 1. where each task's raw bytes lie: one range of one entry that lies inside one run of its slice is encoded where it is,
     // anything else is gathered
     std::vector<const uint8_t *> in(count, nullptr);
@@ -1123,6 +1212,7 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
         for (FilePiece &f : t.files) {
             f.posblock = cum;                                                // csa_io.h:239
             cum += f.size;
+            if (reused(k)) continue;
             if (f.size) {
                 uint64_t src;
                 nonempty++;
@@ -1146,7 +1236,7 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
 
     // 2. gather and sum in one pass: the fragments of the gathered tasks, whose pieces are stored, first -- through k_frag_rows if
     // one of them crosses a run border, else as the CopyPieces they all are; then those of the tasks encoded where they lie, whose
-    // pieces are only summed
+    // pieces are only summed (but for a task whose fragments the update's check has summed already)
     {
         FragTables T;
         std::vector<FilePiece *> ff_piece;
@@ -1164,7 +1254,7 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
         const bool rows = std::any_of(T.gpieces.begin(), T.gpieces.end(), [](const GatherPiece &g) { return g.stride != 0; });
         if (!rows) T.gathered_as_plain();
         for (size_t k = 0; k < count; k++) {
-            if (gathered[k]) continue;
+            if (gathered[k] || reused(k) || (W.upd && W.upd->tasks[first + k].have_sums)) continue;
             for (FilePiece &f : P.tasks[first + k].files) {
                 f.checksum = 0;
                 if (!f.size) continue;
@@ -1190,11 +1280,13 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
         }
     }
 
-    // 3. encode: csa_worker.cpp:23-56 for every task of the wave at once, into scratch of this layer
-    std::vector<CSCMIDevEncode> jobs(count);
+    // 3. encode: csa_worker.cpp:23-56 for every task of the wave that is not reused at once, into scratch of this layer
+    std::vector<CSCMIDevEncode> jobs;
+    std::vector<size_t> job_of(count, SIZE_MAX);
     uint64_t scr_bytes = 0;
-    std::vector<uint64_t> scr_off(count);
+    std::vector<uint64_t> scr_off(count, 0);
     for (size_t k = 0; k < count; k++) {
+        if (reused(k)) continue;
         scr_off[k] = scr_bytes;
         scr_bytes += (stream_cap(W, P.tasks[first + k].total) + 255) & ~255ull;
     }
@@ -1202,25 +1294,44 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
     std::list<DevBuf> more;
     if (!d_scr.alloc(scr_bytes)) return CSCMI_DEVICE_ERROR;
     for (size_t k = 0; k < count; k++) {
+        if (reused(k)) continue;
         const Task &t = P.tasks[first + k];
-        CSCMIDevEncode &j = jobs[k];
+        CSCMIDevEncode j;
         memset(&j, 0, sizeof(j));
         CSCEncProps_Init(&j.props, (uint32_t)std::min<uint64_t>(P.o.dict_size, t.total), P.o.level);   // csa_worker.cpp:35
         j.src = t.total ? (const void *)in[k] : d_scr.p;                     // (no byte of it is loaded when the task is empty)
         j.src_size = (size_t)t.total;
         j.dst = (uint8_t *)d_scr.p + scr_off[k];
         j.dst_cap = (size_t)stream_cap(W, t.total);
+        job_of[k] = jobs.size();
+        jobs.push_back(j);
     }
-    int rc = dev_encode(W, jobs, more);
+    int rc = jobs.empty() ? 0 : dev_encode(W, jobs, more);
     if (rc) return rc;
 
-    // 4. block tables: BlockSink::put over the Write sizes the file path would have seen
+    // 4. placement (csa_io.h:559-573; id == task index, csarc.cpp:393-394): it needs the streams' sizes alone
+    std::vector<Placed> items(count);
+    std::vector<uint64_t> at;
+    for (size_t k = 0; k < count; k++) {
+        if (reused(k)) { const UpdTask &u = W.upd->tasks[first + k]; items[k] = Placed{nullptr, &u.ext, W.upd->base->arc, u.stream}; }
+        else items[k] = Placed{&jobs[job_of[k]], nullptr, nullptr, 0};
+    }
+    rc = dev_place(W, items, nullptr, &at);
+    if (rc) return rc;
+
+    // 5. block tables: BlockSink::put over the Write sizes the file path would have seen -- of an encoded stream where it lies in
+    // scratch, of a reused one where it was placed, so that its table is this writer's whatever cut the base into blocks
     std::vector<BlockTableJob> bj(count);
     uint64_t slots = 0;
     for (size_t k = 0; k < count; k++) {
-        const uint64_t mb = table_bound(jobs[k].produced, jobs[k].props.csc_blocksize);
+        CSCProps props;
+        if (reused(k)) CSCEncProps_Init(&props, (uint32_t)std::min<uint64_t>(P.o.dict_size, P.tasks[first + k].total), P.o.level);   // (its 10 bytes are these props')
+        else props = jobs[job_of[k]].props;
+        const uint64_t produced = items[k].bytes() - CSC_PROP_SIZE;
+        const uint64_t mb = table_bound(produced, props.csc_blocksize);
         if (mb > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
-        bj[k] = BlockTableJob{(const uint8_t *)jobs[k].dst, (uint64_t)jobs[k].produced, jobs[k].props.csc_blocksize, (uint32_t)mb, slots};
+        const uint8_t *stream = reused(k) ? W.arc + at[k] + CSC_PROP_SIZE : (const uint8_t *)jobs[job_of[k]].dst;
+        bj[k] = BlockTableJob{stream, produced, props.csc_blocksize, (uint32_t)mb, slots};
         slots += mb;
     }
     std::vector<BlockTableRes> br(count);
@@ -1236,6 +1347,11 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
         uint64_t nb = 0;
         for (size_t k = 0; k < count; k++) {
             if (br[k].status != kTableOk || br[k].nblocks > bj[k].max_blocks) {
+                if (reused(k)) {
+                    fprintf(stderr, "csa-mi355x: task %zu: the stream reused from the base archive does not end at its length (block table status %u)\n",
+                            first + k, br[k].status);
+                    return -1;
+                }
                 fprintf(stderr, "csa-mi355x: task %zu: its stream does not end where its encoder said (block table status %u)\n", first + k, br[k].status);
                 return CSCMI_DEVICE_ERROR;
             }
@@ -1247,16 +1363,178 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
         W.S.blocks += nb;
     }
 
-    // 5. placement, and the tasks' extents (csa_io.h:559-573; id == task index, csarc.cpp:393-394)
-    uint64_t pos = W.arc_end;
-    size_t at = 0;
+    // 6. the tasks' extents
+    size_t nx = 0;
     for (size_t k = 0; k < count; k++) {
         std::vector<Extent> &ext = W.abindex[first + k];
-        const uint64_t begin = pos;
-        for (uint32_t i = 0; i < br[k].nblocks; i++, at++) { ext.push_back(Extent{pos, sizes[at]}); pos += sizes[at]; }
-        if (pos - begin != CSC_PROP_SIZE + (uint64_t)jobs[k].produced) return CSCMI_DEVICE_ERROR;
+        uint64_t pos = at[k];
+        for (uint32_t i = 0; i < br[k].nblocks; i++, nx++) { ext.push_back(Extent{pos, sizes[nx]}); pos += sizes[nx]; }
+        if (pos - at[k] != items[k].bytes()) return reused(k) ? -1 : CSCMI_DEVICE_ERROR;
     }
-    return dev_place(W, jobs, nullptr);
+    return 0;
+}
+
+// One check wave of CSAMI_DeviceUpdate: candidates cand[first, first + count).  Three launches whatever the mode: k_gather_extents
+// (every candidate's 10 property bytes and, where the streams are decoded, those of more than one archive block), the compare
+// kernel or the sum pass, and the fold.  A candidate leaves as CSA_UPD_REUSED -- its fragments' checksums those of this pass -- or
+// as PROPS, CHANGED or BASE_BAD.  0 or CSCMI_DEVICE_ERROR.
+int dev_check_wave(WriteCtx &W, UpdateCtx &U, AddPlan &P, const std::vector<size_t> &cand, size_t first, size_t count)
+{
+    using namespace csadev;
+    const CSADevArchive &A = *U.base;
+    // 1. the streams: what has to be gathered, where the decoded bytes go
+    std::vector<uint64_t> gat_off(count, 0), raw_off(count, 0);
+    uint64_t gat_bytes = 0, raw_bytes = 0;
+    for (size_t k = 0; k < count && !U.trust; k++) {
+        const UpdTask &u = U.tasks[cand[first + k]];
+        uint64_t r;
+        if (u.stream > CSC_PROP_SIZE && u.ext.size() > 1) {
+            gat_off[k] = gat_bytes;
+            if (!add_ok(u.stream - CSC_PROP_SIZE, 255, &r) || !add_ok(gat_bytes, r & ~255ull, &gat_bytes)) return CSCMI_DEVICE_ERROR;
+        }
+        raw_off[k] = raw_bytes;
+        if (!add_ok(P.tasks[cand[first + k]].total, 255, &r) || !add_ok(raw_bytes, r & ~255ull, &raw_bytes)) return CSCMI_DEVICE_ERROR;
+    }
+    DevBuf d_gat, d_raw, d_props;
+    if (!d_gat.alloc(gat_bytes) || !d_raw.alloc(raw_bytes) || !d_props.alloc(16 * count)) return CSCMI_DEVICE_ERROR;
+
+    // 2. gather, and the property bytes back: a candidate whose 10 bytes are not what this call's encoder would write is out
+    std::vector<CopyPiece> gp;
+    for (size_t k = 0; k < count; k++) {
+        const UpdTask &u = U.tasks[cand[first + k]];
+        uint64_t pos = 0;                                                    // position in the task's stream
+        for (const Extent &x : u.ext) {
+            const uint8_t *src = A.arc + x.off;
+            uint64_t n = x.size;
+            if (pos < CSC_PROP_SIZE) {
+                const uint64_t h = std::min<uint64_t>(CSC_PROP_SIZE - pos, n);
+                gp.push_back(CopyPiece{src, (uint8_t *)d_props.p + 16 * k + pos, (uint32_t)h, 0});
+                src += h; n -= h; pos += h;
+            }
+            if (!U.trust && u.ext.size() > 1 && n)
+                piece_split(src, (uint8_t *)d_gat.p + gat_off[k] + (pos - CSC_PROP_SIZE), n, kGatherPiece,
+                            [&](uint64_t, const CopyPiece &p) { gp.push_back(p); });
+            pos += n;
+            if (U.trust && pos >= CSC_PROP_SIZE) break;
+        }
+    }
+    if (gp.size() > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
+    std::vector<uint8_t> props(16 * count, 0);
+    {
+        DevBuf d_gp;
+        if (!dev_upload(W, d_gp, gp.data(), gp.size() * sizeof(CopyPiece))) return CSCMI_DEVICE_ERROR;
+        if (!W.tm.timed(&U.ms, U.U.check_launches, [&] { launch_gather_extents(d_gp.p, (uint32_t)gp.size(), W.tm.st); })) return CSCMI_DEVICE_ERROR;
+        if (!HIP_OK(hipMemcpy(props.data(), d_props.p, props.size(), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+        W.S.readback_bytes += CSC_PROP_SIZE * count;
+    }
+    for (size_t k = 0; k < count; k++) {
+        UpdTask &u = U.tasks[cand[first + k]];
+        CSCProps want;
+        uint8_t wb[CSC_PROP_SIZE];
+        CSCEncProps_Init(&want, (uint32_t)std::min<uint64_t>(P.o.dict_size, P.tasks[cand[first + k]].total), P.o.level);
+        CSCEnc_WriteProperties(&want, wb, 0);
+        if (u.stream < CSC_PROP_SIZE) { u.candidate = false; u.status = U.trust ? CSA_UPD_PROPS : CSA_UPD_BASE_BAD; }   // (no property bytes, no decoder)
+        else if (memcmp(wb, props.data() + 16 * k, CSC_PROP_SIZE) != 0) { u.candidate = false; u.status = CSA_UPD_PROPS; }
+    }
+
+    // 3. verify: the base streams decoded, as CSAMI_DeviceCompareSlices decodes them -- reusable only if the stream decodes, gives
+    // exactly the task's bytes and is consumed to its last byte
+    if (!U.trust) {
+        std::vector<CSCMIDevDecode> jobs;
+        std::vector<size_t> job_task;
+        for (size_t k = 0; k < count; k++) {
+            const UpdTask &u = U.tasks[cand[first + k]];
+            if (!u.candidate) continue;
+            CSCMIDevDecode j;
+            memset(&j, 0, sizeof(j));
+            CSCDec_ReadProperties(&j.props, props.data() + 16 * k);
+            j.src = u.ext.size() > 1 ? (const uint8_t *)d_gat.p + gat_off[k] : A.arc + u.ext[0].off + CSC_PROP_SIZE;
+            j.src_size = (size_t)(u.stream - CSC_PROP_SIZE);
+            j.dst = (uint8_t *)d_raw.p + raw_off[k];
+            j.dst_cap = (size_t)P.tasks[cand[first + k]].total;
+            jobs.push_back(j);
+            job_task.push_back(k);
+        }
+        if (!jobs.empty()) {
+            CSCMIDevDecodeStats ds;
+            memset(&ds, 0, sizeof(ds));
+            if (CSCMI_DecodeDeviceBatch((int)jobs.size(), jobs.data(), NULL, &ds) != 0) return CSCMI_DEVICE_ERROR;
+            U.U.decode_launches += ds.launches;
+            for (size_t i = 0; i < jobs.size(); i++) {
+                if (jobs[i].rc == CSCMI_DEVICE_ERROR) return CSCMI_DEVICE_ERROR;
+                UpdTask &u = U.tasks[cand[first + job_task[i]]];
+                U.U.decoded_bytes += std::min<uint64_t>(jobs[i].produced, jobs[i].dst_cap);
+                if (jobs[i].rc != 0 || jobs[i].produced != jobs[i].dst_cap || jobs[i].consumed != jobs[i].src_size) {
+                    u.candidate = false;
+                    u.status = CSA_UPD_BASE_BAD;
+                }
+            }
+        }
+    }
+
+    // 4. the candidates' fragments: the decoded bytes against the caller's (verify), or the caller's summed where they lie and
+    // folded against the base index's checksums (trust)
+    FragTables T;
+    std::vector<FilePiece *> ff_piece;
+    std::vector<size_t> ff_task;
+    CSADevSpreadStats X;
+    CSADevGatherStats G;
+    memset(&X, 0, sizeof(X));
+    memset(&G, 0, sizeof(G));
+    for (size_t k = 0; k < count; k++) {
+        const size_t ti = cand[first + k];
+        const UpdTask &u = U.tasks[ti];
+        if (!u.candidate) continue;
+        size_t fi = 0;
+        for (FilePiece &f : P.tasks[ti].files) {
+            const uint32_t base_sum = u.base_sums[fi++];
+            if (!f.size) { f.checksum = 0; continue; }                         // adler32 of nothing, seed 0
+            const bool ok = U.trust ? T.add_gathered(W.buf(f), nullptr, W.slice(f), f.off, f.size, G, base_sum)
+                                    : T.add_spread((const uint8_t *)d_raw.p + raw_off[k] + f.posblock, (uint8_t *)W.buf(f), W.slice(f), f.off, f.size, 0,
+                                                   f.size, true, X);
+            if (!ok) return CSCMI_DEVICE_ERROR;
+            ff_piece.push_back(&f);
+            ff_task.push_back(ti);
+            U.U.checked_bytes += f.size;
+        }
+    }
+    std::vector<uint8_t> differs(ff_piece.size(), 0);
+    if (U.trust) {
+        const bool rows = std::any_of(T.gpieces.begin(), T.gpieces.end(), [](const GatherPiece &g) { return g.stride != 0; });
+        const uint32_t np = (uint32_t)T.gpieces.size();
+        if (!rows) T.gathered_as_plain();
+        W.S.upload_bytes += T.upload_bytes();
+        std::vector<FragResult> res;
+        if (!T.upload()
+            || !W.tm.timed(&U.ms, U.U.check_launches, [&] {
+                   if (rows) launch_frag_rows(T.d_gpieces.p, T.d_sums.p, np, W.tm.st);
+                   else launch_frag_pieces(T.d_pieces.p, T.d_sums.p, np, false, W.tm.st); })
+            || !T.fold(W.tm, &U.ms, U.U.check_launches, res)) return CSCMI_DEVICE_ERROR;
+        W.S.readback_bytes += res.size() * sizeof(FragResult);
+        for (size_t i = 0; i < res.size(); i++) { ff_piece[i]->checksum = res[i].adler; differs[i] = !res[i].ok; }
+    } else {
+        const bool rows = T.xperiodic > 0;
+        if (!rows) T.spread_as_plain();
+        W.S.upload_bytes += T.upload_bytes();
+        std::vector<FragDiff> rd;
+        if (!T.upload(true)
+            || !W.tm.timed(&U.ms, U.U.check_launches, [&] {
+                   if (rows) launch_frag_compare_rows(T.d_pieces.p, T.d_sums.p, T.d_firsts.p, (uint32_t)T.xpieces.size(), W.tm.st);
+                   else launch_frag_compare(T.d_pieces.p, T.d_sums.p, T.d_firsts.p, (uint32_t)T.pieces.size(), W.tm.st); })
+            || !T.fold_diff(W.tm, &U.ms, U.U.check_launches, rd)) return CSCMI_DEVICE_ERROR;
+        W.S.readback_bytes += rd.size() * sizeof(FragDiff);
+        // (where no byte differs the sum of the decoded bytes is the sum of the caller's)
+        for (size_t i = 0; i < rd.size(); i++) { ff_piece[i]->checksum = rd[i].adler; differs[i] = rd[i].first < T.frags[i].size; }
+    }
+    for (size_t i = 0; i < differs.size(); i++)
+        if (differs[i]) { UpdTask &u = U.tasks[ff_task[i]]; u.candidate = false; u.status = CSA_UPD_CHANGED; }
+    for (size_t k = 0; k < count; k++) {
+        UpdTask &u = U.tasks[cand[first + k]];
+        if (u.candidate) u.status = CSA_UPD_REUSED;
+        else if (U.trust && u.status == CSA_UPD_CHANGED) u.have_sums = true;
+        u.candidate = false;
+    }
+    return 0;
 }
 
 }   // namespace
@@ -1318,17 +1596,46 @@ int CSAMI_DeviceWriteSlices(const void *const *ptrs, const uint64_t *sizes, cons
                             const char *arcname, void *arc_dev, uint64_t arc_cap, const CSAOptions *opt, CSADevWriteStats *st,
                             CSADevGatherStats *gather_stats)
 {
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
+    if (n_files && (!sizes || !slices)) {                                    // (the update reads "both NULL" as "every entry whole")
+        if (st) memset(st, 0, sizeof(*st));
+        if (gather_stats) memset(gather_stats, 0, sizeof(*gather_stats));
+        for (double &m : g_write_ms) m = 0;
+        return -1;
+    }
+    return CSAMI_DeviceUpdate(nullptr, ptrs, sizes, slices, files, n_files, arcname, arc_dev, arc_cap, 0, opt, st, gather_stats, nullptr, nullptr, 0);
+}
+
+int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices, CSADevFile *files,
+                       uint32_t n_files, const char *arcname, void *arc_dev, uint64_t arc_cap, uint32_t flags, const CSAOptions *opt,
+                       CSADevWriteStats *st, CSADevGatherStats *gather_stats, CSADevUpdateStats *update_stats, CSADevUpdateTask *tasks,
+                       uint32_t task_cap)
+{
     const double t0 = now_s();
     if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
     WriteCtx W;
+    UpdateCtx U;
     memset(&W.S, 0, sizeof(W.S));
     memset(&W.G, 0, sizeof(W.G));
+    memset(&U.U, 0, sizeof(U.U));
     if (st) *st = W.S;
     if (gather_stats) *gather_stats = W.G;
+    if (update_stats) *update_stats = U.U;
     for (double &m : g_write_ms) m = 0;
     // ---- everything the host can refuse, before any launch
     uint64_t a1;
-    if (!arcname || (!arc_dev && arc_cap) || !add_ok((uintptr_t)arc_dev, arc_cap, &a1) || (n_files && (!ptrs || !sizes || !slices))) return -1;
+    if (!arcname || (!arc_dev && arc_cap) || !add_ok((uintptr_t)arc_dev, arc_cap, &a1) || (n_files && (!ptrs || !files || !sizes != !slices))) return -1;
+    // every entry whole: slices[i] = {0, esize, esize, 1} of a buffer of esize bytes (a table the write refuses is refused below)
+    std::vector<CSADevSlice> whole_sl;
+    std::vector<uint64_t> whole_sz;
+    if (!slices) {
+        whole_sl.assign(n_files, CSADevSlice{0, 0, 0, 0});
+        whole_sz.assign(n_files, 0);
+        for (uint32_t i = 0; i < n_files; i++)
+            if (files[i].esize > 0) { whole_sz[i] = (uint64_t)files[i].esize; whole_sl[i] = CSADevSlice{0, whole_sz[i], whole_sz[i], 1}; }
+        slices = whole_sl.data();
+        sizes = whole_sz.data();
+    }
     AddPlan P;
     int rc = plan_write(P, files, n_files, opt, &W.S.raw_bytes);
     if (rc) return rc;
@@ -1349,30 +1656,83 @@ int CSAMI_DeviceWriteSlices(const void *const *ptrs, const uint64_t *sizes, cons
         if (!add_ok(G.hull_bytes, hull_size[i], &G.hull_bytes)) return -1;
     }
     if (CSAMI_CheckBuffers(hull.data(), hull_size.data(), n_files, arc_dev, arc_cap, 0, nullptr) != 0) return -1;
+    if (base && arc_cap && base->arc_size) {                                 // the base is read while arc is written: updating in place is out of scope
+        const uint64_t b0 = (uint64_t)(uintptr_t)base->arc, x0 = (uint64_t)(uintptr_t)arc_dev;
+        if (x0 <= b0 + (base->arc_size - 1) && b0 <= x0 + (arc_cap - 1)) return -1;
+    }
     if (arc_cap < kHeaderSize) return WRITE_ERROR;
     if (const char *e = getenv("CSA_DEVWRITE_SLACK")) { W.slack = (int64_t)strtoull(e, nullptr, 10); if (W.slack < 0) W.slack = -1; }
     W.ptrs = ptrs; W.slices = sl.data(); W.arc = (uint8_t *)arc_dev; W.arc_cap = arc_cap;
     W.G = G;
     if (!W.tm.ok) return CSCMI_DEVICE_ERROR;
 
-    // ---- waves of consecutive task ids, largest first (csarc.cpp:355): the plan's order and the archive's
     size_t mem_free = 0, mem_total = 0;
     if (!HIP_OK(hipMemGetInfo(&mem_free, &mem_total))) return CSCMI_DEVICE_ERROR;
     const uint64_t budget = hbm_budget(P.o, mem_free);
+
+    // ---- the update: which tasks of the plan are a task of the base (host), and whether their bytes are still the base's (check waves)
+    if (base) {
+        const double tc = now_s();
+        W.upd = &U;
+        U.base = base;
+        U.trust = (flags & CSAMI_UPDATE_TRUST_SUMS) != 0;
+        U.tasks.resize(P.tasks.size());
+        std::vector<uint64_t> bids;
+        std::vector<std::vector<uint32_t>> sums;
+        U.U.candidates = update_candidates(base->index, P, bids, sums);
+        static const std::vector<Extent> kNoBlocks;
+        std::vector<size_t> cand;
+        for (size_t i = 0; i < P.tasks.size(); i++) {
+            if (bids[i] == UINT64_MAX) continue;
+            UpdTask &u = U.tasks[i];
+            u.base_bid = bids[i];
+            u.candidate = true;
+            u.base_sums.swap(sums[i]);
+            auto ab = base->abindex.find(bids[i]);
+            if (!dev_stream_extents(ab == base->abindex.end() ? kNoBlocks : ab->second, base->arc_size, u.ext, u.stream)) return CSCMI_DEVICE_ERROR;
+            cand.push_back(i);
+        }
+        // waves as CSAMI_DeviceRead sizes them (a wave that only sums holds no decoder and no scratch)
+        const size_t cwidth = P.o.device_streams > 0 ? (size_t)P.o.device_streams : std::max<size_t>(cand.size(), 1);
+        for (size_t first = 0; rc == 0 && first < cand.size();) {
+            const size_t count = wave_count(first, cand.size(), cwidth, budget, [&](size_t c) {
+                if (U.trust) return (uint64_t)0;
+                const uint64_t raw = P.tasks[cand[c]].total;
+                uint64_t need = std::min<uint64_t>(std::max<uint64_t>(raw, 1u << 20), 1ull << 30) + (24ull << 20);
+                if (!add_ok(need, raw, &need) || !add_ok(need, U.tasks[cand[c]].stream, &need)) need = UINT64_MAX;
+                return need;
+            });
+            rc = dev_check_wave(W, U, P, cand, first, count);
+            U.U.check_waves++;
+            first += count;
+        }
+        U.U.check_kernel_ms = U.ms;
+        U.U.seconds_check = now_s() - tc;
+    }
+
+    // ---- waves of consecutive task ids, largest first (csarc.cpp:355): the plan's order and the archive's
     size_t width = P.o.device_streams > 0 ? (size_t)P.o.device_streams : csadev::kTableMaxJobs;
     width = std::min<size_t>(width, csadev::kTableMaxJobs);
     for (size_t first = 0; rc == 0 && first < P.tasks.size();) {
-        // what the task's encoder holds (as encode_tasks reckons), a gathered copy of its input (at most) and its scratch stream
+        // what the task's encoder holds (as encode_tasks reckons), a gathered copy of its input (at most) and its scratch stream;
+        // a reused task holds nothing
         const size_t count = wave_count(first, P.tasks.size(), width, budget, [&](size_t i) {
             const Task &t = P.tasks[i];
+            if (W.upd && U.reused(i)) return (uint64_t)0;
             CSCProps p;
             CSCEncProps_Init(&p, (uint32_t)std::min<uint64_t>(P.o.dict_size, t.total), P.o.level);
-            return CSCEnc_EstMemUsage(&p) + (24ull << 20) + t.total + stream_cap(W, t.total);
+            return (uint64_t)(CSCEnc_EstMemUsage(&p) + (24ull << 20) + t.total + stream_cap(W, t.total));
         });
         rc = dev_write_wave(W, P, first, count);
         W.S.waves++;
         for (size_t k = first; k < first + count; k++) { W.S.tasks++; W.S.frags += P.tasks[k].files.size(); }
         first += count;
+    }
+    for (size_t i = 0; W.upd && i < P.tasks.size(); i++) {
+        const UpdTask &u = U.tasks[i];
+        if (u.status == CSA_UPD_REUSED) { U.U.reused_tasks++; U.U.reused_raw_bytes += P.tasks[i].total; U.U.reused_stream_bytes += u.stream; }
+        else { U.U.encoded_tasks++; U.U.encoded_raw_bytes += P.tasks[i].total; }
+        if (tasks && i < task_cap) tasks[i] = CSADevUpdateTask{u.base_bid, u.status, 0};
     }
 
     // ---- fragments, index stream, header: csarc.cpp:371-386, 219-288
@@ -1402,7 +1762,7 @@ int CSAMI_DeviceWriteSlices(const void *const *ptrs, const uint64_t *sizes, cons
             store_le(hdr + 8, W.arc_end, 8);
             store_le(hdr + 16, csize, 4);
             store_le(hdr + 20, raw.size(), 4);
-            rc = dev_place(W, job, hdr);
+            rc = dev_place(W, std::vector<Placed>(1, Placed{&job[0], nullptr, nullptr, 0}), hdr);
         }
         if (rc == 0) {
             W.S.index_raw_size = raw.size();
@@ -1419,7 +1779,26 @@ int CSAMI_DeviceWriteSlices(const void *const *ptrs, const uint64_t *sizes, cons
     W.S.seconds_total = now_s() - t0;
     if (st) *st = W.S;
     if (gather_stats) *gather_stats = W.G;
+    if (update_stats) *update_stats = U.U;
     return rc;
+}
+
+int CSAMI_PlanDeviceUpdate(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const CSADevFile *files, uint32_t n_files,
+                           const CSAOptions *opt, uint64_t *base_bids, uint32_t cap, uint32_t *n_tasks, uint32_t *n_candidates)
+{
+    Index index;
+    DevLayout L;
+    if (!dev_plan_strict(raw_index, raw_size, arc_size, nullptr, 0, index, L)) return -1;
+    AddPlan P;
+    const int rc = plan_write(P, files, n_files, opt, nullptr);
+    if (rc) return rc;
+    std::vector<uint64_t> bids;
+    std::vector<std::vector<uint32_t>> sums;
+    const uint32_t n = update_candidates(index, P, bids, sums);
+    for (size_t i = 0; base_bids && i < bids.size() && i < cap; i++) base_bids[i] = bids[i];
+    if (n_tasks) *n_tasks = (uint32_t)bids.size();
+    if (n_candidates) *n_candidates = n;
+    return 0;
 }
 
 void CSAMI_DeviceWriteKernelMs(double ms[4])

@@ -17,7 +17,8 @@
 //   k_frag_slices         k_frag_pieces<true> for CSAMI_DeviceReadSlices: a piece is still summed whole, and the bytes of it that its
 //                         entry's slice selects -- all, none, or the runs of a periodic pattern -- go to their packed places
 //   k_frag_rows           k_frag_pieces<true> for CSAMI_DeviceWriteSlices, the transpose of k_frag_slices: a piece's destination is
-//                         contiguous and its source is the runs of a periodic pattern in the caller's buffer (or one range of it)
+//                         contiguous and its source is the runs of a periodic pattern in the caller's buffer (or one range of it);
+//                         without a destination it is the sum-only pass of CSAMI_DeviceUpdate's check
 //   k_frag_spread         k_frag_pieces<true> for CSAMI_DeviceReadIntoSlices, the transpose of k_frag_rows: a piece's source is contiguous
 //                         and its destination is the runs of a periodic pattern in the caller's buffer (or one range of it, or none)
 //   k_frag_compare_rows   k_frag_compare for CSAMI_DeviceCompareSlices: the piece against such rows instead of one range
@@ -121,14 +122,18 @@ __global__ __launch_bounds__(kThreads) void k_frag_slices(const SlicePiece *piec
 }
 
 // k_frag_pieces<true> for CSAMI_DeviceWriteSlices: a piece whose packed bytes lie inside one run of its entry's slice is copy_sum's
-// as there; any other is gathered across the run borders (gather_sum, csa_dev_write.h).  Which of the two: the same for the whole
-// workgroup.
+// as there; any other is gathered across the run borders (gather_sum, csa_dev_write.h).  A piece without a destination
+// (CSAMI_DeviceUpdate's check against the base's checksums) is summed and not stored, as in k_frag_pieces<true>.  Which of the four:
+// the same for the whole workgroup.
 __global__ __launch_bounds__(kThreads) void k_frag_rows(const GatherPiece *pieces, PieceSums *out, uint32_t npieces)
 {
     if (blockIdx.x >= npieces) return;
     const GatherPiece pc = pieces[blockIdx.x];
     uint64_t a = 0, b = 0;
-    if (pc.stride) gather_sum(pc, threadIdx.x, kThreads, a, b);
+    if (pc.dst == nullptr) {
+        if (pc.stride) gather_sum<kGPlantNone, false>(pc, threadIdx.x, kThreads, a, b);
+        else copy_sum<false, true>(nullptr, pc.src, pc.len, threadIdx.x, kThreads, a, b);
+    } else if (pc.stride) gather_sum(pc, threadIdx.x, kThreads, a, b);
     else copy_sum<true, true>(pc.dst, pc.src, pc.len, threadIdx.x, kThreads, a, b);
     store_sums(a, b, out + blockIdx.x);
 }

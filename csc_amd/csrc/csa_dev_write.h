@@ -118,13 +118,15 @@ CSADEV_FHD uint32_t block_table(Load ld, uint64_t produced, uint32_t bsize, uint
 
 enum GatherPlant {
     kGPlantNone = 0, kGPlantBorderLate = 1, kGPlantPhaseDropped = 2, kGPlantStraddleContiguous = 3, kGPlantRowNotAdvanced = 4,
-    kGPlantWindowPastHull = 5
+    kGPlantWindowPastHull = 5,
+    // the form that only sums (tests/model/csa_dev_sum_only_model.cpp)
+    kGPlantSumTailDropped = 6, kGPlantSumStillStores = 7
 };
 
 struct GatherPiece {       // one workgroup of k_frag_rows
     const uint8_t *src;    // stride == 0: the piece's one contiguous source (copy_sum<true, true>, as a CopyPiece);
                            // else the address of period position 0, inside the hull (what lies in front of `phase` is not loaded)
-    uint8_t *dst;          // the piece's contiguous destination
+    uint8_t *dst;          // the piece's contiguous destination; NULL: the piece is summed, not stored
     uint64_t stride;       // periodic: the address step from one run to the next, >= run
     uint32_t len;          // <= kFragPiece
     uint32_t phase;        // periodic: byte i of the piece is period position pos = phase + i; row = pos / run, r = pos % run; it lies
@@ -170,20 +172,26 @@ CSADEV_FHD bool gather_reduce(const Slice &s, uint64_t at, uint32_t len, GatherC
 // segment, byte by byte.  The sums are over packed positions, as one piece of len bytes: exactly copy_sum<true, true>'s over the
 // packed bytes.  No division in the unit loop: a thread's (row, r) advances by the workgroup's step, 16 * nthreads packed
 // positions, with one carry.
-template <int PLANT = kGPlantNone>
+//
+// STORE == false (CSAMI_DeviceUpdate's check of a piece against the base's checksum; k_frag_rows with dst == NULL): the piece is
+// summed and nothing is stored -- pc.dst is not looked at.  There is no destination to anchor on, so the 16-byte units begin at
+// the piece's packed position 0 (no head, up to 15 tail bytes); a unit's load window is still checked against the hull.  The sums
+// are those of the storing form, whatever its destination's alignment.
+template <int PLANT = kGPlantNone, bool STORE = true>
 CSADEV_FHD void gather_sum(const GatherPiece &pc, uint32_t tid, uint32_t nthreads, uint64_t &a, uint64_t &b)
 {
+    constexpr bool kStores = STORE || PLANT == kGPlantSumStillStores;
     const uint8_t *src = pc.src;
     uint8_t *dst = pc.dst;
     const uint32_t n = pc.len, run = pc.run;
     const uint64_t stride = pc.stride;
-    uint32_t head = (0u - (uint32_t)(uintptr_t)dst) & 15u;
+    uint32_t head = STORE ? (0u - (uint32_t)(uintptr_t)dst) & 15u : 0u;
     if (head > n) head = n;
-    const uint32_t units = (n - head) >> 4, tail = (n - head) & 15u;
+    const uint32_t units = (n - head) >> 4, tail = !STORE && PLANT == kGPlantSumTailDropped ? 0u : (n - head) & 15u;
     auto one = [&](uint32_t idx) {
         const uint32_t pos = pc.phase + idx, row = pos / run, r = pos - row * run;
         const uint32_t v = src[row * stride + r];
-        dst[idx] = (uint8_t)v;
+        if (kStores) dst[idx] = (uint8_t)v;
         a += v;
         b += (uint64_t)(n - idx) * v;
     };
@@ -208,7 +216,7 @@ CSADEV_FHD void gather_sum(const GatherPiece &pc, uint32_t tid, uint32_t nthread
                 if (++r1 == border) { r1 = 0; p += stride - run; }
             }
         }
-        *(Vec16 *)(dst + i0) = o;
+        if (kStores) *(Vec16 *)(dst + i0) = o;
         sum_word(o.w[0], i0, n, a, b);
         sum_word(o.w[1], i0 + 4, n, a, b);
         sum_word(o.w[2], i0 + 8, n, a, b);

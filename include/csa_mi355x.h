@@ -429,8 +429,9 @@ int CSAMI_DeviceCompare(CSADevArchive *a, const char *const *names, int nnames, 
  * a 16-byte unit inside one run stored as 16 bytes, a unit across a run border byte by byte.  Its table entry holds 32-bit
  * quantities whatever run and stride are.  Nothing outside a fragment's decoded bytes is loaded, not even by an aligned 16-byte
  * window, and nothing but the selected bytes' destinations is stored.
- * Out of scope: stopping inside a fragment, a slice of an entry into a slice of a buffer in one call, updating a slice, and the host
- * paths (CSA_Extract / CSA_Test). */
+ * Out of scope: stopping inside a fragment, a slice of an entry into a slice of a buffer in one call, updating a slice in place (an
+ * update that writes a new archive and copies the unchanged tasks' streams is CSAMI_DeviceUpdate), and the host paths (CSA_Extract /
+ * CSA_Test). */
 typedef struct CSADevSlice { uint64_t offset, run, stride, count; } CSADevSlice;
 typedef struct CSADevSliceStats {
     uint64_t selected_bytes;    /* sum of run * count over the entries */
@@ -490,7 +491,8 @@ int CSAMI_PlanDeviceSlices(const uint8_t *raw_index, uint64_t raw_size, uint64_t
  * Safety contract.  Nothing outside an entry's hull is loaded, not even by an aligned 16-byte window.  Gap bytes inside the hull may
  * be loaded; they are never summed and never stored.  Nothing of the caller's is written.  The bus contract is CSAMI_DeviceWrite's,
  * with 56 bytes in the place of 24 for a stored piece of a wave that runs k_frag_rows: no file byte and no stream byte crosses.
- * Out of scope: updating part of an existing archive, and the host paths (CSA_Add).  The way back -- a read into, and a comparison
+ * Out of scope: updating an existing archive in place (CSAMI_DeviceUpdate writes a new one and reuses the streams of the unchanged
+ * tasks), and the host paths (CSA_Add).  The way back -- a read into, and a comparison
  * against, a slice of a buffer -- is the next section. */
 typedef struct CSADevGatherStats {
     uint64_t selected_bytes;    /* sum of run * count: the entries' bytes */
@@ -544,7 +546,8 @@ int CSAMI_DeviceWriteSlices(const void *const *ptrs, const uint64_t *sizes, cons
  * checked against the hull: gap bytes may be loaded by the comparison; they are never compared.  A unit across a run border goes
  * byte by byte.  With run < 16 every unit crosses a border: that is the slow path (profiles/archive_device_spread.md), and no
  * rate is promised for it.  Nothing outside a hull is loaded or stored, not even by an aligned 16-byte window.
- * Out of scope: a slice of an entry into a slice of a buffer in one call, updating an archive in place, and the host paths. */
+ * Out of scope: a slice of an entry into a slice of a buffer in one call, updating an archive in place (CSAMI_DeviceUpdate writes a
+ * new archive beside the old one), and the host paths. */
 typedef struct CSADevSpreadStats {
     uint64_t selected_bytes;    /* sum over the entries of the bytes delivered / compared: min(size_i, run * count) */
     uint64_t hull_bytes;        /* sum of the slices' hulls: (count - 1) * stride + run */
@@ -568,6 +571,84 @@ int CSAMI_DeviceReadIntoSlices(CSADevArchive *a, const char *const *names, int n
 int CSAMI_DeviceCompareSlices(CSADevArchive *a, const char *const *names, int nnames, const void *const *ptrs, const uint64_t *sizes,
                               const CSADevSlice *slices, uint32_t n, uint32_t flags, const CSAOptions *o, CSADevFile *files,
                               CSADevDiff *diffs, CSADevReadStats *st, CSADevStopStats *stop_stats, CSADevSpreadStats *spread_stats);
+
+/* ---- update: CSAMI_DeviceWriteSlices that copies the streams of unchanged tasks out of an archive already in HBM; not in the reference ----
+ *
+ * A state dict is written again and again, and most of its bytes are last time's.  A task stream is a pure function of the task's
+ * bytes, `level` and the properties CSCEncProps_Init(min(dict_size, total), level) gives, and the plan depends on names and sizes
+ * alone.  So where a task of the new plan has the composition and the bytes of a task of `base` -- a handle from CSAMI_DeviceOpen --
+ * the stream in the base archive IS the stream the encoder would write, and it is copied, not encoded.
+ *
+ * Contract.  arc[0, archive_bytes) is byte for byte what CSAMI_DeviceWriteSlices writes for the same arguments whenever the reused
+ * streams were written at the same `level` by this library or the reference.  The 10 property bytes do not record the level: that
+ * the base was written at this call's level is the CALLER's to ensure.  Otherwise arc is a valid `.csa` that holds those streams.
+ * Nothing of the caller's and nothing of the base is written; nothing outside a hull or the base buffer is loaded.
+ *
+ * Arguments are CSAMI_DeviceWriteSlices's and mean the same, refusals and return values included.  slices == NULL && sizes == NULL
+ * means every entry whole, as CSAMI_DeviceWriteFrom builds it (only one of them NULL: -1).  base == NULL makes the call exactly
+ * CSAMI_DeviceWriteSlices -- that call IS this one with base == NULL, so there is one write path.  Refused with -1, nothing launched
+ * and all three statistics zeroed, besides what the write refuses: [arc, arc + arc_cap) overlapping the base's archive buffer.
+ * Without a visible device CSCMI_DEVICE_ERROR is returned before any argument is looked at.
+ *
+ * Candidates (host; CSAMI_PlanDeviceUpdate is exactly this step over raw index bytes, as strict as CSAMI_PlanDeviceLayout).  A task
+ * of the new plan is a candidate for base task b when its total is above zero and the set of its fragments (name, offset in the
+ * entry, size, posblock), zero-size fragments included, equals the set of ALL fragments of the base index with bid b.  An entry
+ * of that base task missing from the table, one more entry, another size or another split make the sets differ: CSA_UPD_NEW.
+ * edate and eattr do not enter.  Found through one map from (name, offset) to the base's fragments, not by comparing tasks pairwise.
+ * A candidate whose 10 property bytes in the base (read back, 10 bytes a candidate, in st->readback_bytes) are not what
+ * CSCEnc_WriteProperties(CSCEncProps_Init(min(dict_size, total), level)) writes is CSA_UPD_PROPS.
+ *
+ * Check, default (verify).  The remaining candidates' base streams are decoded and compared with the caller's bytes by the machinery
+ * of CSAMI_DeviceCompareSlices, in waves sized as CSAMI_DeviceRead sizes them; no task that is not a candidate is decoded.  A task
+ * is reused when its stream decodes with rc 0, produces exactly the task's total, is consumed to its last byte and no compared
+ * byte differs; else it is CSA_UPD_BASE_BAD or CSA_UPD_CHANGED.  A reused fragment's checksum in the new index is the sum taken in
+ * this pass, not the base index's: a wrong checksum in the base neither blocks reuse nor survives it.
+ *
+ * Check, CSAMI_UPDATE_TRUST_SUMS.  Nothing is decoded.  Each candidate's fragments are summed where they lie in the caller's buffers
+ * (k_frag_pieces, or k_frag_rows without a destination where a piece crosses a run border) and folded against the base index's
+ * checksums; reused means every fragment's adler32 equals the base's.  THIS IS THE FORMAT'S OWN 32-BIT TEST AND NO MORE: two
+ * contents of equal size and equal adler32 are taken for equal -- the archive then holds the OLD bytes under the new table -- and
+ * the base's stream is trusted to be intact.  A candidate found CHANGED that is encoded where it lies keeps the checksums of this
+ * pass and is not summed again.
+ *
+ * A check wave is three launches in either mode, update_stats->check_launches == 3 * check_waves: k_gather_extents (the property
+ * bytes; in verify also the streams of more than one archive block), the compare kernel or the sum pass, and the fold.
+ *
+ * Write.  The waves run over consecutive ids as in the write; a reused task costs nothing in the budget and one slot of the width,
+ * and skips gather and encode.  Its base extents, the property bytes in front, are placed by the wave's one k_gather_extents launch
+ * together with the encoded streams, and its archive-block table is NOT the base index's: it comes from k_block_table over the
+ * placed stream, so it is the canonical one whatever cut the base into blocks.  st->launches <= 5 * st->waves + 2 holds.  If that
+ * walk finds a reused stream that does not end at its length the call returns -1 (in verify: unreachable for an intact decoder).
+ * gather_stats and st->retries count encoded tasks only; st->tasks, frags, blocks, raw_bytes and archive_bytes mean what they mean
+ * for the write.  tasks[i], i < min(task_cap, st->tasks), says what became of task i of the new plan.
+ * Out of scope: updating in place (arc inside the base buffer), reusing part of a task, the host paths, and a strong hash in the
+ * place of adler32. */
+#define CSAMI_UPDATE_TRUST_SUMS 1u
+typedef struct CSADevUpdateTask { uint64_t base_bid; uint32_t status; uint32_t reserved; } CSADevUpdateTask;   /* per task of the NEW plan, in id order */
+/* status */
+#define CSA_UPD_REUSED   0u   /* the base archive's stream was copied; base_bid says which */
+#define CSA_UPD_NEW      1u   /* no task of the base has this composition (base_bid = UINT64_MAX) */
+#define CSA_UPD_PROPS    2u   /* same composition, other 10 property bytes under these options */
+#define CSA_UPD_CHANGED  3u   /* same composition, a byte (or, with TRUST_SUMS, a sum) differs */
+#define CSA_UPD_BASE_BAD 4u   /* verify only: the base task's stream has no decoder, fails, ends early, holds more than its raw size,
+                                 or its decoder did not consume it to its last byte */
+typedef struct CSADevUpdateStats {
+    uint64_t candidates, reused_tasks, encoded_tasks;   /* candidates: what the host step found, before the property bytes */
+    uint64_t reused_raw_bytes, reused_stream_bytes, encoded_raw_bytes;   /* stream bytes: as placed, property bytes included */
+    uint64_t checked_bytes;      /* bytes of the caller's summed (TRUST_SUMS) or compared (verify) in the check phase */
+    uint64_t decoded_bytes;      /* verify: sum of `produced` of the base decodes; 0 with TRUST_SUMS */
+    uint64_t check_waves, check_launches, decode_launches;
+    double check_kernel_ms, seconds_check;
+} CSADevUpdateStats;
+int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices,
+                       CSADevFile *files, uint32_t n_files, const char *arcname, void *arc_dev, uint64_t arc_cap,
+                       uint32_t flags, const CSAOptions *o, CSADevWriteStats *st, CSADevGatherStats *gather_stats,
+                       CSADevUpdateStats *update_stats, CSADevUpdateTask *tasks, uint32_t task_cap);
+/* host only, no GPU: the candidate step.  base_bids[i], i < min(cap, *n_tasks): the base bid task i of the plan of `files` under o
+ * is a candidate for, or UINT64_MAX.  -1 for an index CSAMI_PlanDeviceLayout refuses and a table CSAMI_DeviceWritePlan refuses;
+ * CSA_TOO_MANY_FRAGMENTS as there. */
+int CSAMI_PlanDeviceUpdate(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const CSADevFile *files, uint32_t n_files,
+                           const CSAOptions *o, uint64_t *base_bids, uint32_t cap, uint32_t *n_tasks, uint32_t *n_candidates);
 
 /* YYYYMMDDHHMMSS <-> time_t, csa_common.cpp:3-39 */
 int64_t CSA_DecimalTime(int64_t unix_seconds);
