@@ -250,18 +250,95 @@ __device__ __noinline__ void lanes_copy16(gvec4 *d4, const gvec4 *s4, uint32_t n
 {
     for (uint32_t i = threadIdx.x & 63u; i < n16; i += 64) d4[i] = s4[i];
 }
-__device__ __noinline__ void lanes_copy8(gu8 *dst, const gu8 *src, uint32_t n)
+// 16 bytes at an arbitrary byte address: the aligned dwords that hold them + v_alignbyte (the fifth dword only where the address is
+// not dword-aligned: nothing is read beyond the dword that holds the last byte)
+DEV raw_vec4 load16u(const gu8 *p)
 {
-    for (uint32_t t = threadIdx.x & 63u; t < n; t += 64) dst[t] = src[t];
+    const uintptr_t a = (uintptr_t)p;
+    const uint32_t sh = (uint32_t)a & 3u;
+    const gu32 *q = (const gu32 *)(a & ~(uintptr_t)3);
+    const uint32_t d0 = q[0], d1 = q[1], d2 = q[2], d3 = q[3], d4 = sh ? q[4] : 0u;
+    raw_vec4 v;
+    v.x = __builtin_amdgcn_alignbyte(d1, d0, sh); v.y = __builtin_amdgcn_alignbyte(d2, d1, sh);
+    v.z = __builtin_amdgcn_alignbyte(d3, d2, sh); v.w = __builtin_amdgcn_alignbyte(d4, d3, sh);
+    return v;
+}
+// n16 units of 16 bytes between 16-byte-aligned buffers that do not overlap (__restrict__): eight units a lane are loaded before the
+// first is stored, so a pass is one round trip to memory, not eight.
+// (dst[t] = src[t] a lane at a time is a load, a wait and a store per iteration: the compiler keeps every load behind the store before it.)
+constexpr int kCopyBatch = 8;
+DEV void lanes_copy16_far(gvec4 *__restrict__ d4, const gvec4 *__restrict__ s4, uint32_t n16)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    for (uint32_t u0 = 0; u0 < n16; u0 += 64u * kCopyBatch) {
+        raw_vec4 v[kCopyBatch];
+#pragma unroll
+        for (int k = 0; k < kCopyBatch; k++) v[k] = s4[umin(u0 + 64u * k + lane, n16 - 1u)];      // (a lane beyond the last unit loads the last one again: no branch between the loads)
+#pragma unroll
+        for (int k = 0; k < kCopyBatch; k++) {
+            const uint32_t u = u0 + 64u * k + lane;
+            if (u < n16) d4[u] = v[k];
+        }
+    }
+}
+// A sub-block on its way into the stream: memcpy(wnd + wpos, src, n) (n <= kMinBlock) and the LDS stage of it -- sb[j] = the byte of
+// window position wpos - 16 + j, j in [first, n + 64): 16 bytes of history, the sub-block, 48 bytes of whatever the window holds
+// behind it.  src (the chunk buffer) and the window never overlap.  The copy goes in 16-byte units: a byte head up
+// to the window's 16-byte boundary, units, a byte tail.  The stage takes the sub-block's own bytes from src as well, so that only the
+// 64 bytes around it come from the window, which are loaded before the copy's first store: nothing here waits for a store.
+constexpr int kStageBatch = 4;
+__device__ __noinline__ void lanes_copy_stage(gu8 *__restrict__ wnd, const gu8 *__restrict__ src, uint8_t *sb, uint32_t wpos, uint32_t first, uint32_t n)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    gu8 *dst = wnd + wpos;
+    // the 64 bytes around the sub-block, one a lane: lanes 0-15 the history (from `first`), lanes 16-63 the bytes behind it
+    const uint32_t j = lane < 16u ? lane : n + lane;
+    const bool around = lane >= 16u || lane >= first;
+    uint8_t ab = 0;
+    if (around) ab = (wnd + wpos - 16)[j];
+    // stage: unit u = bytes [16 u, 16 u + 16) of the sub-block -> sb + 16 + 16 u; byte tail
+    const uint32_t sn16 = n >> 4;
+    const uint32_t st = (sn16 << 4) + lane;
+    uint8_t stb = 0;
+    if (lane < 16u && st < n) stb = src[st];
+    // copy: head bytes up to the window's 16-byte boundary, units, tail bytes
+    const uint32_t head = umin(n, (16u - (wpos & 15u)) & 15u), cn16 = (n - head) >> 4;
+    const uint32_t ct = head + (cn16 << 4) + (lane - 16u);       // (lanes 16-31 carry the tail, lanes 0-15 the head)
+    uint8_t hb = 0;
+    if (lane < head) hb = src[lane];
+    else if (lane >= 16u && lane < 32u && ct < n) hb = src[ct];
+    // (what the LDS image guarantees is 8-byte alignment -- alignof(EncLds) -- so a unit goes out as one ds_write2_b64, not a ds_write_b128)
+    typedef __attribute__((address_space(3), aligned(8))) raw_vec4 lvec4;
+    static_assert(alignof(EncLds) % 8 == 0 && offsetof(EncLds, stage) % 8 == 0, "the stage's 16-byte units are written as two aligned 8-byte halves");
+    typedef __attribute__((address_space(3))) uint8_t lu8;
+    lu8 *sl = (lu8 *)sb;
+    lvec4 *s4 = (lvec4 *)(sl + 16);
+    gvec4 *d4 = (gvec4 *)(dst + head);
+    const gu8 *csrc = src + head;
+    // (four units a lane in flight, the stage first: a handful of round trips a sub-block, and few enough registers that the caller,
+    // which sees what this function clobbers, spills nothing around the call)
+    for (uint32_t u0 = lane; u0 < sn16; u0 += 64u * kStageBatch) {
+        raw_vec4 v[kStageBatch];
+#pragma unroll
+        for (int k = 0; k < kStageBatch; k++) v[k] = load16u(src + umin(u0 + 64u * k, sn16 - 1u) * 16u);      // (beyond the last unit: the last one again, no branch)
+#pragma unroll
+        for (int k = 0; k < kStageBatch; k++) if (u0 + 64u * k < sn16) s4[u0 + 64u * k] = v[k];
+    }
+    if (around) sl[j] = ab;
+    if (lane < 16u && st < n) sl[16u + st] = stb;
+    for (uint32_t u0 = lane; u0 < cn16; u0 += 64u * kStageBatch) {
+        raw_vec4 v[kStageBatch];
+#pragma unroll
+        for (int k = 0; k < kStageBatch; k++) v[k] = load16u(csrc + umin(u0 + 64u * k, cn16 - 1u) * 16u);
+#pragma unroll
+        for (int k = 0; k < kStageBatch; k++) if (u0 + 64u * k < cn16) d4[u0 + 64u * k] = v[k];
+    }
+    if (lane < head) dst[lane] = hb;
+    else if (lane >= 16u && lane < 32u && ct < n) dst[ct] = hb;
 }
 __device__ __noinline__ void lanes_fill32(gu32 *dst, uint32_t n, uint32_t v)
 {
     for (uint32_t t = threadIdx.x & 63u; t < n; t += 64) dst[t] = v;
-}
-// bytes [first, end) of the sub-block's LDS stage from the window (src[t] is the byte of stage position t)
-__device__ __noinline__ void lanes_stage(uint8_t *sb, const gu8 *src, uint32_t first, uint32_t end)
-{
-    for (uint32_t t = first + (threadIdx.x & 63u); t < end; t += 64) sb[t] = src[t];
 }
 // hand a finished RC/BC buffer to the host: header + 16-byte-lane copy
 DEV void emit_block(Sc &c, uint32_t kind, const gu8 *buf, uint32_t size)

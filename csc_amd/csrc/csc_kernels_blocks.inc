@@ -65,74 +65,135 @@ DEV void flt_forward_delta(Sc &c, gu8 *src, uint32_t size, uint32_t chn)
     wave_fence();
 }
 
-// Filters::Foward_Dict, csc_filters.cpp:256-335, 64 positions per step, one per lane, in ONE pass over the run:
-//  * every position's longest trie word from the eight bytes the lane has loaded (trie in LDS);
+// Filters::Foward_Dict, csc_filters.cpp:256-335, kDictW steps of 64 positions a pass (lane l of group g stands for position base + 64 g + l), in ONE pass
+// over the run:
+//  * every position's longest trie word from the eight bytes the lane has loaded.  The trie is packed into one word an edge while it is loaded into LDS --
+//    next node | (word index + 1) << 9, the word's symbol being 0x81 + that field -- so a level is one dependent LDS read, and the groups walk their levels in
+//    lock step: kDictW reads are in flight a level;
 //  * which positions are real token starts -- the greedy chain p -> p + advance(p) -- without walking it: with advances of 1..4
 //    "how far is the next token start" is a four-state automaton, a position is a function on its states (state 0: a token starts
-//    here, new state = advance - 1; else state - 1), and function composition is associative: a wave scan over the 64 functions
-//    (a byte per state: composing two is ONE v_perm_b32) gives every lane its state, the step's last function carries the chain
-//    into the next step;
-//  * the chosen lanes emit 1 or 2 bytes at ballot-prefix offsets.
+//    here, new state = advance - 1; else state - 1), and function composition is associative: a scan over a group's 64 functions
+//    (a byte per state: composing two is ONE v_perm_b32) gives every lane the function from the group's entry to itself.  The scans do not depend on the
+//    state the chain arrives in, so the groups' scans run side by side (DPP row shifts and row broadcasts: no LDS round trip); group g's entry state is
+//    group g - 1's total applied to its own, a lane read and a byte select a group, and the last group's carries the chain into the next pass;
+//  * the chosen lanes emit 1 or 2 bytes at ballot-prefix offsets.  Every lane stores -- one with nothing to emit into a dump slot beyond the
+//    2 * size bytes the output can take in the scratch -- so the stores of a pass are a fixed number and the wait for the next pass's bytes can count them instead of draining them.
 // Returns 1 if the run was replaced.
 DEV uint32_t umax16(uint32_t a, uint32_t b) { return a > b ? a : b; }
 // state -> B(A(state)) for functions kept as four bytes (byte s = image of state s): the later function's bytes selected by the earlier one's
 DEV uint32_t flt_compose(uint32_t A, uint32_t B) { return __builtin_amdgcn_perm(0u, B, A); }
+constexpr int kDictW = 2;                        // (measured against 4 and 8: profiles/dict_wide.md)
+constexpr uint32_t kFltIdent = 0x03020100u;      // the identity: what a position beyond the run's, or a lane a DPP shift brings nothing to, stands for
+constexpr uint32_t kTrieEdges = 300 * 26;
+// the lane's function moved along the wavefront: CTRL row_shr:n (0x110 + n), row_bcast:15 (0x142, ROWS 0xA), row_bcast:31 (0x143, ROWS 0xC), wave_shr:1 (0x138)
+template <int CTRL, int ROWS> DEV uint32_t flt_dpp(uint32_t v) { return (uint32_t)__builtin_amdgcn_update_dpp((int)kFltIdent, (int)v, CTRL, ROWS, 0xF, false); }
+DEV uint32_t flt_mbcnt(uint64_t m) { return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u)); }
+#define FLT_SCAN(CTRL, ROWS) _Pragma("unroll") for (int g = 0; g < W; g++) inc[g] = flt_compose(flt_dpp<CTRL, ROWS>(inc[g]), inc[g])
 DEV uint32_t flt_forward_dict(Sc &c, gu8 *src, uint32_t size)
 {
+    size = UNI(size);                                     // (arguments of the function-call form arrive in vector registers)
+    src = uni_gptr(src);
     if (size < 16384) return 0;
+    constexpr int W = kDictW;
     EncLds *L = c.L;
-    EncState *S = c.S;
-    gu8 *dst = c.swapbuf;
+    const GLOBAL_AS EncState *G = (const GLOBAL_AS EncState *)uni_gptr(c.S);
+    gu8 *dst = uni_gptr(c.swapbuf);
     const uint32_t n5 = size - 5;
-    // the trie borrows the LDS of the (idle) DP nodes for the duration of the filter
-    for (uint32_t i = c.lane; i < 300 * 26; i += 64) L->trie_next[i] = S->trie_next[i];
-    for (uint32_t i = c.lane; i < 300; i += 64) L->trie_sym[i] = S->trie_sym[i];
-    uint32_t s_in = 0, dst_size = 0, p = 0;
-    const uint64_t lower = (1ull << c.lane) - 1ull;
-    uint64_t v8n = load8u(src + c.lane);                  // (the next step's bytes travel while this step works)
-    for (uint32_t base = 0; base < n5; base += 64) {
-        const uint32_t i = base + c.lane;
-        const bool valid = i < n5;
-        const uint64_t v8 = v8n;
-        if (base + 64 < n5) v8n = load8u(src + i + 64);
-        const uint32_t b = (uint32_t)v8 & 0xFFu;
-        uint32_t sym = 0, adv = 1;
-        if (valid && b >= 'a' && b <= 'z') {
-            uint32_t node = 0;
-            for (uint32_t j = 0; j < 8;) {
-                const uint32_t idx = ((uint32_t)(v8 >> (8u * j)) & 0xFFu) - 'a';
-                if (idx > 25) break;
-                const uint32_t nx = L->trie_next[node * 26 + idx];
-                if (nx == 0) break;
-                node = nx;
-                j++;
-                const uint32_t ws = L->trie_sym[node];
-                if (ws) { sym = ws; adv = j; }
-            }
-        }
-        uint32_t inc = valid ? (((adv - 1u) & 3u) | 0x02010000u) : 0x03020100u;      // beyond the run's positions: the identity
+    // the trie borrows the LDS of the (idle) DP nodes for the duration of the filter; eight edges a lane are in flight
+    {
+        const gu16 *tn = (const gu16 *)G->trie_next;
+        const gu8 *ts = (const gu8 *)G->trie_sym;
+        for (uint32_t i0 = c.lane; i0 < kTrieEdges; i0 += 64u * 8u) {
+            uint32_t nx[8], sy[8];
 #pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const uint32_t t = (uint32_t)__shfl_up((int)inc, o);
-            inc = (int)c.lane >= o ? flt_compose(t, inc) : inc;
+            for (int k = 0; k < 8; k++) nx[k] = tn[umin(i0 + 64u * k, kTrieEdges - 1u)];
+#pragma unroll
+            for (int k = 0; k < 8; k++) sy[k] = ts[nx[k]];
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                if (i0 + 64u * k < kTrieEdges) L->trie_next[i0 + 64u * k] = (uint16_t)((nx[k] && sy[k]) ? nx[k] | ((sy[k] - 0x81u) << 9) : nx[k]);
         }
-        const uint32_t prev = (uint32_t)__shfl_up((int)inc, 1);
-        const uint32_t sb = c.lane == 0 ? s_in : (prev >> (8u * s_in)) & 3u;       // distance to the next token start, before this position
-        const bool mine = valid && sb == 0;
-        const uint64_t on = __ballot(mine);
-        const bool two = mine && sym == 0 && b >= 0x82;
-        const uint64_t m2 = __ballot(two);
-        const uint32_t off = dst_size + (uint32_t)__builtin_popcountll(on & lower) + (uint32_t)__builtin_popcountll(m2 & lower);
-        if (mine) {
-            if (sym) dst[off] = (uint8_t)sym;
-            else if (two) { dst[off] = 254; dst[off + 1] = (uint8_t)b; }
-            else dst[off] = (uint8_t)b;
-        }
-        dst_size += (uint32_t)__builtin_popcountll(on) + (uint32_t)__builtin_popcountll(m2);
-        const uint32_t vcount = umin(64u, n5 - base);
-        s_in = (rdlane(inc, vcount - 1) >> (8u * s_in)) & 3u;
-        p = base + vcount + s_in;                                        // (after the last step: where the chain leaves the walked range)
     }
+    uint32_t s_in = 0, dst_size = 0;
+    // The dump slot: 64 bytes at 3 * size.  The output is at most 2 * size bytes (every byte escaped), so anything from there on is free; 3 * size keeps the
+    // slot a whole `size` clear of it and inside the scratch, which the host allocates as 4 * raw_blocksize + 512 bytes (csc_host.cpp, o_swap) for runs of
+    // at most raw_blocksize + 256 bytes (the chunk buffer's size): 3 * size + 64 <= 3 * raw_blocksize + 832 < 4 * raw_blocksize + 512 from 16 384 up.
+    gu8 *const dump = dst + 3u * (size_t)size + c.lane;
+    // a lane's eight bytes: three aligned dwords + v_alignbyte.  The next pass's dwords travel while this pass works and are put together
+    // at its head; the byte offset inside the dword is the lane's own in every pass (a pass is 64 W positions on).  Positions beyond
+    // the walked range load the dwords of position n5 instead and are never looked at.
+    const uint32_t sh = (uint32_t)(uintptr_t)(src + c.lane) & 3u;
+    uint32_t rawn[W][3];
+#pragma unroll
+    for (int g = 0; g < W; g++) {
+        const gu32 *q = (const gu32 *)((uintptr_t)(src + umin(64u * g + c.lane, n5)) & ~(uintptr_t)3);
+        rawn[g][0] = q[0]; rawn[g][1] = q[1]; rawn[g][2] = q[2];
+    }
+    for (uint32_t base = 0; base < n5; base += 64u * W) {
+        uint64_t v8[W];
+        uint32_t b[W], sym[W], adv[W], node[W], inc[W];
+        bool valid[W], go[W];
+#pragma unroll
+        for (int g = 0; g < W; g++)
+            v8[g] = ((uint64_t)__builtin_amdgcn_alignbyte(rawn[g][2], rawn[g][1], sh) << 32) | __builtin_amdgcn_alignbyte(rawn[g][1], rawn[g][0], sh);
+#pragma unroll
+        for (int g = 0; g < W; g++) {
+            const gu32 *q = (const gu32 *)((uintptr_t)(src + umin(base + 64u * (W + g) + c.lane, n5)) & ~(uintptr_t)3);
+            rawn[g][0] = q[0]; rawn[g][1] = q[1]; rawn[g][2] = q[2];
+        }
+#pragma unroll
+        for (int g = 0; g < W; g++) {
+            valid[g] = base + 64u * g + c.lane < n5;
+            b[g] = (uint32_t)v8[g] & 0xFFu;
+            sym[g] = 0; adv[g] = 1; node[g] = 0; go[g] = valid[g];
+        }
+        // the groups' trie walks, level by level, until no lane of any group continues (a lane that has stopped reads edge 0 and ignores it)
+        for (uint32_t j = 1; j <= 8; j++) {
+            uint32_t e[W];
+#pragma unroll
+            for (int g = 0; g < W; g++) {
+                const uint32_t idx = ((uint32_t)v8[g] & 0xFFu) - 'a';
+                go[g] = go[g] && idx <= 25u;
+                e[g] = L->trie_next[go[g] ? node[g] * 26u + idx : 0u];
+                v8[g] >>= 8;
+            }
+            bool any = false;
+#pragma unroll
+            for (int g = 0; g < W; g++) {
+                const uint32_t nx = e[g] & 511u, f = e[g] >> 9;
+                go[g] = go[g] && nx != 0;
+                node[g] = go[g] ? nx : node[g];
+                const bool word = go[g] && f != 0;
+                sym[g] = word ? 0x81u + f : sym[g];
+                adv[g] = word ? j : adv[g];
+                any = any || go[g];
+            }
+            if (!__ballot(any)) break;
+        }
+#pragma unroll
+        for (int g = 0; g < W; g++) inc[g] = valid[g] ? (((adv[g] - 1u) & 3u) | 0x02010000u) : kFltIdent;      // beyond the run's positions: the identity
+        // inclusive scans, the groups side by side: inside the rows of 16, row 0 into row 1 and row 2 into row 3, rows 0-1 into rows 2-3
+        FLT_SCAN(0x111, 0xF); FLT_SCAN(0x112, 0xF); FLT_SCAN(0x114, 0xF); FLT_SCAN(0x118, 0xF);
+        FLT_SCAN(0x142, 0xA); FLT_SCAN(0x143, 0xC);
+        uint32_t s = s_in;                                   // distance to the next token start on entry to the group
+#pragma unroll
+        for (int g = 0; g < W; g++) {
+            const uint32_t prev = flt_dpp<0x138, 0xF>(inc[g]);                    // the function up to the position before this one (lane 0: the identity)
+            const uint32_t sb = (prev >> (8u * s)) & 3u;                          // distance to the next token start, before this position
+            const bool mine = valid[g] && sb == 0;
+            const uint64_t on = __ballot(mine);
+            const bool two = mine && sym[g] == 0 && b[g] >= 0x82;
+            const uint64_t m2 = __ballot(two);
+            const uint32_t off = dst_size + flt_mbcnt(on) + flt_mbcnt(m2);
+            gu8 *const a1 = mine ? dst + off : dump, *const a2 = two ? dst + off + 1 : dump;
+            *a1 = (uint8_t)(sym[g] ? sym[g] : two ? 254u : b[g]);
+            *a2 = (uint8_t)b[g];
+            dst_size += (uint32_t)__builtin_popcountll(on) + (uint32_t)__builtin_popcountll(m2);
+            s = (rdlane(inc[g], 63) >> (8u * s)) & 3u;                             // (positions beyond the run's are the identity: lane 63 holds the group's total)
+        }
+        s_in = s;
+    }
+    const uint32_t p = n5 + s_in;                           // where the chain leaves the walked range
     wave_fence();
     for (uint32_t i = p; i < size; i++) {   // last bytes: escape only (:319-326)
         uint32_t b = ldb(src + i);
@@ -141,21 +202,20 @@ DEV uint32_t flt_forward_dict(Sc &c, gu8 *src, uint32_t size)
     }
     if ((double)dst_size > (double)size * 0.82) return 0;   // :328
     wave_fence();
-    // the run is replaced, padded with blanks to its size (:332): 16 bytes a lane (src and the scratch are 16-byte aligned)
+    // the run is replaced, padded with blanks to its size (:332): 16 bytes a lane (src and the scratch are 16-byte aligned, and do not overlap)
     {
-        const uint32_t full = dst_size & ~15u, up = (size + 15u) & ~15u;
-        const gvec4 *s4 = (const gvec4 *)dst;
+        const uint32_t full = dst_size & ~15u;
         gvec4 *d4 = (gvec4 *)src;
         raw_vec4 blanks; blanks.x = blanks.y = blanks.z = blanks.w = 0x20202020u;
-        for (uint32_t t = c.lane * 16u; t < full; t += 1024u) d4[t >> 4] = s4[t >> 4];
+        lanes_copy16_far(d4, (const gvec4 *)dst, full >> 4);
         for (uint32_t t = full + c.lane; t < umin(full + 16u, size); t += 64) src[t] = t < dst_size ? dst[t] : (uint8_t)0x20;
         for (uint32_t t = full + 16u + c.lane * 16u; t + 16u <= size; t += 1024u) d4[t >> 4] = blanks;
         for (uint32_t t = umax16(full + 16u, size & ~15u) + c.lane; t < size; t += 64) src[t] = (uint8_t)0x20;
-        (void)up;
     }
     wave_fence();
     return 1;
 }
+#undef FLT_SCAN
 
 // ==========================================================================================
 // CSCEncoder::compress_block, csc_encoder_main.cpp:35-83.  Same order of effects as the

@@ -414,20 +414,18 @@ DEV void lz_encode_normal(Sc &c, const gu8 *src, uint32_t size, uint32_t lz_mode
     for (uint32_t i = 0; i < size;) {
         uint32_t cur = umin(c.wnd_size - c.wnd_curpos, size - i);
         cur = umin(cur, kMinBlock);
-        // memcpy(wnd_ + wnd_curpos_, src + i, cur): byte-granular, 64 lanes
+        // memcpy(wnd_ + wnd_curpos_, src + i, cur), 64 lanes
         {
-            gu8 *dst = c.wnd + c.wnd_curpos;
             const gu8 *s = src + i;
             TM_DECL;
-            lanes_copy8(dst, s, cur);
-            wave_fence();
             // stage the sub-block (+16 bytes of history, +48 of whatever the window holds after it:
             // hashes at the tail read those stale bytes, SURVEY App. C #4) in LDS
             c.stage_base = c.wnd_curpos;
             c.stage_end = c.wnd_curpos + cur + 40;
             uint32_t first = c.wnd_curpos >= 16 ? 0u : 16u - c.wnd_curpos;   // nothing before window position 0
             uint8_t *sb = (uint8_t *)c.L->stage;
-            lanes_stage(sb, c.wnd + c.wnd_curpos - 16, first, cur + 16 + 48);
+            lanes_copy_stage(c.wnd, s, sb, c.wnd_curpos, first, cur);      // (copy and stage in one: both take the sub-block from s)
+            wave_fence();
             TM_ADD(c, 9);
         }
         if (lz_mode == 5) {

@@ -27,8 +27,8 @@ st = St(); lib.lib.CSCMI_GetStats.argtypes = [C.c_void_p, C.c_void_p]; lib.lib.C
 lib.lib.CSCMI_DebugTimers.argtypes = [C.c_void_p, C.POINTER(C.c_uint64)]
 tm = (C.c_uint64 * 16)(); lib.lib.CSCMI_DebugTimers(h, tm)
 names = ["wait: slide acknowledged", "window function (DP nodes)", "exit: back-trace", "way out: packets into lanes", "literal flags (incl. the window-less literals)", "waiting for the tree wavefront (d6_join)", "exit: length, event, rebase", "way out: match / rep packets, exit packet",
-         "# deviations (undo + replay)", "# rep lengths by compare", "wait record (cyc/16)", "# record waits", "wait literal price (cyc/16)", "# literal waits", "# nodes on the straight-line path", "# waits for a re-based mask (id guard)"]
-tot = sum(tm[:8])
+         "dictionary filter (flt_forward_dict, in front of the parse)", "sub-block copy into the window + LDS stage","wait record (cyc/16)", "# record waits", "wait literal price (cyc/16)", "# literal waits", "# nodes on the straight-line path", "# waits for a re-based mask (id guard)"]
+tot = sum(tm[:10])      # sections 0-7 (the parse) + 8, 9 (the master wavefront's loops in front of it): the shares below are of all ten
 print(f"{len(data)/1e6/dt:.3f} MB/s, kernel {st.encode_kernel_ms:.0f} ms, nodes {st.find}, slid {st.slide}, lit {st.lit}, match {st.match}")
 for i, (n, v) in enumerate(zip(names, tm)):
     if not v: continue
