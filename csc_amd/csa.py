@@ -579,11 +579,39 @@ def _is_bytes_tensor(t) -> bool:
     return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.dim() == 1
 
 
-def _write_slices(base, entries, arcname, arc, flags, whole_default, opts):
-    """DeviceArchive.write_slices (base None) and DeviceArchive.update: the table, the two capacities, and the call --
-    CSAMI_DeviceWriteSlices, or CSAMI_DeviceUpdate over the base.
-    whole_default: an entry without "slice" is its whole tensor (else: no bytes)"""
+def _write_planned(files, arcname, arc, device, opts, call, plan=False):
+    """The one write call below write, write_tensors, write_slices and update: the table, the two capacities, the call and the stats
+    dict.  arc None: the archive tensor is allocated here on `device` with the plan's capacity, and once more with twice the room
+    on WRITE_ERROR (`plan`: the plan is made even with an arc).  call(table, n, (arcname, arc address, arc bytes), options, number
+    of planned tasks or None) makes the library call and returns (rc, [its statistics structs, the write's first]).
+    -> (rc, uint8 CUDA view of the archive, stats dict)"""
     import torch
+    o, nt, caps = options(**opts), None, [None]
+    if arc is None or plan:
+        rc, nt, _, raw = device_write_plan(files, arcname, **opts)
+        if rc != 0:
+            return rc, None, {"files": []}
+    if arc is None:
+        cap = 24 + raw + raw // 8 + (64 << 10) * (nt + 1) + (1 << 20)
+        caps = [cap, 2 * cap]
+    for cap in caps:
+        if cap is not None:
+            arc = torch.empty(cap, dtype=torch.uint8, device=device)
+        arr, keep = _write_table(files)
+        torch.cuda.synchronize()                   # the buffers were filled on torch's stream, the library launches on its own
+        rc, stats = call(arr, len(keep), (arcname.encode(), C.c_void_p(arc.data_ptr()) if arc.numel() else None, int(arc.numel())), o, nt)
+        if rc != WRITE_ERROR:
+            break
+    d = {}
+    for st in stats:
+        d.update(st.as_dict())
+    d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
+    return rc, (arc[:stats[0].archive_bytes] if rc == 0 else None), d
+
+
+def _write_slices(base, entries, arcname, arc, flags, whole_default, opts):
+    """DeviceArchive.write_slices (base None) and DeviceArchive.update: CSAMI_DeviceWriteSlices, or CSAMI_DeviceUpdate over the base.
+    whole_default: an entry without "slice" is its whole tensor (else: no bytes)"""
     files, table = [], (CSADevSlice * max(len(entries), 1))()
     for a, e in zip(table, entries):
         t = e["tensor"]
@@ -598,38 +626,20 @@ def _write_slices(base, entries, arcname, arc, flags, whole_default, opts):
     ptrs = (C.c_void_p * max(len(live), 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in live])
     sizes = (C.c_uint64 * max(len(live), 1))(*[0 if t is None else int(t.numel()) for t in live])
     device = arc.device if arc is not None else next((t.device for t in live if t is not None), "cuda")
-    o = options(**opts)
-    caps, nt = [None], None
-    if arc is None or base is not None:
-        rc, nt, _, raw = device_write_plan(files, arcname, **opts)
-        if rc != 0:
-            return rc, None, {"files": []}
-    if arc is None:
-        cap = 24 + raw + raw // 8 + (64 << 10) * (nt + 1) + (1 << 20)
-        caps = [cap, 2 * cap]
-    for cap in caps:
-        if cap is not None:
-            arc = torch.empty(cap, dtype=torch.uint8, device=device)
-        arr, keep = _write_table(files)
+    last = []
+
+    def call(arr, n, where, o, nt):
         st, gs, us = CSADevWriteStats(), CSADevGatherStats(), CSADevUpdateStats()
-        tasks = (CSADevUpdateTask * max(nt or 0, 1))()
-        torch.cuda.synchronize()                   # the buffers were filled on torch's stream, the library launches on its own
-        where = (arcname.encode(), C.c_void_p(arc.data_ptr()) if arc.numel() else None, int(arc.numel()))
         if base is None:
-            rc = lib().CSAMI_DeviceWriteSlices(ptrs, sizes, table, arr, len(keep), *where, C.byref(o), C.byref(st), C.byref(gs))
-        else:
-            rc = lib().CSAMI_DeviceUpdate(base._h, ptrs, sizes, table, arr, len(keep), *where, flags, C.byref(o), C.byref(st), C.byref(gs),
-                                          C.byref(us), tasks, nt)
-        if rc != WRITE_ERROR:
-            break
-    del live
-    d = st.as_dict()
-    d.update(gs.as_dict())
-    if base is not None:
-        d.update(us.as_dict())
-        d["tasks"] = [t.as_dict() for t in tasks[:min(nt, int(st.tasks))]]
-    d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
-    return rc, (arc[:st.archive_bytes] if rc == 0 else None), d
+            return lib().CSAMI_DeviceWriteSlices(ptrs, sizes, table, arr, n, *where, C.byref(o), C.byref(st), C.byref(gs)), [st, gs]
+        tasks = (CSADevUpdateTask * max(nt, 1))()
+        last[:] = [tasks, nt, st]
+        return lib().CSAMI_DeviceUpdate(base._h, ptrs, sizes, table, arr, n, *where, flags, C.byref(o), C.byref(st), C.byref(gs),
+                                        C.byref(us), tasks, nt), [st, gs, us]
+    rc, arc, d = _write_planned(files, arcname, arc, device, opts, call, plan=base is not None)
+    if last:
+        d["tasks"] = [t.as_dict() for t in last[0][:min(last[1], int(last[2].tasks))]]
+    return rc, arc, d
 
 
 class DeviceArchive:
@@ -643,8 +653,7 @@ class DeviceArchive:
     def open(cls, tensor) -> "DeviceArchive":
         """tensor: 1-d contiguous torch.uint8 CUDA tensor of any alignment.  Raises ValueError(rc) where CSAMI_DeviceOpen refuses it."""
         import torch
-        if not (isinstance(tensor, torch.Tensor) and tensor.dtype == torch.uint8 and tensor.is_cuda and tensor.is_contiguous()
-                and tensor.dim() == 1):
+        if not _is_bytes_tensor(tensor):
             raise TypeError("a contiguous 1-d torch.uint8 CUDA tensor")
         torch.cuda.synchronize()                       # the tensor was filled on torch's stream, the library launches on its own
         h = C.c_void_p()
@@ -695,7 +704,7 @@ class DeviceArchive:
         import torch
         if dst is None:
             dst = torch.empty(max(self._plan(names)[3], 1), dtype=torch.uint8, device=self._arc.device)
-        elif not (isinstance(dst, torch.Tensor) and dst.dtype == torch.uint8 and dst.is_cuda and dst.is_contiguous() and dst.dim() == 1):
+        elif not _is_bytes_tensor(dst):
             raise TypeError("dst: a contiguous 1-d torch.uint8 CUDA tensor")
         rc, files, st = self._read(names, dst, opts, stop_early)
         st["files"] = files
@@ -714,41 +723,20 @@ class DeviceArchive:
         esize, edate, eattr and offset are read); src: the 1-d contiguous torch.uint8 CUDA tensor they lie in, any alignment; arc: the
         tensor to write into (allocated here when None, and once more with twice the room on WRITE_ERROR).  stats["files"] is the
         table as returned: size = esize, nfrags = the fragments the entry got."""
-        import torch
-
-        def ok(t):
-            return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.dim() == 1
-        if not ok(src) or not (arc is None or ok(arc)):
+        if not _is_bytes_tensor(src) or not (arc is None or _is_bytes_tensor(arc)):
             raise TypeError("src, arc: contiguous 1-d torch.uint8 CUDA tensors")
-        o = options(**opts)
-        caps = [None]
-        if arc is None:
-            rc, nt, _, raw = device_write_plan(files, arcname, **opts)
-            if rc != 0:
-                return rc, None, {"files": []}
-            cap = 24 + raw + raw // 8 + (64 << 10) * (nt + 1) + (1 << 20)
-            caps = [cap, 2 * cap]
-        for cap in caps:
-            if cap is not None:
-                arc = torch.empty(cap, dtype=torch.uint8, device=src.device)
-            arr, keep = _write_table(files)
+
+        def call(arr, n, where, o, nt):
             st = CSADevWriteStats()
-            torch.cuda.synchronize()                   # src was filled on torch's stream, the library launches on its own
-            rc = lib().CSAMI_DeviceWrite(C.c_void_p(src.data_ptr()) if src.numel() else None, int(src.numel()), arr, len(keep),
-                                         arcname.encode(), C.c_void_p(arc.data_ptr()) if arc.numel() else None, int(arc.numel()),
-                                         C.byref(o), C.byref(st))
-            if rc != WRITE_ERROR:
-                break
-        d = st.as_dict()
-        d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
-        return rc, (arc[:st.archive_bytes] if rc == 0 else None), d
+            return lib().CSAMI_DeviceWrite(C.c_void_p(src.data_ptr()) if src.numel() else None, int(src.numel()), arr, n, *where,
+                                           C.byref(o), C.byref(st)), [st]
+        return _write_planned(files, arcname, arc, src.device, opts, call)
 
     @staticmethod
     def write_tensors(entries, arcname: str = "out.csa", arc=None, **opts):
         """`csarc a -t1` of entries that lie in tensors of their own (CSAMI_DeviceWriteFrom) -> (rc, uint8 CUDA view of the archive,
         stats dict), as write.  entries: dicts with name, tensor, edate, eattr; tensor: a 1-d contiguous torch.uint8 CUDA tensor of any
         alignment, its numel the entry's size, or None for directories and empty files.  The tensors may alias each other, not arc."""
-        import torch
         files = []
         for e in entries:
             t = e["tensor"]
@@ -760,28 +748,11 @@ class DeviceArchive:
         live = [e["tensor"] for e in entries]                      # alive across the call
         ptrs = (C.c_void_p * max(len(live), 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in live])
         device = arc.device if arc is not None else next((t.device for t in live if t is not None), "cuda")
-        o = options(**opts)
-        caps = [None]
-        if arc is None:
-            rc, nt, _, raw = device_write_plan(files, arcname, **opts)
-            if rc != 0:
-                return rc, None, {"files": []}
-            cap = 24 + raw + raw // 8 + (64 << 10) * (nt + 1) + (1 << 20)
-            caps = [cap, 2 * cap]
-        for cap in caps:
-            if cap is not None:
-                arc = torch.empty(cap, dtype=torch.uint8, device=device)
-            arr, keep = _write_table(files)
+
+        def call(arr, n, where, o, nt):
             st = CSADevWriteStats()
-            torch.cuda.synchronize()                   # the tensors were filled on torch's stream, the library launches on its own
-            rc = lib().CSAMI_DeviceWriteFrom(ptrs, arr, len(keep), arcname.encode(), C.c_void_p(arc.data_ptr()) if arc.numel() else None,
-                                             int(arc.numel()), C.byref(o), C.byref(st))
-            if rc != WRITE_ERROR:
-                break
-        del live
-        d = st.as_dict()
-        d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
-        return rc, (arc[:st.archive_bytes] if rc == 0 else None), d
+            return lib().CSAMI_DeviceWriteFrom(ptrs, arr, n, *where, C.byref(o), C.byref(st)), [st]
+        return _write_planned(files, arcname, arc, device, opts, call)
 
     @staticmethod
     def write_slices(entries, arcname: str = "out.csa", arc=None, **opts):
@@ -803,39 +774,74 @@ class DeviceArchive:
         different contents can pass.  arc must not overlap this archive's tensor."""
         return _write_slices(self, entries, arcname, arc, CSAMI_UPDATE_TRUST_SUMS if trust_sums else 0, True, opts)
 
-    def _by_name(self, bufs, names):
-        """the selection's files table and, per entry of it, the caller's tensor (None: verified only).  KeyError for a key that is
-        no selected entry."""
+    def _by(self, bufs, names, take):
+        """the selection's files table and, per entry of it, the caller's base buffer, its address and size, and the slice of it (None,
+        count 0: verified only).  take(b) -> (base tensor, slice or None: none is set) for a value of bufs that is not None.
+        KeyError for a key that is no selected entry."""
         files = self.plan(names)[0]
         bufs = dict(bufs)
         unknown = set(bufs) - {f["name"] for f in files}
         if unknown:
             raise KeyError(sorted(unknown)[0])
-        live = [bufs.get(f["name"]) for f in files]
-        if not all(t is None or _is_bytes_tensor(t) for t in live):
-            raise TypeError("a contiguous 1-d torch.uint8 CUDA tensor, or None")
+        live, table = [], (CSADevSlice * max(len(files), 1))()
+        for a, f in zip(table, files):
+            b = bufs.get(f["name"])
+            if b is not None:
+                b, s = take(b)
+                if s is not None:
+                    a.offset, a.run, a.stride, a.count = (s[0], s[1], s[1], 1 if s[1] else 0) if len(s) == 2 else s
+            live.append(b)
         # (an empty tensor may have no address: it stands for itself with the archive's, which a range of size 0 never overlaps)
         ptrs = (C.c_void_p * max(len(live), 1))(*[None if t is None else (t.data_ptr() or self._arc.data_ptr()) for t in live])
         sizes = (C.c_uint64 * max(len(live), 1))(*[0 if t is None else int(t.numel()) for t in live])
-        return files, live, ptrs, sizes
+        return files, live, ptrs, sizes, table
+
+    def _by_name(self, bufs, names):
+        """the selection's files table and, per entry of it, the caller's tensor (None: verified only).  KeyError for a key that is
+        no selected entry."""
+        def take(t):
+            if not _is_bytes_tensor(t):
+                raise TypeError("a contiguous 1-d torch.uint8 CUDA tensor, or None")
+            return t, None
+        return self._by(bufs, names, take)[:4]
+
+    def _by_slice(self, bufs, names):
+        """the selection's files table and, per entry of it, the caller's base buffer and the slice of it (None, count 0: verified
+        only).  bufs: {stored name: (1-d contiguous torch.uint8 CUDA base tensor, (offset, length) | (offset, run, stride, count)) |
+        any CUDA tensor tensor_slice takes | None}.  KeyError for a key that is no selected entry."""
+        import torch
+
+        def take(b):
+            t, s = tensor_slice(b) if isinstance(b, torch.Tensor) else b
+            if not _is_bytes_tensor(t):
+                raise TypeError("a CUDA tensor, or (a contiguous 1-d torch.uint8 CUDA tensor, slice), or None")
+            return t, s
+        return self._by(bufs, names, take)
+
+    def _call(self, fn, names, files, args, stop_early, opts, extra=(), compare=False):
+        """One read call over buffers of the caller's: fn(handle, names, *args, number of entries, flags, options, files table[, diffs],
+        read statistics, stop statistics, *extra) -> (rc, stats dict with `extra`'s merged in and the files table, {name: diff} or None)"""
+        import torch
+        arr, n = _names(names)
+        table, st, ss, o = (CSADevFile * max(len(files), 1))(), CSADevReadStats(), CSADevStopStats(), options(**opts)
+        diffs = (CSADevDiff * max(len(files), 1))() if compare else None
+        torch.cuda.synchronize()
+        rc = fn(self._h, arr, n, *args, len(files), CSAMI_DEV_STOP_EARLY if stop_early else 0, C.byref(o), table,
+                *([diffs] if compare else []), C.byref(st), C.byref(ss), *[C.byref(x) for x in extra])
+        out = st.as_dict()
+        if stop_early:
+            out.update(ss.as_dict())
+        for x in extra:
+            out.update(x.as_dict())
+        out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(table, files)]
+        return rc, out, ({f["name"]: d.as_dict() for f, d in zip(files, diffs)} if compare else None)
 
     def extract_into(self, dsts, names: Sequence[str] = (), stop_early=False, **opts):
         """`csarc x` into tensors of the caller's (CSAMI_DeviceReadInto) -> (rc, stats dict); stats["files"] as in extract.
         dsts: {stored name: 1-d contiguous torch.uint8 CUDA tensor of at least the entry's size, or None}; a selected entry that is
         absent or None is verified only.  The tensors must not overlap each other or the archive."""
-        import torch
         files, live, ptrs, caps = self._by_name(dsts, names)
-        arr, n = _names(names)
-        table, st, ss, o = (CSADevFile * max(len(files), 1))(), CSADevReadStats(), CSADevStopStats(), options(**opts)
-        torch.cuda.synchronize()
-        rc = lib().CSAMI_DeviceReadInto(self._h, arr, n, ptrs, caps, len(files), CSAMI_DEV_STOP_EARLY if stop_early else 0, C.byref(o),
-                                        table, C.byref(st), C.byref(ss))
-        del live
-        out = st.as_dict()
-        if stop_early:
-            out.update(ss.as_dict())
-        out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(table, files)]
-        return rc, out
+        return self._call(lib().CSAMI_DeviceReadInto, names, files, (ptrs, caps), stop_early, opts)[:2]
 
     def extract_slices(self, slices, dsts=None, names: Sequence[str] = (), stop_early=True, **opts):
         """byte ranges and strided slices of entries (CSAMI_DeviceReadSlices) -> (rc, {name: uint8 CUDA tensor of the packed slice},
@@ -851,16 +857,7 @@ class DeviceArchive:
             if f["name"] not in given and s.count:
                 given[f["name"]] = torch.empty(s.run * s.count, dtype=torch.uint8, device=self._arc.device)
         files, live, ptrs, caps = self._by_name(given, names)
-        arr, n = _names(names)
-        ftab, st, ss, sl, o = (CSADevFile * max(len(files), 1))(), CSADevReadStats(), CSADevStopStats(), CSADevSliceStats(), options(**opts)
-        torch.cuda.synchronize()
-        rc = lib().CSAMI_DeviceReadSlices(self._h, arr, n, table, ptrs, caps, len(files), CSAMI_DEV_STOP_EARLY if stop_early else 0, C.byref(o),
-                                          ftab, C.byref(st), C.byref(ss), C.byref(sl))
-        out = st.as_dict()
-        if stop_early:
-            out.update(ss.as_dict())
-        out.update(sl.as_dict())
-        out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(ftab, files)]
+        rc, out, _ = self._call(lib().CSAMI_DeviceReadSlices, names, files, (table, ptrs, caps), stop_early, opts, (CSADevSliceStats(),))
         got = {f["name"]: t[:s.run * s.count] for f, t, s in zip(files, live, table) if t is not None and s.count and rc != WRITE_ERROR}
         return rc, got, out
 
@@ -869,46 +866,9 @@ class DeviceArchive:
         (rc, {name: {"status", "first_diff", "failed_frags"}}, stats dict).  srcs: as dsts of extract_into; the tensors are only read
         and may alias each other.  status: 0 or a sum of CSA_DIFF_*; first_diff: NO_DIFF without CSA_DIFF_BYTES.  rc is the
         archive's health, as test returns it."""
-        import torch
         files, live, ptrs, sizes = self._by_name(srcs, names)
-        arr, n = _names(names)
-        table, st, ss, o = (CSADevFile * max(len(files), 1))(), CSADevReadStats(), CSADevStopStats(), options(**opts)
-        diffs = (CSADevDiff * max(len(files), 1))()
-        torch.cuda.synchronize()
-        rc = lib().CSAMI_DeviceCompare(self._h, arr, n, ptrs, sizes, len(files), CSAMI_DEV_STOP_EARLY if stop_early else 0, C.byref(o),
-                                       table, diffs, C.byref(st), C.byref(ss))
-        del live
-        out = st.as_dict()
-        if stop_early:
-            out.update(ss.as_dict())
-        out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(table, files)]
-        return rc, {f["name"]: d.as_dict() for f, d in zip(files, diffs)}, out
-
-    def _by_slice(self, bufs, names):
-        """the selection's files table and, per entry of it, the caller's base buffer and the slice of it (None, count 0: verified
-        only).  bufs: {stored name: (1-d contiguous torch.uint8 CUDA base tensor, (offset, length) | (offset, run, stride, count)) |
-        any CUDA tensor tensor_slice takes | None}.  KeyError for a key that is no selected entry."""
-        import torch
-        files = self.plan(names)[0]
-        bufs = dict(bufs)
-        unknown = set(bufs) - {f["name"] for f in files}
-        if unknown:
-            raise KeyError(sorted(unknown)[0])
-        live, table = [], (CSADevSlice * max(len(files), 1))()
-        for a, f in zip(table, files):
-            b = bufs.get(f["name"])
-            if isinstance(b, torch.Tensor):
-                b = tensor_slice(b)
-            if b is not None:
-                t, s = b
-                if not _is_bytes_tensor(t):
-                    raise TypeError("a CUDA tensor, or (a contiguous 1-d torch.uint8 CUDA tensor, slice), or None")
-                a.offset, a.run, a.stride, a.count = (s[0], s[1], s[1], 1 if s[1] else 0) if len(s) == 2 else s
-                b = t
-            live.append(b)
-        ptrs = (C.c_void_p * max(len(live), 1))(*[None if t is None else (t.data_ptr() or self._arc.data_ptr()) for t in live])
-        sizes = (C.c_uint64 * max(len(live), 1))(*[0 if t is None else int(t.numel()) for t in live])
-        return files, live, ptrs, sizes, table
+        rc, out, diffs = self._call(lib().CSAMI_DeviceCompare, names, files, (ptrs, sizes), stop_early, opts, compare=True)
+        return rc, diffs, out
 
     def extract_into_slices(self, dsts, names: Sequence[str] = (), stop_early=False, **opts):
         """`csarc x` into strided slices of buffers of the caller's (CSAMI_DeviceReadIntoSlices), the way back of write_slices ->
@@ -917,41 +877,18 @@ class DeviceArchive:
         as t2d[:, c0:c1] | None}; a selected entry that is absent or None is verified only.  The entry's packed bytes go to the bytes
         the slice selects, which must be at least the entry's size; nothing else of the buffer is stored to.  The selections must not
         meet each other -- their hulls may interleave, as the column blocks of one matrix do -- and no hull may overlap the archive."""
-        import torch
         files, live, ptrs, sizes, slices = self._by_slice(dsts, names)
-        arr, n = _names(names)
-        table, st, ss, sp, o = (CSADevFile * max(len(files), 1))(), CSADevReadStats(), CSADevStopStats(), CSADevSpreadStats(), options(**opts)
-        torch.cuda.synchronize()
-        rc = lib().CSAMI_DeviceReadIntoSlices(self._h, arr, n, ptrs, sizes, slices, len(files), CSAMI_DEV_STOP_EARLY if stop_early else 0,
-                                              C.byref(o), table, C.byref(st), C.byref(ss), C.byref(sp))
-        del live
-        out = st.as_dict()
-        if stop_early:
-            out.update(ss.as_dict())
-        out.update(sp.as_dict())
-        out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(table, files)]
-        return rc, out
+        return self._call(lib().CSAMI_DeviceReadIntoSlices, names, files, (ptrs, sizes, slices), stop_early, opts, (CSADevSpreadStats(),))[:2]
 
     def compare_slices(self, srcs, names: Sequence[str] = (), stop_early=False, **opts):
         """compare against strided slices of buffers of the caller's (CSAMI_DeviceCompareSlices) -> (rc, diffs, stats dict), shaped as
         compare returns them, with the spread statistics beside the read's.  srcs: as dsts of extract_into_slices; the buffers are only
         read and may alias each other.  CSA_DIFF_SIZE: the slice does not select exactly the entry's size; first_diff is a packed
         offset in the entry."""
-        import torch
         files, live, ptrs, sizes, slices = self._by_slice(srcs, names)
-        arr, n = _names(names)
-        table, st, ss, sp, o = (CSADevFile * max(len(files), 1))(), CSADevReadStats(), CSADevStopStats(), CSADevSpreadStats(), options(**opts)
-        diffs = (CSADevDiff * max(len(files), 1))()
-        torch.cuda.synchronize()
-        rc = lib().CSAMI_DeviceCompareSlices(self._h, arr, n, ptrs, sizes, slices, len(files), CSAMI_DEV_STOP_EARLY if stop_early else 0,
-                                             C.byref(o), table, diffs, C.byref(st), C.byref(ss), C.byref(sp))
-        del live
-        out = st.as_dict()
-        if stop_early:
-            out.update(ss.as_dict())
-        out.update(sp.as_dict())
-        out["files"] = [_file_dict(f, C.string_at(f.name).decode("latin-1")) if f.name else g for f, g in zip(table, files)]
-        return rc, {f["name"]: d.as_dict() for f, d in zip(files, diffs)}, out
+        rc, out, diffs = self._call(lib().CSAMI_DeviceCompareSlices, names, files, (ptrs, sizes, slices), stop_early, opts,
+                                    (CSADevSpreadStats(),), compare=True)
+        return rc, diffs, out
 
     def kernel_ms(self):
         """HIP-event milliseconds of the last extract / test by kernel: (k_gather_extents, k_frag_pieces, k_frag_fold); after compare:

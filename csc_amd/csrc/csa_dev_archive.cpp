@@ -10,6 +10,7 @@
 #include <list>
 #include <map>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "csa_internal.h"
@@ -43,6 +44,15 @@ struct CSADevArchive {
 namespace {
 
 bool add_ok(uint64_t a, uint64_t b, uint64_t *out) { return !__builtin_add_overflow(a, b, out); }
+
+csadev::Slice dev_slice(const CSADevSlice &s) { return csadev::Slice{s.offset, s.run, s.stride, s.count}; }
+
+// "every byte of a buffer of n bytes": one run of n, nothing where n == 0
+csadev::Slice whole_slice(uint64_t n) { return n ? csadev::Slice{0, n, n, 1} : csadev::Slice{0, 0, 0, 0}; }
+
+// what a task of `raw` bytes' decoder holds: the dictionary (bounded by the raw size and by 1 GiB) and ~24 MiB of rings and buffers,
+// as read_archive reckons
+uint64_t decoder_need(uint64_t raw) { return std::min<uint64_t>(std::max<uint64_t>(raw, 1u << 20), 1ull << 30) + (24ull << 20); }
 
 struct DevFilePlan { Index::const_iterator it; uint64_t offset, size; };
 struct DevFrag { uint32_t file; uint32_t checksum; uint64_t posblock, size, posfile; };
@@ -89,7 +99,7 @@ bool dev_layout(const Index &index, const std::map<uint64_t, uint64_t> &raw, con
         csadev::Slice sl = {0, 0, 0, 0};
         if (L.sliced) {
             if (fi >= nslices) return false;
-            sl = csadev::Slice{slices[fi].offset, slices[fi].run, slices[fi].stride, slices[fi].count};
+            sl = dev_slice(slices[fi]);
             uint64_t bytes;
             if (!csadev::slice_check(sl, size, &bytes)) return false;
             L.slices.push_back(sl);
@@ -186,148 +196,276 @@ struct DevTimer {                              // HIP-event time of this layer's
     }
 };
 
-// The tables of k_frag_pieces and k_frag_fold for the fragments of a wave, and their device copies.  The callers launch
-// k_frag_pieces themselves, over d_pieces and d_sums: once per wave (read), or stored and summed pieces apart (write).
+// Where a launch is accounted: the HIP-event time of a piece pass and of a fold, and the caller's launch counter.
+struct LaunchSlot { DevTimer &tm; double *ms, *ms_fold; uint64_t &launches; };
+
+// The piece and fold tables for the fragments of a wave, their device copies and their launches.  A table holds one kind of leading
+// pieces -- kSliced: SlicePieces (add_sliced); kSpread: SpreadPieces (add_spread); kGathered: GatherPieces (add_gathered), with
+// pieces that are only summed behind them (add_summed) -- and runs itself: sum() the store / sum pass and k_frag_fold, compare()
+// the compare pass and k_frag_fold_diff.  A table none of whose pieces is periodic goes through k_frag_pieces / k_frag_compare as the
+// CopyPieces its pieces then are.  This is where a new kind of piece plugs in: a vector, an add_*, a line in lead() and in sum() or compare().
 struct FragTables {
-    std::vector<csadev::CopyPiece> pieces;
+    enum Kind { kSliced, kSpread, kGathered };
+    explicit FragTables(Kind k) : kind(k) {}
     std::vector<csadev::FragFold> frags;
-    DevBuf d_pieces, d_frags, d_sums, d_res, d_firsts;
-    // a fragment of `size` > 0 bytes at src, copied to dst unless that is NULL; false: more pieces than a launch takes.
-    // With `cmp` (k_frag_compare) dst is the caller's range instead, and the fragment's first cmp <= size bytes are compared with it.
-    bool add(const uint8_t *src, uint8_t *dst, uint64_t size, uint32_t checksum, uint64_t cmp = 0)
-    {
-        using namespace csadev;
-        const uint64_t np = piece_count(size, kFragPiece);
-        if (gpieces.size() + pieces.size() + np > 0x7FFFFFFFull) return false;
-        frags.push_back(FragFold{size, (uint32_t)(gpieces.size() + pieces.size()), (uint32_t)np, checksum, 0});
-        piece_split(src, dst, size, kFragPiece, [&](uint64_t k, CopyPiece p) {
-            const uint64_t off = k * kFragPiece;
-            p.cmp = (uint32_t)(cmp > off ? std::min<uint64_t>(cmp - off, p.len) : 0);
-            pieces.push_back(p);
-        });
-        return true;
-    }
-    // CSAMI_DeviceReadSlices, in the place of add() and `pieces`: the fragment lies at [posfile, posfile + size) of an entry under the
-    // (checked) slice sl, and dst is the entry's packed destination, or NULL.  Each 16 KiB cell is classified (slice_reduce).
-    std::vector<csadev::SlicePiece> spieces;
+    size_t summed() const { return pieces.size(); }        // the pieces add_summed made
+
+    // CSAMI_DeviceReadSlices: the fragment of `size` > 0 bytes at src lies at [posfile, posfile + size) of an entry under the (checked)
+    // slice sl, and dst is the entry's packed destination, or NULL.  Each 16 KiB cell is classified (slice_reduce).
+    // false (here and below): more pieces than a launch takes.
     bool add_sliced(const uint8_t *src, uint8_t *dst, const csadev::Slice &sl, uint64_t posfile, uint64_t size, uint32_t checksum,
                     CSADevSliceStats &SL)
     {
         using namespace csadev;
-        const uint64_t np = piece_count(size, kFragPiece);
-        if (spieces.size() + np > 0x7FFFFFFFull) return false;
-        frags.push_back(FragFold{size, (uint32_t)spieces.size(), (uint32_t)np, checksum, 0});
+        if (!add_frag(spieces.size(), size, checksum)) return false;
         piece_split(src, nullptr, size, kFragPiece, [&](uint64_t k, const CopyPiece &p) {
             SlicePiece sp = {p.src, nullptr, p.len, 0, 0, 0, 0, 0};
             SliceCut c;
-            const SliceKind kind = dst ? slice_reduce(sl, posfile + k * kFragPiece, p.len, c) : kSliceNone;
-            if (kind != kSliceNone) sp.dst = (uint8_t *)((uintptr_t)dst + c.dst);
-            if (kind == kSlicePeriodic) { sp.lo = c.lo; sp.hi = c.hi; sp.phase = c.phase; sp.run = c.run; sp.stride = c.stride; }
-            (kind == kSlicePeriodic ? SL.periodic_pieces : SL.plain_pieces)++;
+            const SliceKind kd = dst ? slice_reduce(sl, posfile + k * kFragPiece, p.len, c) : kSliceNone;
+            if (kd != kSliceNone) sp.dst = (uint8_t *)((uintptr_t)dst + c.dst);
+            if (kd == kSlicePeriodic) { sp.lo = c.lo; sp.hi = c.hi; sp.phase = c.phase; sp.run = c.run; sp.stride = c.stride; }
+            (kd == kSlicePeriodic ? SL.periodic_pieces : SL.plain_pieces)++;
             spieces.push_back(sp);
         });
         return true;
     }
-    // CSAMI_DeviceWriteSlices, in front of `pieces`: a fragment of `size` > 0 bytes that is the packed bytes [at, at + size) of the
-    // (checked) slice sl of the buffer `buf`, gathered to dst.  Each 16 KiB cell of the packed fragment is classified (gather_reduce).
-    // Its pieces and their sums come first: add() counts from behind them.  dst == NULL (CSAMI_DeviceUpdate's check under
-    // CSAMI_UPDATE_TRUST_SUMS): the fragment is summed where it lies and folded against `checksum`.
-    std::vector<csadev::GatherPiece> gpieces;
-    DevBuf d_gpieces;
+    // CSAMI_DeviceWriteSlices: a fragment of `size` > 0 bytes that is the packed bytes [at, at + size) of the (checked) slice sl of the
+    // buffer `buf`, gathered to dst.  Its pieces and their sums come first: add_summed counts from behind them.  dst == NULL
+    // (CSAMI_DeviceUpdate's check under CSAMI_UPDATE_TRUST_SUMS): the fragment is summed where it lies and folded against `checksum`.
     bool add_gathered(const uint8_t *buf, uint8_t *dst, const csadev::Slice &sl, uint64_t at, uint64_t size, CSADevGatherStats &G,
                       uint32_t checksum = 0)
     {
+        stores = stores || dst;
+        return pieces.empty() && add_rows(gpieces, buf, sl, at, size, size, checksum, G.plain_pieces, G.periodic_pieces,
+                                          [&](uint64_t off, uint32_t len, uint32_t, const uint8_t *side) {
+            return csadev::GatherPiece{side, dst ? dst + off : nullptr, 0, len, 0, 0, 0, nullptr, nullptr};
+        });
+    }
+    // behind the gathered fragments: a fragment of `size` > 0 bytes that is summed where it lies, at src
+    bool add_summed(const uint8_t *src, uint64_t size)
+    {
         using namespace csadev;
-        const uint64_t np = piece_count(size, kFragPiece);
-        if (!pieces.empty() || gpieces.size() + np > 0x7FFFFFFFull) return false;
-        frags.push_back(FragFold{size, (uint32_t)gpieces.size(), (uint32_t)np, checksum, 0});
-        const uint8_t *lo = buf + sl.offset, *hi = lo + (sl.count - 1) * sl.stride + sl.run;
-        for (uint64_t off = 0; off < size; off += kFragPiece) {
-            GatherCut c;
-            const uint32_t len = (uint32_t)std::min<uint64_t>(size - off, kFragPiece);
-            const bool whole = gather_reduce(sl, at + off, len, c);
-            (whole ? G.plain_pieces : G.periodic_pieces)++;
-            uint8_t *d = dst ? dst + off : nullptr;
-            gpieces.push_back(whole ? GatherPiece{buf + c.src, d, 0, len, 0, 0, 0, nullptr, nullptr}
-                                    : GatherPiece{buf + c.src, d, c.stride, len, c.phase, c.run, 0, lo, hi});
-        }
+        if (!add_frag(gpieces.size() + pieces.size(), size, 0)) return false;
+        piece_split(src, nullptr, size, kFragPiece, [&](uint64_t, const CopyPiece &p) { pieces.push_back(p); });
         return true;
     }
-    // no piece of `gpieces` is periodic: they become the CopyPieces they are, for k_frag_pieces<true>
-    void gathered_as_plain()
-    {
-        for (const csadev::GatherPiece &g : gpieces) pieces.push_back(csadev::CopyPiece{g.src, g.dst, g.len, 0});
-        gpieces.clear();
-    }
-    // The read paths over the caller's buffers, in the place of add() and `pieces`: the fragment's delivered bytes are the packed
-    // bytes [posfile, posfile + size) of its entry, whose side in the caller's buffer `buf` (NULL: none) is what the (checked) slice sl
-    // selects of it.  The leading `use` <= size bytes have that side -- all of them where they are stored, the compared ones with
-    // `compare` -- and the rest is summed only.  Each 16 KiB cell is planned as the write plans it (gather_reduce).
-    std::vector<csadev::SpreadPiece> xpieces;
-    uint64_t xperiodic = 0;
+    // The read paths over the caller's buffers: the fragment's delivered bytes, at src, are the packed bytes [posfile, posfile + size)
+    // of its entry, whose side in the caller's buffer `buf` (NULL: none) is what the (checked) slice sl selects of it.  The leading
+    // `use` <= size bytes have that side -- all of them where they are stored, the compared ones with `compare` -- and the rest is
+    // summed only.
     bool add_spread(const uint8_t *src, uint8_t *buf, const csadev::Slice &sl, uint64_t posfile, uint64_t size, uint32_t checksum,
                     uint64_t use, bool compare, CSADevSpreadStats &X)
     {
+        stores = stores || buf;
+        return add_rows(xpieces, buf, sl, posfile, size, buf ? use : 0, checksum, X.plain_pieces, X.periodic_pieces,
+                        [&](uint64_t off, uint32_t len, uint32_t u, const uint8_t *side) {
+            return csadev::SpreadPiece{src + off, (uint8_t *)side, 0, len, 0, 0, compare ? u : 0, nullptr, nullptr};
+        });
+    }
+
+    // The store / sum pass over the leading pieces (`always`: even where there is none -- a read wave and a check wave are always the
+    // same three launches), the sum pass over the pieces behind them where there are any, and the fold: res[i] is fragment i's.
+    // *uploaded (NULL: not counted) gets the bytes of the tables.
+    bool sum(const LaunchSlot &at, bool always, uint64_t *uploaded, std::vector<csadev::FragResult> &res)
+    {
         using namespace csadev;
-        const uint64_t np = piece_count(size, kFragPiece);
-        if (xpieces.size() + np > 0x7FFFFFFFull) return false;
-        frags.push_back(FragFold{size, (uint32_t)xpieces.size(), (uint32_t)np, checksum, 0});
-        if (!buf) use = 0;
+        const uint32_t nlead = (uint32_t)lead().n, nsum = (uint32_t)pieces.size();
+        const bool rows = plan_rows();
+        if (!upload<FragResult>(rows, uploaded)) return false;
+        if ((always || nlead) && !at.tm.timed(at.ms, at.launches, [&] {
+                if (kind == kSliced) launch_frag_slices(d_lead.p, d_sums.p, nlead, at.tm.st);
+                else if (!rows) launch_frag_pieces(d_pieces.p, d_sums.p, nlead, stores, at.tm.st);
+                else if (kind == kSpread) launch_frag_spread(d_lead.p, d_sums.p, nlead, at.tm.st);
+                else launch_frag_rows(d_lead.p, d_sums.p, nlead, at.tm.st); })) return false;
+        // (the summed pieces lie behind the leading ones in d_pieces where those became CopyPieces, else at its front)
+        if (nsum && !at.tm.timed(at.ms, at.launches, [&] {
+                launch_frag_pieces((const CopyPiece *)d_pieces.p + (rows ? 0 : nlead), (PieceSums *)d_sums.p + nlead, nsum, false, at.tm.st); }))
+            return false;
+        return fold(at, res);
+    }
+    // The compare pass over a kSpread table -- each piece's leading cmp bytes against the caller's -- and the fold: res[i].first is the
+    // first differing offset in fragment i, its size if there is none.
+    bool compare(const LaunchSlot &at, uint64_t *uploaded, std::vector<csadev::FragDiff> &res)
+    {
+        const uint32_t n = (uint32_t)xpieces.size();
+        const bool rows = plan_rows();
+        if (!upload<csadev::FragDiff>(rows, uploaded)) return false;
+        if (!at.tm.timed(at.ms, at.launches, [&] {
+                if (rows) launch_frag_compare_rows(d_lead.p, d_sums.p, d_firsts.p, n, at.tm.st);
+                else launch_frag_compare(d_pieces.p, d_sums.p, d_firsts.p, n, at.tm.st); })) return false;
+        return fold(at, res);
+    }
+
+private:
+    const Kind kind;
+    std::vector<csadev::SlicePiece> spieces;
+    std::vector<csadev::GatherPiece> gpieces;
+    std::vector<csadev::SpreadPiece> xpieces;
+    std::vector<csadev::CopyPiece> pieces;
+    uint64_t periodic = 0;                     // leading pieces that cross a run border
+    bool stores = false;                       // a leading piece has a side it is stored to
+    DevBuf d_lead, d_pieces, d_frags, d_sums, d_res, d_firsts;
+    struct Lead { const void *p; size_t n, bytes; };
+    Lead lead() const
+    {
+        return kind == kSliced   ? Lead{spieces.data(), spieces.size(), spieces.size() * sizeof(csadev::SlicePiece)}
+               : kind == kSpread ? Lead{xpieces.data(), xpieces.size(), xpieces.size() * sizeof(csadev::SpreadPiece)}
+                                 : Lead{gpieces.data(), gpieces.size(), gpieces.size() * sizeof(csadev::GatherPiece)};
+    }
+    bool add_frag(size_t first, uint64_t size, uint32_t checksum)
+    {
+        const uint64_t np = csadev::piece_count(size, csadev::kFragPiece);
+        if (first + np > 0x7FFFFFFFull) return false;
+        frags.push_back(csadev::FragFold{size, (uint32_t)first, (uint32_t)np, checksum, 0});
+        return true;
+    }
+    // The row planner of add_gathered and add_spread: the fragment is the packed bytes [at, at + size) of the slice sl of `buf`, and
+    // the leading `use` bytes of it have that side.  Each 16 KiB cell is planned by gather_reduce: make(off, len, u, side) gives the
+    // piece of the cell at `off` whose leading u bytes have the one contiguous side `side` (NULL where u == 0); a cell that crosses a
+    // run border gets its period and the slice's hull on top, and counts as periodic.
+    template <class Piece, class Make>
+    bool add_rows(std::vector<Piece> &out, const uint8_t *buf, const csadev::Slice &sl, uint64_t at, uint64_t size, uint64_t use, uint32_t checksum,
+                  uint64_t &n_plain, uint64_t &n_periodic, Make make)
+    {
+        using namespace csadev;
+        if (!add_frag(out.size(), size, checksum)) return false;
         const uint8_t *lo = use ? buf + sl.offset : nullptr, *hi = use ? lo + (sl.count - 1) * sl.stride + sl.run : nullptr;
         for (uint64_t off = 0; off < size; off += kFragPiece) {
             const uint32_t len = (uint32_t)std::min<uint64_t>(size - off, kFragPiece);
             const uint32_t u = (uint32_t)(use > off ? std::min<uint64_t>(use - off, len) : 0);
-            SpreadPiece sp = {src + off, nullptr, 0, len, 0, 0, 0, nullptr, nullptr};
-            if (u) {
-                GatherCut c;
-                const bool whole = gather_reduce(sl, posfile + off, u, c);
-                sp.dst = buf + c.src;
-                sp.cmp = compare ? u : 0;
-                if (!whole) { sp.stride = c.stride; sp.phase = c.phase; sp.run = c.run; sp.lo = lo; sp.hi = hi; xperiodic++; }
-            }
-            (sp.stride ? X.periodic_pieces : X.plain_pieces)++;
-            xpieces.push_back(sp);
+            GatherCut c = {0, 0, 0, 0};
+            const bool whole = !u || gather_reduce(sl, at + off, u, c);
+            Piece p = make(off, len, u, u ? buf + c.src : nullptr);
+            if (!whole) { p.stride = c.stride; p.phase = c.phase; p.run = c.run; p.lo = lo; p.hi = hi; periodic++; }
+            (whole ? n_plain : n_periodic)++;
+            out.push_back(p);
         }
         return true;
     }
-    // no piece of `xpieces` is periodic: they become the CopyPieces they are, for k_frag_pieces / k_frag_compare
-    void spread_as_plain()
+    static uint32_t cmp_of(const csadev::GatherPiece &) { return 0; }
+    static uint32_t cmp_of(const csadev::SpreadPiece &x) { return x.cmp; }
+    template <class Piece> void as_plain(std::vector<Piece> &rows)
     {
-        pieces.reserve(xpieces.size());
-        for (const csadev::SpreadPiece &x : xpieces) pieces.push_back(csadev::CopyPiece{x.src, x.dst, x.len, x.cmp});
-        xpieces.clear();
+        std::vector<csadev::CopyPiece> front;
+        front.reserve(rows.size() + pieces.size());
+        for (const Piece &r : rows) front.push_back(csadev::CopyPiece{r.src, r.dst, r.len, cmp_of(r)});
+        front.insert(front.end(), pieces.begin(), pieces.end());
+        pieces.swap(front);
+        rows.clear();
     }
-    uint64_t upload_bytes() const
+    // true: the leading pieces go through their own kernel.  false: none of them is periodic, and they have become the CopyPieces they
+    // are, in front of `pieces`.
+    bool plan_rows()
     {
-        return gpieces.size() * sizeof(csadev::GatherPiece) + xpieces.size() * sizeof(csadev::SpreadPiece) + pieces.size() * sizeof(csadev::CopyPiece)
-               + frags.size() * sizeof(csadev::FragFold);
+        if (kind == kSliced || periodic) return true;
+        if (kind == kSpread) as_plain(xpieces); else as_plain(gpieces);
+        return false;
     }
-    bool upload(bool compare = false)
+    // the tables to the device, and room for the sums and for a result of type R per fragment
+    template <class R> bool upload(bool rows, uint64_t *uploaded)
     {
-        const size_t np = pieces.size() + spieces.size() + gpieces.size() + xpieces.size();   // (spieces, or xpieces, or pieces with gpieces in front of them)
-        return (!xpieces.empty() ? d_pieces.upload(xpieces.data(), xpieces.size() * sizeof(csadev::SpreadPiece))
-                : spieces.empty() ? d_pieces.upload(pieces.data(), pieces.size() * sizeof(csadev::CopyPiece))
-                                  : d_pieces.upload(spieces.data(), spieces.size() * sizeof(csadev::SlicePiece)))
-               && (gpieces.empty() || d_gpieces.upload(gpieces.data(), gpieces.size() * sizeof(csadev::GatherPiece)))
+        const Lead ld = lead();
+        const size_t np = ld.n + pieces.size();
+        if (uploaded) *uploaded += ld.bytes + pieces.size() * sizeof(csadev::CopyPiece) + frags.size() * sizeof(csadev::FragFold);
+        return (!rows || d_lead.upload(ld.p, ld.bytes))
+               && ((rows && kind != kGathered) || d_pieces.upload(pieces.data(), pieces.size() * sizeof(csadev::CopyPiece)))
                && d_frags.upload(frags.data(), frags.size() * sizeof(csadev::FragFold))
                && d_sums.alloc(np * sizeof(csadev::PieceSums))
-               && d_res.alloc(frags.size() * (compare ? sizeof(csadev::FragDiff) : sizeof(csadev::FragResult)))
-               && (!compare || d_firsts.alloc(np * sizeof(uint32_t)));
+               && d_res.alloc(frags.size() * sizeof(R))
+               && (!std::is_same<R, csadev::FragDiff>::value || d_firsts.alloc(np * sizeof(uint32_t)));
     }
-    // k_frag_fold over the sums k_frag_pieces left, and the fragments' results read back: res.size() * sizeof(FragResult) bytes
-    bool fold(DevTimer &tm, double *ms, uint64_t &launches, std::vector<csadev::FragResult> &res)
+    // k_frag_fold over the sums the piece pass left (k_frag_fold_diff: and over the first differences), and the fragments' results
+    // read back: res.size() * sizeof(R) bytes
+    template <class R> bool fold(const LaunchSlot &at, std::vector<R> &res)
     {
-        if (!tm.timed(ms, launches, [&] { launch_frag_fold(d_frags.p, d_sums.p, d_res.p, (uint32_t)frags.size(), tm.st); })) return false;
-        res.resize(frags.size());
-        return res.empty() || HIP_OK(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(csadev::FragResult), hipMemcpyDeviceToHost));
+        const uint32_t n = (uint32_t)frags.size();
+        if (!at.tm.timed(at.ms_fold, at.launches, [&] {
+                if (std::is_same<R, csadev::FragDiff>::value) launch_frag_fold_diff(d_frags.p, d_sums.p, d_firsts.p, d_res.p, n, at.tm.st);
+                else launch_frag_fold(d_frags.p, d_sums.p, d_res.p, n, at.tm.st); })) return false;
+        res.resize(n);
+        return res.empty() || HIP_OK(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(R), hipMemcpyDeviceToHost));
     }
-    // k_frag_fold_diff over what k_frag_compare left: res.size() * sizeof(FragDiff) bytes read back
-    bool fold_diff(DevTimer &tm, double *ms, uint64_t &launches, std::vector<csadev::FragDiff> &res)
+};
+
+// The coded streams of a wave's tasks, staged for CSCMI_DecodeDeviceBatch (csa_worker.cpp:59-90 for every task at once): one
+// k_gather_extents launch brings every task's 10 property bytes -- they may span archive blocks -- into a 16-byte slot, and the stream
+// of every task of more than one archive block into one piece of d_gat; a stream of one block is decoded where it lies.  The
+// property bytes are read back.  Both directions use it: the read for the tasks it decodes, the update for the candidates it checks.
+struct StagedStreams {
+    // a task's archive blocks clipped to the archive (dev_stream_extents), their bytes, and the room its decoded bytes get
+    struct Task { const std::vector<Extent> *ext; uint64_t stream, cap; };
+    std::vector<Task> tasks;
+    std::vector<uint8_t> props;                // 16 bytes per task, the first CSC_PROP_SIZE of them read back
+    uint64_t raw_bytes = 0;                    // all the decoded bytes' room
+    uint64_t table_bytes = 0;                  // the piece table of the gather, as uploaded
+
+    // body == false: the property bytes only -- no stream is gathered, nothing will be decoded.  The launch is `launches`' and its
+    // time *ms's.  false: a device error, or sizes that wrap.
+    bool stage(const uint8_t *arc_, bool body, DevTimer &tm, double *ms, uint64_t &launches)
     {
-        if (!tm.timed(ms, launches, [&] { launch_frag_fold_diff(d_frags.p, d_sums.p, d_firsts.p, d_res.p, (uint32_t)frags.size(), tm.st); })) return false;
-        res.resize(frags.size());
-        return res.empty() || HIP_OK(hipMemcpy(res.data(), d_res.p, res.size() * sizeof(csadev::FragDiff), hipMemcpyDeviceToHost));
+        using namespace csadev;
+        const size_t count = tasks.size();
+        arc = arc_;
+        gat_off.assign(count, 0);
+        raw_off.assign(count, 0);
+        uint64_t gat_bytes = 0, r;
+        for (size_t k = 0; k < count && body; k++) {
+            const Task &t = tasks[k];
+            if (t.stream > CSC_PROP_SIZE && t.ext->size() > 1) {
+                gat_off[k] = gat_bytes;
+                if (!add_ok(t.stream - CSC_PROP_SIZE, 255, &r) || !add_ok(gat_bytes, r & ~255ull, &gat_bytes)) return false;
+            }
+            raw_off[k] = raw_bytes;
+            if (!add_ok(t.cap, 255, &r) || !add_ok(raw_bytes, r & ~255ull, &raw_bytes)) return false;
+        }
+        if (!d_gat.alloc(gat_bytes) || !d_raw.alloc(raw_bytes) || !d_props.alloc(16 * count)) return false;
+        std::vector<CopyPiece> gp;
+        for (size_t k = 0; k < count; k++) {
+            uint64_t pos = 0;                                                    // position in the task's stream
+            for (const Extent &x : *tasks[k].ext) {
+                const uint8_t *src = arc + x.off;
+                uint64_t n = x.size;
+                if (pos < CSC_PROP_SIZE) {
+                    const uint64_t h = std::min<uint64_t>(CSC_PROP_SIZE - pos, n);
+                    gp.push_back(CopyPiece{src, (uint8_t *)d_props.p + 16 * k + pos, (uint32_t)h, 0});
+                    src += h; n -= h; pos += h;
+                }
+                if (body && tasks[k].ext->size() > 1 && n)
+                    piece_split(src, (uint8_t *)d_gat.p + gat_off[k] + (pos - CSC_PROP_SIZE), n, kGatherPiece,
+                                [&](uint64_t, const CopyPiece &p) { gp.push_back(p); });
+                pos += n;
+                if (!body && pos >= CSC_PROP_SIZE) break;
+            }
+        }
+        if (gp.size() > 0x7FFFFFFFull) return false;
+        props.assign(16 * count, 0);
+        table_bytes = gp.size() * sizeof(CopyPiece);
+        DevBuf d_gp;
+        return d_gp.upload(gp.data(), table_bytes)
+               && tm.timed(ms, launches, [&] { launch_gather_extents(d_gp.p, (uint32_t)gp.size(), tm.st); })
+               && HIP_OK(hipMemcpy(props.data(), d_props.p, props.size(), hipMemcpyDeviceToHost));
     }
+    bool has_props(size_t k) const { return tasks[k].stream >= CSC_PROP_SIZE; }       // csa_worker.cpp:77-80: no property bytes, no decoder
+    const uint8_t *props_of(size_t k) const { return props.data() + 16 * k; }
+    const uint8_t *raw(size_t k) const { return (const uint8_t *)d_raw.p + raw_off[k]; }   // where task k's decoded bytes go
+    // the decode of task k (has_props(k), staged with its body): its properties, its stream behind them, its room
+    CSCMIDevDecode job(size_t k) const
+    {
+        const Task &t = tasks[k];
+        CSCMIDevDecode j;
+        memset(&j, 0, sizeof(j));
+        CSCDec_ReadProperties(&j.props, const_cast<uint8_t *>(props_of(k)));
+        j.src = t.ext->size() > 1 ? (const uint8_t *)d_gat.p + gat_off[k] : arc + (*t.ext)[0].off + CSC_PROP_SIZE;
+        j.src_size = (size_t)(t.stream - CSC_PROP_SIZE);
+        j.dst = (uint8_t *)d_raw.p + raw_off[k];
+        j.dst_cap = (size_t)t.cap;
+        return j;
+    }
+
+private:
+    const uint8_t *arc = nullptr;
+    DevBuf d_gat, d_raw, d_props;
+    std::vector<uint64_t> gat_off, raw_off;
 };
 
 // The caller's side of a read: entry i of the layout (L.files) is delivered to -- or, with `diffs`, compared with -- ptrs[i].
@@ -352,73 +490,32 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
     using namespace csadev;
     static const std::vector<Extent> kNoBlocks;
     int worst = 0;
-    // 1. the streams: where each task's coded bytes lie, what has to be gathered, where its decoded bytes go
+    // 1. the streams, staged: where each task's coded bytes lie, and its decoded bytes' room
     std::vector<std::vector<Extent>> ext(count);
-    std::vector<uint64_t> total(count, 0), gat_off(count, 0), raw_off(count, 0);
-    uint64_t gat_bytes = 0, raw_bytes = 0;
+    StagedStreams St;
     for (size_t k = 0; k < count; k++) {
         const DevTask &t = L.tasks[first + k];
         auto ab = A.abindex.find(t.bid);
-        if (!dev_stream_extents(ab == A.abindex.end() ? kNoBlocks : ab->second, A.arc_size, ext[k], total[k])) return CSCMI_DEVICE_ERROR;
-        uint64_t r;
-        if (total[k] > CSC_PROP_SIZE && ext[k].size() > 1) {
-            gat_off[k] = gat_bytes;
-            if (!add_ok(total[k] - CSC_PROP_SIZE, 255, &r) || !add_ok(gat_bytes, r & ~255ull, &gat_bytes)) return CSCMI_DEVICE_ERROR;
-        }
-        raw_off[k] = raw_bytes;
-        if (!add_ok(SS ? t.stop : t.raw, 255, &r) || !add_ok(raw_bytes, r & ~255ull, &raw_bytes)) return CSCMI_DEVICE_ERROR;
+        uint64_t total;
+        if (!dev_stream_extents(ab == A.abindex.end() ? kNoBlocks : ab->second, A.arc_size, ext[k], total)) return CSCMI_DEVICE_ERROR;
+        St.tasks.push_back(StagedStreams::Task{&ext[k], total, SS ? t.stop : t.raw});
     }
-    DevBuf d_gat, d_raw, d_props;
-    if (!d_gat.alloc(gat_bytes) || !d_raw.alloc(raw_bytes) || !d_props.alloc(16 * count)) return CSCMI_DEVICE_ERROR;
+    if (!St.stage(A.arc, true, tm, &A.kernel_ms[0], S.launches)) return CSCMI_DEVICE_ERROR;
+    S.readback_bytes += St.props.size();
 
-    // 2. gather: the property bytes of every task (they may span blocks) and the streams of more than one block
-    std::vector<CopyPiece> gp;
-    for (size_t k = 0; k < count; k++) {
-        uint64_t pos = 0;                                                    // position in the task's stream
-        for (const Extent &x : ext[k]) {
-            const uint8_t *src = A.arc + x.off;
-            uint64_t n = x.size;
-            if (pos < CSC_PROP_SIZE) {
-                const uint64_t h = std::min<uint64_t>(CSC_PROP_SIZE - pos, n);
-                gp.push_back(CopyPiece{src, (uint8_t *)d_props.p + 16 * k + pos, (uint32_t)h, 0});
-                src += h; n -= h; pos += h;
-            }
-            if (ext[k].size() > 1 && n)
-                piece_split(src, (uint8_t *)d_gat.p + gat_off[k] + (pos - CSC_PROP_SIZE), n, kGatherPiece,
-                            [&](uint64_t, const CopyPiece &p) { gp.push_back(p); });
-            pos += n;
-        }
-    }
-    if (gp.size() > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
-    std::vector<uint8_t> props(16 * count, 0);
-    {
-        DevBuf d_gp;
-        if (!d_gp.upload(gp.data(), gp.size() * sizeof(CopyPiece))) return CSCMI_DEVICE_ERROR;
-        if (!tm.timed(&A.kernel_ms[0], S.launches, [&] { launch_gather_extents(d_gp.p, (uint32_t)gp.size(), tm.st); })) return CSCMI_DEVICE_ERROR;
-        if (!HIP_OK(hipMemcpy(props.data(), d_props.p, props.size(), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-        S.readback_bytes += props.size();
-    }
-
-    // 3. decode: csa_worker.cpp:59-90 for every task of the wave at once
+    // 2. decode
     std::vector<CSCMIDevDecode> jobs;
     std::vector<size_t> job_task;
     std::vector<uint64_t> stops;
     std::vector<uint64_t> produced(count, 0);
     for (size_t k = 0; k < count; k++) {
-        if (total[k] < CSC_PROP_SIZE) { worst = -1; continue; }               // csa_worker.cpp:77-80: no property bytes, no decoder
-        CSCMIDevDecode j;
-        memset(&j, 0, sizeof(j));
-        CSCDec_ReadProperties(&j.props, props.data() + 16 * k);
-        j.src = ext[k].size() > 1 ? (const uint8_t *)d_gat.p + gat_off[k] : A.arc + ext[k][0].off + CSC_PROP_SIZE;
-        j.src_size = (size_t)(total[k] - CSC_PROP_SIZE);
-        j.dst = (uint8_t *)d_raw.p + raw_off[k];
-        j.dst_cap = (size_t)(SS ? L.tasks[first + k].stop : L.tasks[first + k].raw);
-        jobs.push_back(j);
+        if (!St.has_props(k)) { worst = -1; continue; }
+        jobs.push_back(St.job(k));
         job_task.push_back(k);
-        stops.push_back(j.dst_cap);
+        stops.push_back(jobs.back().dst_cap);
     }
     if (SS) {
-        SS->scratch_bytes += raw_bytes;
+        SS->scratch_bytes += St.raw_bytes;
         for (size_t k = 0; k < count; k++) {
             const DevTask &t = L.tasks[first + k];
             SS->task_raw_bytes += t.raw;
@@ -439,11 +536,11 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
         }
     }
 
-    // 4. scatter (or compare) and verify: the fragments at least one byte of which was delivered, clipped to what was delivered
-    FragTables T;
+    // 3. scatter (or compare) and verify: the fragments at least one byte of which was delivered, clipped to what was delivered
+    // (both launches even when no fragment was delivered: a wave is always the same three)
+    FragTables T(L.sliced ? FragTables::kSliced : FragTables::kSpread);
     std::vector<uint32_t> ff_file;
     std::vector<uint64_t> ff_posfile;
-    bool store = false;
     for (size_t k = 0; k < count; k++) {
         const DevTask &t = L.tasks[first + k];
         for (const DevFrag &f : t.frags) {
@@ -456,28 +553,19 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
                 if (n < want) B.diffs[f.file].status |= CSA_DIFF_SHORT;
             }
             if (!n) continue;
-            const uint8_t *src = (const uint8_t *)d_raw.p + raw_off[k] + f.posblock;
+            const uint8_t *src = St.raw(k) + f.posblock;
             if (!(L.sliced ? T.add_sliced(src, p, L.slices[f.file], f.posfile, n, f.checksum, *B.slice_stats)
                            : T.add_spread(src, p, B.bslices[f.file], f.posfile, n, f.checksum, B.diffs ? cmp : n, B.diffs != nullptr, *B.spread)))
                 return CSCMI_DEVICE_ERROR;
             ff_file.push_back(f.file);
             ff_posfile.push_back(f.posfile);
-            store = store || p;
         }
     }
-    // (both launches even when no fragment was delivered: a wave is always the same three)
-    // a wave with a periodic piece sends all its pieces through k_frag_spread / k_frag_compare_rows with one table; any other runs
-    // k_frag_pieces / k_frag_compare over CopyPieces
-    const bool rows = T.xperiodic > 0;
-    if (!rows) T.spread_as_plain();
+    const LaunchSlot slot = {tm, &A.kernel_ms[1], &A.kernel_ms[2], S.launches};
     std::vector<FragResult> res;
     if (B.diffs) {
         std::vector<FragDiff> rd;
-        if (!T.upload(true)
-            || !tm.timed(&A.kernel_ms[1], S.launches, [&] {
-                   if (rows) launch_frag_compare_rows(T.d_pieces.p, T.d_sums.p, T.d_firsts.p, (uint32_t)T.xpieces.size(), tm.st);
-                   else launch_frag_compare(T.d_pieces.p, T.d_sums.p, T.d_firsts.p, (uint32_t)T.pieces.size(), tm.st); })
-            || !T.fold_diff(tm, &A.kernel_ms[2], S.launches, rd)) return CSCMI_DEVICE_ERROR;
+        if (!T.compare(slot, nullptr, rd)) return CSCMI_DEVICE_ERROR;
         S.readback_bytes += rd.size() * sizeof(FragDiff);
         for (size_t i = 0; i < rd.size(); i++) {
             res.push_back(FragResult{rd[i].adler, rd[i].ok});
@@ -487,12 +575,7 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
             d.first_diff = std::min(d.first_diff, ff_posfile[i] + rd[i].first);
         }
     } else {
-        if (!T.upload()
-            || !tm.timed(&A.kernel_ms[1], S.launches, [&] {
-                   if (L.sliced) launch_frag_slices(T.d_pieces.p, T.d_sums.p, (uint32_t)T.spieces.size(), tm.st);
-                   else if (rows) launch_frag_spread(T.d_pieces.p, T.d_sums.p, (uint32_t)T.xpieces.size(), tm.st);
-                   else launch_frag_pieces(T.d_pieces.p, T.d_sums.p, (uint32_t)T.pieces.size(), store, tm.st); })
-            || !T.fold(tm, &A.kernel_ms[2], S.launches, res)) return CSCMI_DEVICE_ERROR;
+        if (!T.sum(slot, true, nullptr, res)) return CSCMI_DEVICE_ERROR;
         S.readback_bytes += res.size() * sizeof(FragResult);
     }
     for (size_t i = 0; i < res.size(); i++)
@@ -564,14 +647,6 @@ int CSAMI_DevicePlan(CSADevArchive *a, const char *const *names, int nnames,
 
 namespace {
 
-// whole-buffer slices: entry i's side is all of a buffer of bytes[i] bytes
-void whole_slices(const uint64_t *bytes, size_t n, std::vector<csadev::Slice> &out)
-{
-    out.assign(n, csadev::Slice{0, 0, 0, 0});
-    for (size_t i = 0; i < n; i++)
-        if (bytes[i]) out[i] = csadev::Slice{0, bytes[i], bytes[i], 1};
-}
-
 // false where CSAMI_CheckSlices refuses the caller's buffers: the slice B.bslices[i] of B.ptrs[i], nothing where that is NULL
 bool dev_bufs_ok(const CSADevArchive *a, const DevLayout &L, const ReadBufs &B, bool disjoint)
 {
@@ -582,17 +657,13 @@ bool dev_bufs_ok(const CSADevArchive *a, const DevLayout &L, const ReadBufs &B, 
     return CSAMI_CheckSlices((const void *const *)B.ptrs, B.bsizes, sl.data(), (uint32_t)L.files.size(), a->arc, a->arc_size, disjoint, nullptr) == 0;
 }
 
-// The one read path below CSAMI_DeviceReadIntoSlices, CSAMI_DeviceCompareSlices, CSAMI_DeviceReadInto, CSAMI_DeviceReadSlices, CSAMI_DeviceCompare,
-// CSAMI_DeviceRead and CSAMI_DeviceReadStop: the address checks, then the waves.  B.bslices[i] selects the bytes of B.ptrs[i] that
-// may be touched (ignored where that is NULL); `disjoint`: they are written, so no two selections may meet.  ss: stop every task
-// behind its last selected byte, and add to *ss.  `failed` gets one count per entry.  -1 with nothing launched where
-// CSAMI_CheckSlices refuses the buffers.
-int dev_read_run(CSADevArchive *a, const DevLayout &L, const ReadBufs &B, bool disjoint, const CSAOptions *opt,
-                 std::vector<uint32_t> &failed, CSADevReadStats &S, CSADevStopStats *ss)
+// The waves of a read over buffers dev_bufs_ok has passed.  ss: stop every task behind its last selected byte, and add to *ss.
+// `failed` gets one count per entry.
+int dev_read_run(CSADevArchive *a, const DevLayout &L, const ReadBufs &B, const CSAOptions *opt, std::vector<uint32_t> &failed,
+                 CSADevReadStats &S, CSADevStopStats *ss)
 {
     const double t0 = now_s();
     failed.assign(L.files.size(), 0);
-    if (!dev_bufs_ok(a, L, B, disjoint)) return -1;
     CSAOptions o;
     if (opt) o = *opt; else CSA_OptionsInit(&o);
     a->kernel_ms[0] = a->kernel_ms[1] = a->kernel_ms[2] = 0;
@@ -606,12 +677,11 @@ int dev_read_run(CSADevArchive *a, const DevLayout &L, const ReadBufs &B, bool d
     int worst = 0;
     S.readback_bytes = a->open_readback;
     for (size_t first = 0; first < L.tasks.size() && worst != CSCMI_DEVICE_ERROR;) {
-        // the task's decoded bytes and (at most) a copy of its stream, plus what its decoder holds: the dictionary (bounded by
-        // the raw size and by 1 GiB) and ~24 MiB of rings and buffers, as read_archive reckons
+        // the task's decoded bytes and (at most) a copy of its stream, plus what its decoder holds
         // (stopped early: the decoded bytes are `stop`; the dictionary and the stream's copy are what they were)
         const size_t count = wave_count(first, L.tasks.size(), width, budget, [&](size_t t) {
             const uint64_t raw = L.tasks[t].raw, out = ss ? L.tasks[t].stop : raw;
-            uint64_t need = std::min<uint64_t>(std::max<uint64_t>(raw, 1u << 20), 1ull << 30) + (24ull << 20);
+            uint64_t need = decoder_need(raw);
             if (!add_ok(need, out, &need) || !add_ok(need, raw, &need)) need = UINT64_MAX;
             return need;
         });
@@ -631,103 +701,135 @@ int dev_read_run(CSADevArchive *a, const DevLayout &L, const ReadBufs &B, bool d
     return 0;
 }
 
-// CSAMI_DeviceRead (ss == nullptr) and CSAMI_DeviceReadStop (ss: its stop statistics, never null there): the layout's offsets into
-// dst as the entries' pointers
-int dev_read(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
-             const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st, CSADevStopStats *ss)
+// What the seven read entry points hand to their one body, dev_read_call.
+struct ReadCall {
+    CSADevArchive *a;
+    const char *const *names;
+    int nnames;
+    const CSAOptions *opt;
+    CSADevFile *files;                         // the files table, of room `cap`
+    uint32_t cap;
+    bool own_buffers;                          // the entries go to `cap` buffers of the caller's: exactly that many entries, their offsets 0
+    const CSADevSlice *layout_slices;          // `sliced` (CSAMI_DeviceReadSlices): per entry, what is read of it
+    bool sliced, check_device, stop;           // check_device: refuse without a device first; stop: every task behind its last selected byte
+    CSADevReadStats *st;
+    CSADevStopStats *stop_stats;
+};
+
+// The one read call body below CSAMI_DeviceRead, CSAMI_DeviceReadStop, CSAMI_DeviceReadInto, CSAMI_DeviceCompare, CSAMI_DeviceReadSlices,
+// CSAMI_DeviceReadIntoSlices and CSAMI_DeviceCompareSlices: the refusal without a device, the zeroed statistics, the layout, the files
+// table, then what only the entry point knows -- prepare(L, B, x, disjoint) fills the caller's side B of the layout L and its own
+// statistics x, says whether the buffers are written (`disjoint`: no two selections may meet), and returns 0 or its refusal --, the
+// address checks (-1 with nothing launched where CSAMI_CheckSlices refuses the buffers), the waves, and `failed` and the statistics
+// copied out.  A refusal leaves every statistics struct zeroed.
+template <class X, class Prepare>
+int dev_read_call(const ReadCall &c, X *extra, Prepare prepare)
 {
+    static const CSADevSlice kNone = {0, 0, 0, 0};
+    if (c.check_device && CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
     CSADevReadStats S;
+    CSADevStopStats SS;
+    X x;
     memset(&S, 0, sizeof(S));
-    if (st) *st = S;
+    memset(&SS, 0, sizeof(SS));
+    memset(&x, 0, sizeof(x));
+    if (c.st) *c.st = S;
+    if (c.stop_stats) *c.stop_stats = SS;
+    if (extra) *extra = x;
     DevLayout L;
-    if (!a || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L)) return -1;
-    dev_fill_files(L, files, cap);
-    if (dst && dst_cap < L.dst_bytes) return WRITE_ERROR;
-    std::vector<uint8_t *> ptrs(L.files.size());
-    std::vector<uint64_t> sizes(L.files.size());
-    for (size_t i = 0; i < L.files.size(); i++) { ptrs[i] = dst ? (uint8_t *)dst + L.files[i].offset : nullptr; sizes[i] = L.files[i].size; }
-    std::vector<csadev::Slice> bs;
-    whole_slices(sizes.data(), sizes.size(), bs);
-    CSADevSpreadStats X;
-    memset(&X, 0, sizeof(X));
+    const CSADevSlice *ls = !c.sliced ? nullptr : c.layout_slices ? c.layout_slices : &kNone;
+    if (!c.a || (c.sliced && c.cap && !c.layout_slices) || !dev_layout(c.a->index, c.a->task_raw, make_selection(c.names, c.nnames), L, ls, ls ? c.cap : 0)
+        || (c.own_buffers && L.files.size() != c.cap)) return -1;
+    dev_fill_files(L, c.files, c.cap);
+    for (uint32_t i = 0; c.own_buffers && c.files && i < c.cap; i++) c.files[i].offset = 0;
     ReadBufs B;
-    if (dst) B.ptrs = ptrs.data();
-    B.bslices = bs.data(); B.bsizes = sizes.data(); B.spread = &X;
+    bool disjoint = true;
+    if (const int rc = prepare(L, B, x, disjoint)) return rc;
+    if (!dev_bufs_ok(c.a, L, B, disjoint)) return -1;
     std::vector<uint32_t> failed;
-    const int rc = dev_read_run(a, L, B, true, opt, failed, S, ss);
-    for (size_t i = 0; files && i < failed.size() && i < cap; i++) files[i].failed_frags = failed[i];
-    if (st) *st = S;
+    const int rc = dev_read_run(c.a, L, B, c.opt, failed, S, c.stop ? &SS : nullptr);
+    for (size_t i = 0; i < failed.size() && i < c.cap; i++) {
+        if (B.diffs) B.diffs[i].failed_frags = failed[i];
+        if (c.files) c.files[i].failed_frags = failed[i];
+    }
+    if (c.st) *c.st = S;
+    if (c.stop_stats) *c.stop_stats = SS;
+    if (extra) *extra = x;
     return rc;
 }
 
+// CSAMI_DeviceRead and CSAMI_DeviceReadStop (`stop`, with its stop statistics): the layout's offsets into dst as the entries' pointers
+int dev_read(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap, const CSAOptions *opt, CSADevFile *files,
+             uint32_t cap, CSADevReadStats *st, bool stop, CSADevStopStats *stop_stats)
+{
+    std::vector<uint8_t *> ptrs;
+    std::vector<uint64_t> sizes;
+    std::vector<csadev::Slice> bs;
+    const ReadCall c = {a, names, nnames, opt, files, cap, false, nullptr, false, stop, stop, st, stop_stats};
+    return dev_read_call(c, (CSADevSpreadStats *)nullptr, [&](const DevLayout &L, ReadBufs &B, CSADevSpreadStats &X, bool &) {
+        if (dst && dst_cap < L.dst_bytes) return WRITE_ERROR;
+        for (const DevFilePlan &f : L.files) {
+            ptrs.push_back(dst ? (uint8_t *)dst + f.offset : nullptr);
+            sizes.push_back(f.size);
+            bs.push_back(whole_slice(f.size));
+        }
+        if (dst) B.ptrs = ptrs.data();
+        B.bslices = bs.data(); B.bsizes = sizes.data(); B.spread = &X;
+        return 0;
+    });
+}
+
 // CSAMI_DeviceReadIntoSlices (diffs == nullptr) and CSAMI_DeviceCompareSlices (compare; diffs may still be NULL, which is refused):
-// the refusal without a device, the zeroed statistics, the layout, n, the files table with offset 0, the slices, dev_read_run.
+// entry i's side is the slice slices[i] of the buffer ptrs[i] of sizes[i] bytes.
 // `whole` (CSAMI_DeviceReadInto, CSAMI_DeviceCompare): `slices` is not looked at -- entry i's side is the first size_i bytes of a buffer
 // of sizes[i] (the read), or all sizes[i] bytes of it (the comparison).
 int dev_into(CSADevArchive *a, const char *const *names, int nnames, const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices,
              bool whole, uint32_t n, uint32_t flags, const CSAOptions *opt, CSADevFile *files, bool compare, CSADevDiff *diffs, CSADevReadStats *st,
              CSADevStopStats *stop_stats, CSADevSpreadStats *spread_stats)
 {
-    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;               // (before anything of the caller's is touched)
-    if (st) memset(st, 0, sizeof(*st));
-    if (stop_stats) memset(stop_stats, 0, sizeof(*stop_stats));
-    if (spread_stats) memset(spread_stats, 0, sizeof(*spread_stats));
-    DevLayout L;
-    if (!a || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L) || L.files.size() != n) return -1;
-    dev_fill_files(L, files, n);
-    for (uint32_t i = 0; files && i < n; i++) files[i].offset = 0;
-    if (n && ((!whole && (!slices || !sizes)) || (compare && (!diffs || (ptrs && !sizes))))) return -1;
-    // the slices, each inside its buffer; the bytes each selects
     std::vector<csadev::Slice> bs(n, csadev::Slice{0, 0, 0, 0});
     std::vector<uint64_t> bsz(n, 0), sel(n, 0), lim(n, 0);
-    CSADevSpreadStats X;
-    memset(&X, 0, sizeof(X));
-    for (uint32_t i = 0; i < n; i++) {
-        if (!ptrs || !ptrs[i]) continue;
-        const uint64_t size = L.files[i].size;
-        if (whole) {
-            if (!compare && (!sizes || sizes[i] < size)) return WRITE_ERROR;
-            bsz[i] = sizes[i];
-            sel[i] = compare ? sizes[i] : size;
-            if (sel[i]) bs[i] = csadev::Slice{0, sel[i], sel[i], 1};
-        } else {
-            bs[i] = csadev::Slice{slices[i].offset, slices[i].run, slices[i].stride, slices[i].count};
-            bsz[i] = sizes[i];
-            if (!csadev::slice_check(bs[i], bsz[i], &sel[i])) return -1;
+    const ReadCall c = {a, names, nnames, opt, files, n, true, nullptr, false, true, (flags & CSAMI_DEV_STOP_EARLY) != 0, st, stop_stats};
+    return dev_read_call(c, spread_stats, [&](const DevLayout &L, ReadBufs &B, CSADevSpreadStats &X, bool &disjoint) {
+        if (n && ((!whole && (!slices || !sizes)) || (compare && (!diffs || (ptrs && !sizes))))) return -1;
+        // the slices, each inside its buffer; the bytes each selects
+        for (uint32_t i = 0; i < n; i++) {
+            if (!ptrs || !ptrs[i]) continue;
+            const uint64_t size = L.files[i].size;
+            if (whole) {
+                if (!compare && (!sizes || sizes[i] < size)) return WRITE_ERROR;
+                bsz[i] = sizes[i];
+                sel[i] = compare ? sizes[i] : size;
+                bs[i] = whole_slice(sel[i]);
+            } else {
+                bs[i] = dev_slice(slices[i]);
+                bsz[i] = sizes[i];
+                if (!csadev::slice_check(bs[i], bsz[i], &sel[i])) return -1;
+            }
         }
-    }
-    for (uint32_t i = 0; i < n; i++) {
-        const bool have = ptrs && ptrs[i];
-        const uint64_t size = L.files[i].size;
-        if (have && !compare && sel[i] < size) return WRITE_ERROR;           // a destination too short for its entry
-        lim[i] = std::min(size, sel[i]);
-        const uint64_t hull = bs[i].count ? (bs[i].count - 1) * bs[i].stride + bs[i].run : 0;      // (checked by slice_check)
-        if (!add_ok(X.selected_bytes, lim[i], &X.selected_bytes)) X.selected_bytes = UINT64_MAX;      // (statistics only: they saturate)
-        if (!add_ok(X.hull_bytes, hull, &X.hull_bytes)) X.hull_bytes = UINT64_MAX;
-    }
-    for (uint32_t i = 0; compare && i < n; i++) {
-        const bool have = ptrs && ptrs[i];
-        diffs[i].first_diff = UINT64_MAX;
-        diffs[i].status = !have ? CSA_DIFF_SKIPPED : sel[i] != L.files[i].size ? CSA_DIFF_SIZE : 0u;
-        diffs[i].failed_frags = 0;
-    }
-    ReadBufs B;
-    B.ptrs = (uint8_t *const *)ptrs;                                       // (k_frag_compare / k_frag_compare_rows only load from them)
-    B.bslices = bs.data(); B.bsizes = bsz.data(); B.spread = &X;
-    if (compare) { B.lim = lim.data(); B.diffs = diffs; }
-    if (!dev_bufs_ok(a, L, B, !compare)) return -1;                         // (here too, so that a refusal leaves *spread_stats zeroed)
-    CSADevReadStats S;
-    CSADevStopStats SS;
-    memset(&S, 0, sizeof(S));
-    memset(&SS, 0, sizeof(SS));
-    std::vector<uint32_t> failed;
-    const int rc = dev_read_run(a, L, B, !compare, opt, failed, S, (flags & CSAMI_DEV_STOP_EARLY) ? &SS : nullptr);
-    for (uint32_t i = 0; i < n; i++) { if (compare) diffs[i].failed_frags = failed[i]; if (files) files[i].failed_frags = failed[i]; }
-    if (st) *st = S;
-    if (stop_stats) *stop_stats = SS;
-    if (spread_stats) *spread_stats = X;
-    return rc;
+        for (uint32_t i = 0; i < n; i++) {
+            const bool have = ptrs && ptrs[i];
+            const uint64_t size = L.files[i].size;
+            if (have && !compare && sel[i] < size) return WRITE_ERROR;           // a destination too short for its entry
+            lim[i] = std::min(size, sel[i]);
+            const uint64_t hull = bs[i].count ? (bs[i].count - 1) * bs[i].stride + bs[i].run : 0;      // (checked by slice_check)
+            if (!add_ok(X.selected_bytes, lim[i], &X.selected_bytes)) X.selected_bytes = UINT64_MAX;      // (statistics only: they saturate)
+            if (!add_ok(X.hull_bytes, hull, &X.hull_bytes)) X.hull_bytes = UINT64_MAX;
+        }
+        for (uint32_t i = 0; compare && i < n; i++) {
+            const bool have = ptrs && ptrs[i];
+            diffs[i].first_diff = UINT64_MAX;
+            diffs[i].status = !have ? CSA_DIFF_SKIPPED : sel[i] != L.files[i].size ? CSA_DIFF_SIZE : 0u;
+            diffs[i].failed_frags = 0;
+        }
+        B.ptrs = (uint8_t *const *)ptrs;                                       // (k_frag_compare / k_frag_compare_rows only load from them)
+        B.bslices = bs.data(); B.bsizes = bsz.data(); B.spread = &X;
+        if (compare) { B.lim = lim.data(); B.diffs = diffs; }
+        disjoint = !compare;
+        return 0;
+    });
 }
+
 
 }   // namespace
 
@@ -763,19 +865,13 @@ int CSAMI_CheckBuffers(const void *const *ptrs, const uint64_t *sizes, uint32_t 
 int CSAMI_DeviceRead(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
                      const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st)
 {
-    return dev_read(a, names, nnames, dst, dst_cap, opt, files, cap, st, nullptr);
+    return dev_read(a, names, nnames, dst, dst_cap, opt, files, cap, st, false, nullptr);
 }
 
 int CSAMI_DeviceReadStop(CSADevArchive *a, const char *const *names, int nnames, void *dst, uint64_t dst_cap,
                          const CSAOptions *opt, CSADevFile *files, uint32_t cap, CSADevReadStats *st, CSADevStopStats *stop_stats)
 {
-    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;               // (before anything of the caller's is touched)
-    CSADevStopStats SS;
-    memset(&SS, 0, sizeof(SS));
-    if (stop_stats) *stop_stats = SS;
-    const int rc = dev_read(a, names, nnames, dst, dst_cap, opt, files, cap, st, &SS);
-    if (stop_stats) *stop_stats = SS;
-    return rc;
+    return dev_read(a, names, nnames, dst, dst_cap, opt, files, cap, st, true, stop_stats);
 }
 
 int CSAMI_CheckSlices(const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices, uint32_t n, const void *excl, uint64_t excl_size,
@@ -786,7 +882,7 @@ int CSAMI_CheckSlices(const void *const *ptrs, const uint64_t *sizes, const CSAD
     struct H { uint64_t lo, hi, run, stride; uint32_t i; bool rows; };     // the hull [lo, hi]: hi is its last byte; rows: count > 1
     std::vector<H> hs;
     for (uint32_t i = 0; n && ptrs && sizes && slices && i < n; i++) {
-        csadev::Slice s = {slices[i].offset, slices[i].run, slices[i].stride, slices[i].count};
+        csadev::Slice s = dev_slice(slices[i]);
         uint64_t bytes, lo;
         if (!csadev::slice_check(s, sizes[i], &bytes)) { worst = std::min(worst, i); continue; }
         if (!s.count) continue;
@@ -858,40 +954,20 @@ int CSAMI_DeviceReadSlices(CSADevArchive *a, const char *const *names, int nname
                            const uint64_t *caps, uint32_t n, uint32_t flags, const CSAOptions *opt, CSADevFile *files, CSADevReadStats *st,
                            CSADevStopStats *stop_stats, CSADevSliceStats *slice_stats)
 {
-    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;               // (before anything of the caller's is touched)
-    if (st) memset(st, 0, sizeof(*st));
-    if (stop_stats) memset(stop_stats, 0, sizeof(*stop_stats));
-    if (slice_stats) memset(slice_stats, 0, sizeof(*slice_stats));
-    static const CSADevSlice kNone = {0, 0, 0, 0};
-    DevLayout L;
-    if (!a || (n && !slices) || !dev_layout(a->index, a->task_raw, make_selection(names, nnames), L, slices ? slices : &kNone, n)) return -1;
-    dev_fill_files(L, files, n);
-    for (uint32_t i = 0; files && i < n; i++) files[i].offset = 0;
-    CSADevSliceStats SL;
-    memset(&SL, 0, sizeof(SL));
-    SL.touched_bytes = L.touched_bytes;
-    for (uint32_t i = 0; i < n; i++) {
-        if (ptrs && ptrs[i] && (!caps || caps[i] < L.slice_bytes[i])) return WRITE_ERROR;
-        if (!add_ok(SL.selected_bytes, L.slice_bytes[i], &SL.selected_bytes)) return -1;
-    }
+    const ReadCall c = {a, names, nnames, opt, files, n, true, slices, true, true, (flags & CSAMI_DEV_STOP_EARLY) != 0, st, stop_stats};
     std::vector<csadev::Slice> bs;
-    whole_slices(L.slice_bytes.data(), L.slice_bytes.size(), bs);
-    ReadBufs B;
-    B.ptrs = (uint8_t *const *)ptrs;
-    B.bslices = bs.data(); B.bsizes = L.slice_bytes.data();
-    B.slice_stats = &SL;
-    CSADevReadStats S;
-    CSADevStopStats SS;
-    memset(&S, 0, sizeof(S));
-    memset(&SS, 0, sizeof(SS));
-    std::vector<uint32_t> failed;
-    if (!dev_bufs_ok(a, L, B, true)) return -1;      // (here too, so that a refusal leaves *slice_stats zeroed)
-    const int rc = dev_read_run(a, L, B, true, opt, failed, S, (flags & CSAMI_DEV_STOP_EARLY) ? &SS : nullptr);
-    for (uint32_t i = 0; files && i < n; i++) files[i].failed_frags = failed[i];
-    if (st) *st = S;
-    if (stop_stats) *stop_stats = SS;
-    if (slice_stats) *slice_stats = SL;
-    return rc;
+    return dev_read_call(c, slice_stats, [&](const DevLayout &L, ReadBufs &B, CSADevSliceStats &SL, bool &) {
+        SL.touched_bytes = L.touched_bytes;
+        for (uint32_t i = 0; i < n; i++) {
+            if (ptrs && ptrs[i] && (!caps || caps[i] < L.slice_bytes[i])) return WRITE_ERROR;
+            if (!add_ok(SL.selected_bytes, L.slice_bytes[i], &SL.selected_bytes)) return -1;
+            bs.push_back(whole_slice(L.slice_bytes[i]));
+        }
+        B.ptrs = (uint8_t *const *)ptrs;
+        B.bslices = bs.data(); B.bsizes = L.slice_bytes.data();
+        B.slice_stats = &SL;
+        return 0;
+    });
 }
 
 void CSAMI_DeviceKernelMs(const CSADevArchive *a, double ms[3])
@@ -1235,10 +1311,10 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
     if (gat_bytes && !d_gat.alloc(gat_bytes)) return CSCMI_DEVICE_ERROR;
 
     // 2. gather and sum in one pass: the fragments of the gathered tasks, whose pieces are stored, first -- through k_frag_rows if
-    // one of them crosses a run border, else as the CopyPieces they all are; then those of the tasks encoded where they lie, whose
-    // pieces are only summed (but for a task whose fragments the update's check has summed already)
+    // one of them crosses a run border, else as the CopyPieces they all are; then, in a launch of their own, those of the tasks
+    // encoded where they lie, whose pieces are only summed (but for a task whose fragments the update's check has summed already)
     {
-        FragTables T;
+        FragTables T(FragTables::kGathered);
         std::vector<FilePiece *> ff_piece;
         for (size_t k = 0; k < count; k++) {
             if (!gathered[k]) continue;
@@ -1250,31 +1326,19 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
             }
             in[k] = (const uint8_t *)d_gat.p + gat_off[k];
         }
-        const size_t nstore = T.gpieces.size();
-        const bool rows = std::any_of(T.gpieces.begin(), T.gpieces.end(), [](const GatherPiece &g) { return g.stride != 0; });
-        if (!rows) T.gathered_as_plain();
         for (size_t k = 0; k < count; k++) {
             if (gathered[k] || reused(k) || (W.upd && W.upd->tasks[first + k].have_sums)) continue;
             for (FilePiece &f : P.tasks[first + k].files) {
                 f.checksum = 0;
                 if (!f.size) continue;
-                if (!T.add(in[k], nullptr, f.size, 0)) return CSCMI_DEVICE_ERROR;
+                if (!T.add_summed(in[k], f.size)) return CSCMI_DEVICE_ERROR;
                 ff_piece.push_back(&f);
             }
         }
         if (!T.frags.empty()) {
-            const size_t nsum = T.gpieces.size() + T.pieces.size() - nstore, sum0 = rows ? 0 : nstore;   // sum0: the first summed piece in d_pieces
-            W.G.plain_pieces += nsum;
-            W.S.upload_bytes += T.upload_bytes();
-            if (!T.upload()) return CSCMI_DEVICE_ERROR;
-            if (nstore && !W.tm.timed(&g_write_ms[0], W.S.launches, [&] {
-                    if (rows) launch_frag_rows(T.d_gpieces.p, T.d_sums.p, (uint32_t)nstore, W.tm.st);
-                    else launch_frag_pieces(T.d_pieces.p, T.d_sums.p, (uint32_t)nstore, true, W.tm.st); })) return CSCMI_DEVICE_ERROR;
-            if (nsum && !W.tm.timed(&g_write_ms[0], W.S.launches, [&] {
-                    launch_frag_pieces((const CopyPiece *)T.d_pieces.p + sum0, (PieceSums *)T.d_sums.p + nstore, (uint32_t)nsum, false, W.tm.st); }))
-                return CSCMI_DEVICE_ERROR;
+            W.G.plain_pieces += T.summed();
             std::vector<FragResult> res;
-            if (!T.fold(W.tm, &g_write_ms[1], W.S.launches, res)) return CSCMI_DEVICE_ERROR;
+            if (!T.sum(LaunchSlot{W.tm, &g_write_ms[0], &g_write_ms[1], W.S.launches}, false, &W.S.upload_bytes, res)) return CSCMI_DEVICE_ERROR;
             W.S.readback_bytes += res.size() * sizeof(FragResult);
             for (size_t i = 0; i < res.size(); i++) ff_piece[i]->checksum = res[i].adler;        // csa_io.h:250
         }
@@ -1381,78 +1445,35 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
 int dev_check_wave(WriteCtx &W, UpdateCtx &U, AddPlan &P, const std::vector<size_t> &cand, size_t first, size_t count)
 {
     using namespace csadev;
-    const CSADevArchive &A = *U.base;
-    // 1. the streams: what has to be gathered, where the decoded bytes go
-    std::vector<uint64_t> gat_off(count, 0), raw_off(count, 0);
-    uint64_t gat_bytes = 0, raw_bytes = 0;
-    for (size_t k = 0; k < count && !U.trust; k++) {
-        const UpdTask &u = U.tasks[cand[first + k]];
-        uint64_t r;
-        if (u.stream > CSC_PROP_SIZE && u.ext.size() > 1) {
-            gat_off[k] = gat_bytes;
-            if (!add_ok(u.stream - CSC_PROP_SIZE, 255, &r) || !add_ok(gat_bytes, r & ~255ull, &gat_bytes)) return CSCMI_DEVICE_ERROR;
-        }
-        raw_off[k] = raw_bytes;
-        if (!add_ok(P.tasks[cand[first + k]].total, 255, &r) || !add_ok(raw_bytes, r & ~255ull, &raw_bytes)) return CSCMI_DEVICE_ERROR;
-    }
-    DevBuf d_gat, d_raw, d_props;
-    if (!d_gat.alloc(gat_bytes) || !d_raw.alloc(raw_bytes) || !d_props.alloc(16 * count)) return CSCMI_DEVICE_ERROR;
-
-    // 2. gather, and the property bytes back: a candidate whose 10 bytes are not what this call's encoder would write is out
-    std::vector<CopyPiece> gp;
+    // 1. the base streams, staged (under trust: their property bytes alone), and the property bytes back: a candidate whose 10 bytes
+    // are not what this call's encoder would write is out
+    StagedStreams St;
     for (size_t k = 0; k < count; k++) {
         const UpdTask &u = U.tasks[cand[first + k]];
-        uint64_t pos = 0;                                                    // position in the task's stream
-        for (const Extent &x : u.ext) {
-            const uint8_t *src = A.arc + x.off;
-            uint64_t n = x.size;
-            if (pos < CSC_PROP_SIZE) {
-                const uint64_t h = std::min<uint64_t>(CSC_PROP_SIZE - pos, n);
-                gp.push_back(CopyPiece{src, (uint8_t *)d_props.p + 16 * k + pos, (uint32_t)h, 0});
-                src += h; n -= h; pos += h;
-            }
-            if (!U.trust && u.ext.size() > 1 && n)
-                piece_split(src, (uint8_t *)d_gat.p + gat_off[k] + (pos - CSC_PROP_SIZE), n, kGatherPiece,
-                            [&](uint64_t, const CopyPiece &p) { gp.push_back(p); });
-            pos += n;
-            if (U.trust && pos >= CSC_PROP_SIZE) break;
-        }
+        St.tasks.push_back(StagedStreams::Task{&u.ext, u.stream, P.tasks[cand[first + k]].total});
     }
-    if (gp.size() > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
-    std::vector<uint8_t> props(16 * count, 0);
-    {
-        DevBuf d_gp;
-        if (!dev_upload(W, d_gp, gp.data(), gp.size() * sizeof(CopyPiece))) return CSCMI_DEVICE_ERROR;
-        if (!W.tm.timed(&U.ms, U.U.check_launches, [&] { launch_gather_extents(d_gp.p, (uint32_t)gp.size(), W.tm.st); })) return CSCMI_DEVICE_ERROR;
-        if (!HIP_OK(hipMemcpy(props.data(), d_props.p, props.size(), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-        W.S.readback_bytes += CSC_PROP_SIZE * count;
-    }
+    const bool staged = St.stage(U.base->arc, !U.trust, W.tm, &U.ms, U.U.check_launches);
+    W.S.upload_bytes += St.table_bytes;
+    if (!staged) return CSCMI_DEVICE_ERROR;
+    W.S.readback_bytes += CSC_PROP_SIZE * count;
     for (size_t k = 0; k < count; k++) {
         UpdTask &u = U.tasks[cand[first + k]];
         CSCProps want;
         uint8_t wb[CSC_PROP_SIZE];
         CSCEncProps_Init(&want, (uint32_t)std::min<uint64_t>(P.o.dict_size, P.tasks[cand[first + k]].total), P.o.level);
         CSCEnc_WriteProperties(&want, wb, 0);
-        if (u.stream < CSC_PROP_SIZE) { u.candidate = false; u.status = U.trust ? CSA_UPD_PROPS : CSA_UPD_BASE_BAD; }   // (no property bytes, no decoder)
-        else if (memcmp(wb, props.data() + 16 * k, CSC_PROP_SIZE) != 0) { u.candidate = false; u.status = CSA_UPD_PROPS; }
+        if (!St.has_props(k)) { u.candidate = false; u.status = U.trust ? CSA_UPD_PROPS : CSA_UPD_BASE_BAD; }
+        else if (memcmp(wb, St.props_of(k), CSC_PROP_SIZE) != 0) { u.candidate = false; u.status = CSA_UPD_PROPS; }
     }
 
-    // 3. verify: the base streams decoded, as CSAMI_DeviceCompareSlices decodes them -- reusable only if the stream decodes, gives
+    // 2. verify: the base streams decoded, as CSAMI_DeviceCompareSlices decodes them -- reusable only if the stream decodes, gives
     // exactly the task's bytes and is consumed to its last byte
     if (!U.trust) {
         std::vector<CSCMIDevDecode> jobs;
         std::vector<size_t> job_task;
         for (size_t k = 0; k < count; k++) {
-            const UpdTask &u = U.tasks[cand[first + k]];
-            if (!u.candidate) continue;
-            CSCMIDevDecode j;
-            memset(&j, 0, sizeof(j));
-            CSCDec_ReadProperties(&j.props, props.data() + 16 * k);
-            j.src = u.ext.size() > 1 ? (const uint8_t *)d_gat.p + gat_off[k] : A.arc + u.ext[0].off + CSC_PROP_SIZE;
-            j.src_size = (size_t)(u.stream - CSC_PROP_SIZE);
-            j.dst = (uint8_t *)d_raw.p + raw_off[k];
-            j.dst_cap = (size_t)P.tasks[cand[first + k]].total;
-            jobs.push_back(j);
+            if (!U.tasks[cand[first + k]].candidate) continue;
+            jobs.push_back(St.job(k));
             job_task.push_back(k);
         }
         if (!jobs.empty()) {
@@ -1472,9 +1493,9 @@ int dev_check_wave(WriteCtx &W, UpdateCtx &U, AddPlan &P, const std::vector<size
         }
     }
 
-    // 4. the candidates' fragments: the decoded bytes against the caller's (verify), or the caller's summed where they lie and
+    // 3. the candidates' fragments: the decoded bytes against the caller's (verify), or the caller's summed where they lie and
     // folded against the base index's checksums (trust)
-    FragTables T;
+    FragTables T(U.trust ? FragTables::kGathered : FragTables::kSpread);
     std::vector<FilePiece *> ff_piece;
     std::vector<size_t> ff_task;
     CSADevSpreadStats X;
@@ -1490,38 +1511,23 @@ int dev_check_wave(WriteCtx &W, UpdateCtx &U, AddPlan &P, const std::vector<size
             const uint32_t base_sum = u.base_sums[fi++];
             if (!f.size) { f.checksum = 0; continue; }                         // adler32 of nothing, seed 0
             const bool ok = U.trust ? T.add_gathered(W.buf(f), nullptr, W.slice(f), f.off, f.size, G, base_sum)
-                                    : T.add_spread((const uint8_t *)d_raw.p + raw_off[k] + f.posblock, (uint8_t *)W.buf(f), W.slice(f), f.off, f.size, 0,
-                                                   f.size, true, X);
+                                    : T.add_spread(St.raw(k) + f.posblock, (uint8_t *)W.buf(f), W.slice(f), f.off, f.size, 0, f.size, true, X);
             if (!ok) return CSCMI_DEVICE_ERROR;
             ff_piece.push_back(&f);
             ff_task.push_back(ti);
             U.U.checked_bytes += f.size;
         }
     }
+    const LaunchSlot slot = {W.tm, &U.ms, &U.ms, U.U.check_launches};
     std::vector<uint8_t> differs(ff_piece.size(), 0);
     if (U.trust) {
-        const bool rows = std::any_of(T.gpieces.begin(), T.gpieces.end(), [](const GatherPiece &g) { return g.stride != 0; });
-        const uint32_t np = (uint32_t)T.gpieces.size();
-        if (!rows) T.gathered_as_plain();
-        W.S.upload_bytes += T.upload_bytes();
         std::vector<FragResult> res;
-        if (!T.upload()
-            || !W.tm.timed(&U.ms, U.U.check_launches, [&] {
-                   if (rows) launch_frag_rows(T.d_gpieces.p, T.d_sums.p, np, W.tm.st);
-                   else launch_frag_pieces(T.d_pieces.p, T.d_sums.p, np, false, W.tm.st); })
-            || !T.fold(W.tm, &U.ms, U.U.check_launches, res)) return CSCMI_DEVICE_ERROR;
+        if (!T.sum(slot, true, &W.S.upload_bytes, res)) return CSCMI_DEVICE_ERROR;
         W.S.readback_bytes += res.size() * sizeof(FragResult);
         for (size_t i = 0; i < res.size(); i++) { ff_piece[i]->checksum = res[i].adler; differs[i] = !res[i].ok; }
     } else {
-        const bool rows = T.xperiodic > 0;
-        if (!rows) T.spread_as_plain();
-        W.S.upload_bytes += T.upload_bytes();
         std::vector<FragDiff> rd;
-        if (!T.upload(true)
-            || !W.tm.timed(&U.ms, U.U.check_launches, [&] {
-                   if (rows) launch_frag_compare_rows(T.d_pieces.p, T.d_sums.p, T.d_firsts.p, (uint32_t)T.xpieces.size(), W.tm.st);
-                   else launch_frag_compare(T.d_pieces.p, T.d_sums.p, T.d_firsts.p, (uint32_t)T.pieces.size(), W.tm.st); })
-            || !T.fold_diff(W.tm, &U.ms, U.U.check_launches, rd)) return CSCMI_DEVICE_ERROR;
+        if (!T.compare(slot, &W.S.upload_bytes, rd)) return CSCMI_DEVICE_ERROR;
         W.S.readback_bytes += rd.size() * sizeof(FragDiff);
         // (where no byte differs the sum of the decoded bytes is the sum of the caller's)
         for (size_t i = 0; i < rd.size(); i++) { ff_piece[i]->checksum = rd[i].adler; differs[i] = rd[i].first < T.frags[i].size; }
@@ -1584,12 +1590,8 @@ int CSAMI_DeviceWriteFrom(const void *const *ptrs, CSADevFile *files, uint32_t n
                           void *arc_dev, uint64_t arc_cap, const CSAOptions *opt, CSADevWriteStats *st)
 {
     if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
-    // every entry whole: slices[i] = {0, esize, esize, 1} of a buffer of esize bytes (a table the write refuses is refused there)
-    std::vector<CSADevSlice> slices(n_files, CSADevSlice{0, 0, 0, 0});
-    std::vector<uint64_t> sizes(n_files, 0);
-    for (uint32_t i = 0; files && i < n_files; i++)
-        if (files[i].esize > 0) { sizes[i] = (uint64_t)files[i].esize; slices[i] = CSADevSlice{0, sizes[i], sizes[i], 1}; }
-    return CSAMI_DeviceWriteSlices(ptrs, sizes.data(), slices.data(), files, n_files, arcname, arc_dev, arc_cap, opt, st, nullptr);
+    // every entry whole: the update reads sizes == slices == NULL as that (a table the write refuses is refused there)
+    return CSAMI_DeviceUpdate(nullptr, ptrs, nullptr, nullptr, files, n_files, arcname, arc_dev, arc_cap, 0, opt, st, nullptr, nullptr, nullptr, 0);
 }
 
 int CSAMI_DeviceWriteSlices(const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices, CSADevFile *files, uint32_t n_files,
@@ -1625,29 +1627,20 @@ int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint6
     // ---- everything the host can refuse, before any launch
     uint64_t a1;
     if (!arcname || (!arc_dev && arc_cap) || !add_ok((uintptr_t)arc_dev, arc_cap, &a1) || (n_files && (!ptrs || !files || !sizes != !slices))) return -1;
-    // every entry whole: slices[i] = {0, esize, esize, 1} of a buffer of esize bytes (a table the write refuses is refused below)
-    std::vector<CSADevSlice> whole_sl;
-    std::vector<uint64_t> whole_sz;
-    if (!slices) {
-        whole_sl.assign(n_files, CSADevSlice{0, 0, 0, 0});
-        whole_sz.assign(n_files, 0);
-        for (uint32_t i = 0; i < n_files; i++)
-            if (files[i].esize > 0) { whole_sz[i] = (uint64_t)files[i].esize; whole_sl[i] = CSADevSlice{0, whole_sz[i], whole_sz[i], 1}; }
-        slices = whole_sl.data();
-        sizes = whole_sz.data();
-    }
     AddPlan P;
     int rc = plan_write(P, files, n_files, opt, &W.S.raw_bytes);
     if (rc) return rc;
     // the slices, each inside its buffer and selecting exactly its entry's bytes; the hulls, which are all that is loaded
+    // (slices == NULL: every entry whole -- all of a buffer of esize bytes)
     std::vector<csadev::Slice> sl(n_files);
     std::vector<const void *> hull(n_files, nullptr);
     std::vector<uint64_t> hull_size(n_files, 0);
     CSADevGatherStats G = W.G;
     for (uint32_t i = 0; i < n_files; i++) {
-        sl[i] = csadev::Slice{slices[i].offset, slices[i].run, slices[i].stride, slices[i].count};
+        const uint64_t esize = (uint64_t)files[i].esize;                     // (plan_write: not negative)
+        sl[i] = slices ? dev_slice(slices[i]) : whole_slice(esize);
         uint64_t bytes, at;
-        if (!csadev::slice_check(sl[i], sizes[i], &bytes) || bytes != (uint64_t)files[i].esize) return -1;
+        if (!csadev::slice_check(sl[i], slices ? sizes[i] : esize, &bytes) || bytes != esize) return -1;
         if (!sl[i].count) continue;
         if (!ptrs[i] || !add_ok((uintptr_t)ptrs[i], sl[i].offset, &at)) return -1;
         hull[i] = (const void *)(uintptr_t)at;
@@ -1698,7 +1691,7 @@ int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint6
             const size_t count = wave_count(first, cand.size(), cwidth, budget, [&](size_t c) {
                 if (U.trust) return (uint64_t)0;
                 const uint64_t raw = P.tasks[cand[c]].total;
-                uint64_t need = std::min<uint64_t>(std::max<uint64_t>(raw, 1u << 20), 1ull << 30) + (24ull << 20);
+                uint64_t need = decoder_need(raw);
                 if (!add_ok(need, raw, &need) || !add_ok(need, U.tasks[cand[c]].stream, &need)) need = UINT64_MAX;
                 return need;
             });
