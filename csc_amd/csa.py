@@ -119,6 +119,20 @@ class CSADevUpdateStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class CSADevDigest(C.Structure):
+    _fields_ = [("b", C.c_uint8 * 32)]
+
+
+class CSADevDigestStats(C.Structure):
+    _fields_ = [("frags", C.c_uint64), ("leaves", C.c_uint64), ("digested_bytes", C.c_uint64), ("launches", C.c_uint64),
+                ("mismatches", C.c_uint64), ("first_mismatch", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        """(the names the write's and the read's statistics also have get a prefix: the dicts are merged)"""
+        return {"digest_frags": self.frags, "digest_leaves": self.leaves, "digested_bytes": self.digested_bytes, "digest_launches": self.launches,
+                "mismatches": self.mismatches, "first_mismatch": self.first_mismatch, "digest_kernel_ms": self.kernel_ms}
+
+
 LIST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(CSAFrag))
 
 SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", "CSA_ReadIndex",
@@ -130,7 +144,9 @@ SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", 
            "CSAMI_CheckBuffers", "CSAMI_DeviceWriteFrom", "CSAMI_DeviceReadInto", "CSAMI_DeviceCompare",
            "CSAMI_DeviceReadSlices", "CSAMI_PlanDeviceSlices", "CSAMI_DeviceWriteSlices",
            "CSAMI_CheckSlices", "CSAMI_DeviceReadIntoSlices", "CSAMI_DeviceCompareSlices",
-           "CSAMI_DeviceUpdate", "CSAMI_PlanDeviceUpdate"]
+           "CSAMI_DeviceUpdate", "CSAMI_PlanDeviceUpdate",
+           "CSAMI_DeviceWriteFragCount", "CSAMI_DeviceDigestSlices", "CSAMI_DeviceUpdateDigests", "CSAMI_DeviceReadDigests",
+           "CSAMI_DeviceDigestKernelMs"]
 
 CSA_MAX_FRAGMENTS = 127
 CSA_TOO_MANY_FRAGMENTS = -94
@@ -140,6 +156,9 @@ WRITE_ERROR = -97
 CSAMI_DEV_STOP_EARLY = 1
 CSA_DIFF_BYTES, CSA_DIFF_SIZE, CSA_DIFF_SKIPPED, CSA_DIFF_SHORT = 1, 2, 4, 8
 CSAMI_UPDATE_TRUST_SUMS = 1
+CSAMI_UPDATE_TRUST_DIGESTS = 2
+DIGEST_BYTES, DIGEST_LEAF = 32, 16384
+NO_MISMATCH = (1 << 64) - 1                # CSADevDigestStats.first_mismatch where nothing differs
 CSA_UPD_REUSED, CSA_UPD_NEW, CSA_UPD_PROPS, CSA_UPD_CHANGED, CSA_UPD_BASE_BAD = 0, 1, 2, 3, 4
 NO_BID = (1 << 64) - 1                     # CSADevUpdateTask.base_bid of a task that is no candidate
 NO_DIFF = (1 << 64) - 1                    # CSADevDiff.first_diff without CSA_DIFF_BYTES
@@ -246,6 +265,19 @@ def lib():
         L.CSAMI_PlanDeviceUpdate.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, files, C.c_uint32, C.POINTER(CSAOptions), u64s, C.c_uint32,
                                              C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
         L.CSAMI_PlanDeviceUpdate.restype = C.c_int
+        L.CSAMI_DeviceWriteFragCount.argtypes = [files, C.c_uint32, C.c_char_p, C.POINTER(CSAOptions), u64s]
+        L.CSAMI_DeviceWriteFragCount.restype = C.c_int
+        L.CSAMI_DeviceDigestSlices.argtypes = [ptrs, u64s, slices, files, C.c_uint32, C.c_char_p, C.POINTER(CSAOptions), C.c_void_p, C.c_uint64,
+                                               C.POINTER(CSADevDigestStats)]
+        L.CSAMI_DeviceDigestSlices.restype = C.c_int
+        L.CSAMI_DeviceUpdateDigests.argtypes = ([C.c_void_p, C.c_void_p, C.c_uint64] + L.CSAMI_DeviceUpdate.argtypes[1:]
+                                                + [C.c_void_p, C.c_uint64, C.POINTER(CSADevDigestStats)])
+        L.CSAMI_DeviceUpdateDigests.restype = C.c_int
+        L.CSAMI_DeviceReadDigests.argtypes = [C.c_void_p, C.POINTER(CSAOptions), C.c_void_p, C.c_uint64, C.c_void_p, C.POINTER(CSADevReadStats),
+                                              C.POINTER(CSADevDigestStats)]
+        L.CSAMI_DeviceReadDigests.restype = C.c_int
+        L.CSAMI_DeviceDigestKernelMs.argtypes = [C.POINTER(C.c_double)]
+        L.CSAMI_DeviceDigestKernelMs.restype = None
         _lib = L
     return _lib
 
@@ -526,6 +558,28 @@ def device_write_plan(files, arcname: str = "out.csa", **opts):
     return rc, int(nt.value), int(mf.value), int(raw.value)
 
 
+def device_write_frag_count(files, arcname: str = "out.csa", **opts):
+    """CSAMI_DeviceWriteFragCount (host only): the fragments, and so the entries of the digest table, that DeviceArchive.write of this
+    table makes -> (rc, number of fragments)"""
+    arr, keep = _write_table(files)
+    o = options(**opts)
+    n = C.c_uint64()
+    rc = lib().CSAMI_DeviceWriteFragCount(arr, len(keep), arcname.encode(), C.byref(o), C.byref(n))
+    return rc, int(n.value)
+
+
+def fragment_digest(data: bytes) -> bytes:
+    """The digest of one fragment as the device computes it (include/csa_mi355x.h): BLAKE2s-256 in tree mode -- fan-out 0, maximal
+    depth 2, leaf length 16384, inner length 32 -- with hashlib's stock parameters.  The host reference of the digest tables."""
+    import hashlib
+    data = bytes(data)
+    n_leaves = max(1, -(-len(data) // DIGEST_LEAF))
+    tree = dict(digest_size=DIGEST_BYTES, fanout=0, depth=2, leaf_size=DIGEST_LEAF, inner_size=DIGEST_BYTES)
+    leaves = b"".join(hashlib.blake2s(data[DIGEST_LEAF * i:DIGEST_LEAF * (i + 1)], node_offset=i, node_depth=0, last_node=(i == n_leaves - 1),
+                                      **tree).digest() for i in range(n_leaves))
+    return hashlib.blake2s(leaves, node_offset=0, node_depth=1, last_node=True, **tree).digest()
+
+
 def plan_device_update(raw_index: bytes, arc_size: int, files, **opts):
     """CSAMI_PlanDeviceUpdate (host only): the candidate step of DeviceArchive.update over these raw index bytes of the base and the
     new table (dicts with name, esize, edate, eattr) -> (rc, [base bid of every task of the new plan, NO_BID where it is no
@@ -547,6 +601,13 @@ def device_write_kernel_ms():
     with a piece across a run border --, k_frag_fold, k_block_table, k_gather_extents)"""
     ms = (C.c_double * 4)()
     lib().CSAMI_DeviceWriteKernelMs(ms)
+    return tuple(ms)
+
+
+def device_digest_kernel_ms():
+    """HIP-event milliseconds of this thread's last digesting call by kernel: (k_digest_leaves, k_digest_roots)"""
+    ms = (C.c_double * 2)()
+    lib().CSAMI_DeviceDigestKernelMs(ms)
     return tuple(ms)
 
 
@@ -609,9 +670,22 @@ def _write_planned(files, arcname, arc, device, opts, call, plan=False):
     return rc, (arc[:stats[0].archive_bytes] if rc == 0 else None), d
 
 
-def _write_slices(base, entries, arcname, arc, flags, whole_default, opts):
-    """DeviceArchive.write_slices (base None) and DeviceArchive.update: CSAMI_DeviceWriteSlices, or CSAMI_DeviceUpdate over the base.
-    whole_default: an entry without "slice" is its whole tensor (else: no bytes)"""
+def _is_digest_table(t) -> bool:
+    import torch
+    return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and t.dim() == 2 and t.shape[1] == DIGEST_BYTES
+
+
+def _digest_table(files, arcname, device, opts):
+    """an empty digest table for a write of `files`: (rc, uint8 CUDA tensor [n_frags, 32] or None)"""
+    import torch
+    rc, n = device_write_frag_count(files, arcname, **opts)
+    return rc, (torch.empty((n, DIGEST_BYTES), dtype=torch.uint8, device=device) if rc == 0 else None)
+
+
+def _write_slices(base, entries, arcname, arc, flags, whole_default, opts, digests=False, base_digests=None, whole=False):
+    """DeviceArchive.write_tensors (whole), DeviceArchive.write_slices (base None) and DeviceArchive.update: CSAMI_DeviceWriteSlices, or
+    CSAMI_DeviceUpdate over the base; with digests or base_digests CSAMI_DeviceUpdateDigests, and stats["digests"] is the table.
+    whole_default: an entry without "slice" is its whole tensor (else: no bytes); whole: no slices at all are handed in"""
     files, table = [], (CSADevSlice * max(len(entries), 1))()
     for a, e in zip(table, entries):
         t = e["tensor"]
@@ -627,18 +701,43 @@ def _write_slices(base, entries, arcname, arc, flags, whole_default, opts):
     sizes = (C.c_uint64 * max(len(live), 1))(*[0 if t is None else int(t.numel()) for t in live])
     device = arc.device if arc is not None else next((t.device for t in live if t is not None), "cuda")
     last = []
+    if base_digests is not None and not _is_digest_table(base_digests):
+        raise TypeError("base_digests: a contiguous torch.uint8 CUDA tensor [n, 32]")
+    out = None
+    if _is_digest_table(digests):
+        out = digests
+    elif digests is not False and digests is not None:
+        if digests is not True:
+            raise TypeError("digests: True, or a contiguous torch.uint8 CUDA tensor [n, 32] to write the table into")
+        rc, out = _digest_table(files, arcname, device, opts)
+        if rc != 0:
+            return rc, None, {"files": []}
 
     def call(arr, n, where, o, nt):
-        st, gs, us = CSADevWriteStats(), CSADevGatherStats(), CSADevUpdateStats()
-        if base is None:
-            return lib().CSAMI_DeviceWriteSlices(ptrs, sizes, table, arr, n, *where, C.byref(o), C.byref(st), C.byref(gs)), [st, gs]
-        tasks = (CSADevUpdateTask * max(nt, 1))()
-        last[:] = [tasks, nt, st]
-        return lib().CSAMI_DeviceUpdate(base._h, ptrs, sizes, table, arr, n, *where, flags, C.byref(o), C.byref(st), C.byref(gs),
-                                        C.byref(us), tasks, nt), [st, gs, us]
+        st, gs, us, ds = CSADevWriteStats(), CSADevGatherStats(), CSADevUpdateStats(), CSADevDigestStats()
+        plain = out is None and base_digests is None and not flags & CSAMI_UPDATE_TRUST_DIGESTS
+        if plain:
+            if whole:
+                return lib().CSAMI_DeviceWriteFrom(ptrs, arr, n, *where, C.byref(o), C.byref(st)), [st]
+            if base is None:
+                return lib().CSAMI_DeviceWriteSlices(ptrs, sizes, table, arr, n, *where, C.byref(o), C.byref(st), C.byref(gs)), [st, gs]
+        tasks = (CSADevUpdateTask * max(nt or 0, 1))()
+        if base is not None:
+            last[:] = [tasks, nt, st]
+        if plain:
+            return lib().CSAMI_DeviceUpdate(base._h, ptrs, sizes, table, arr, n, *where, flags, C.byref(o), C.byref(st), C.byref(gs),
+                                            C.byref(us), tasks, nt), [st, gs, us]
+        rc = lib().CSAMI_DeviceUpdateDigests(
+            None if base is None else base._h, None if base_digests is None else C.c_void_p(base_digests.data_ptr() or 0),
+            0 if base_digests is None else int(base_digests.shape[0]), ptrs, None if whole else sizes, None if whole else table, arr, n, *where,
+            flags, C.byref(o), C.byref(st), C.byref(gs), C.byref(us), tasks, nt or 0,
+            None if out is None else C.c_void_p(out.data_ptr() or 0), 0 if out is None else int(out.shape[0]), C.byref(ds))
+        return rc, ([st] if whole else [st, gs]) + ([us] if base is not None else []) + [ds]
     rc, arc, d = _write_planned(files, arcname, arc, device, opts, call, plan=base is not None)
     if last:
         d["tasks"] = [t.as_dict() for t in last[0][:min(last[1], int(last[2].tasks))]]
+    if out is not None:
+        d["digests"] = out
     return rc, arc, d
 
 
@@ -733,10 +832,12 @@ class DeviceArchive:
         return _write_planned(files, arcname, arc, src.device, opts, call)
 
     @staticmethod
-    def write_tensors(entries, arcname: str = "out.csa", arc=None, **opts):
+    def write_tensors(entries, arcname: str = "out.csa", arc=None, digests=False, **opts):
         """`csarc a -t1` of entries that lie in tensors of their own (CSAMI_DeviceWriteFrom) -> (rc, uint8 CUDA view of the archive,
         stats dict), as write.  entries: dicts with name, tensor, edate, eattr; tensor: a 1-d contiguous torch.uint8 CUDA tensor of any
-        alignment, its numel the entry's size, or None for directories and empty files.  The tensors may alias each other, not arc."""
+        alignment, its numel the entry's size, or None for directories and empty files.  The tensors may alias each other, not arc.
+        digests (True, or a contiguous uint8 CUDA tensor [n, 32] to write into): stats["digests"] is the archive's digest table, a uint8
+        CUDA tensor [n_frags, 32] in index order, and the digest statistics are merged in (CSAMI_DeviceUpdateDigests)."""
         files = []
         for e in entries:
             t = e["tensor"]
@@ -748,6 +849,8 @@ class DeviceArchive:
         live = [e["tensor"] for e in entries]                      # alive across the call
         ptrs = (C.c_void_p * max(len(live), 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in live])
         device = arc.device if arc is not None else next((t.device for t in live if t is not None), "cuda")
+        if digests is not False and digests is not None:
+            return _write_slices(None, entries, arcname, arc, 0, True, opts, digests=digests, whole=True)
 
         def call(arr, n, where, o, nt):
             st = CSADevWriteStats()
@@ -755,24 +858,76 @@ class DeviceArchive:
         return _write_planned(files, arcname, arc, device, opts, call)
 
     @staticmethod
-    def write_slices(entries, arcname: str = "out.csa", arc=None, **opts):
+    def write_slices(entries, arcname: str = "out.csa", arc=None, digests=False, **opts):
         """`csarc a -t1` of entries gathered from strided slices of buffers (CSAMI_DeviceWriteSlices) -> (rc, uint8 CUDA view of the
         archive, stats dict), as write_tensors, with the gather statistics beside the write's.  entries: dicts with name, tensor,
         slice, edate, eattr; tensor: the 1-d contiguous torch.uint8 CUDA base buffer (None for directories and empty files); slice:
         (offset, length) | (offset, run, stride, count) into it -- rows_slice makes one for a block of a row-major matrix,
         tensor_slice both for a strided view.  The entry's bytes are the selected ones, packed: esize = run * count.  The buffers
-        are only read and may alias each other, not arc."""
-        return _write_slices(None, entries, arcname, arc, 0, False, opts)
+        are only read and may alias each other, not arc.  digests: as in write_tensors."""
+        return _write_slices(None, entries, arcname, arc, 0, False, opts, digests=digests)
 
-    def update(self, entries, arcname: str = "out.csa", arc=None, trust_sums=False, **opts):
+    @staticmethod
+    def digest_slices(entries, arcname: str = "out.csa", **opts):
+        """the digest table write_slices(entries, digests=True) would hand out, with nothing written and nothing encoded
+        (CSAMI_DeviceDigestSlices) -> (rc, uint8 CUDA tensor [n_frags, 32], stats dict).  An entry without "slice" is its whole tensor.
+        Row i is fragment_digest of fragment i of the index: the entries in byte-wise name order, an entry's fragments in offset order."""
+        import torch
+        files, table = [], (CSADevSlice * max(len(entries), 1))()
+        for a, e in zip(table, entries):
+            t = e["tensor"]
+            if not (t is None or _is_bytes_tensor(t)):
+                raise TypeError("tensor: a contiguous 1-d torch.uint8 CUDA tensor, or None")
+            s = e.get("slice") or ((0, int(t.numel())) if t is not None else (0, 0, 0, 0))
+            a.offset, a.run, a.stride, a.count = (s[0], s[1], s[1], 1 if s[1] else 0) if len(s) == 2 else s
+            files.append({"name": e["name"], "esize": a.run * a.count if a.count else 0, "edate": e["edate"], "eattr": e["eattr"]})
+        live = [e["tensor"] for e in entries]
+        ptrs = (C.c_void_p * max(len(live), 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in live])
+        sizes = (C.c_uint64 * max(len(live), 1))(*[0 if t is None else int(t.numel()) for t in live])
+        device = next((t.device for t in live if t is not None), "cuda")
+        rc, out = _digest_table(files, arcname, device, opts)
+        if rc != 0:
+            return rc, None, {}
+        arr, keep = _write_table(files)
+        o, ds = options(**opts), CSADevDigestStats()
+        torch.cuda.synchronize()
+        rc = lib().CSAMI_DeviceDigestSlices(ptrs, sizes, table, arr, len(keep), arcname.encode(), C.byref(o), C.c_void_p(out.data_ptr() or 0),
+                                            int(out.shape[0]), C.byref(ds))
+        return rc, (out if rc == 0 else None), ds.as_dict()
+
+    def digests(self, expect=None, **opts):
+        """`csarc t` of the whole archive that also hands out its digest table (CSAMI_DeviceReadDigests) -> (rc, uint8 CUDA tensor
+        [n_frags, 32], stats dict: the read's and the digest statistics).  expect: a table to compare every fragment with on the
+        device; a mismatch counts as a failed checksum of that fragment does, and in stats["mismatches"] / ["first_mismatch"]."""
+        import torch
+        if expect is not None and not _is_digest_table(expect):
+            raise TypeError("expect: a contiguous torch.uint8 CUDA tensor [n, 32]")
+        n = sum(f["nfrags"] for f in self.plan()[0])
+        if expect is not None and int(expect.shape[0]) != n:
+            raise ValueError(f"expect: {n} rows, one per fragment of the archive")
+        out = torch.empty((n, DIGEST_BYTES), dtype=torch.uint8, device=self._arc.device)
+        o, st, ds = options(**opts), CSADevReadStats(), CSADevDigestStats()
+        torch.cuda.synchronize()
+        rc = lib().CSAMI_DeviceReadDigests(self._h, C.byref(o), C.c_void_p(out.data_ptr() or 0), n,
+                                           None if expect is None else C.c_void_p(expect.data_ptr() or 0), C.byref(st), C.byref(ds))
+        d = st.as_dict()
+        d.update(ds.as_dict())
+        return rc, out, d
+
+    def update(self, entries, arcname: str = "out.csa", arc=None, trust_sums=False, digests=False, base_digests=None, trust_digests=False,
+               **opts):
         """write_slices of `entries` with this archive as the base (CSAMI_DeviceUpdate): a task of the new plan that has the
         composition and the bytes of a task of this archive gets that task's stream copied, not encoded -> (rc, uint8 CUDA view of
         the new archive, stats dict) as write_slices, with the update statistics merged in and stats["tasks"] = [{"base_bid",
         "status"}] per task of the new plan.  entries: write_slices's; an entry without "slice" is its whole tensor.  The new
         archive is byte for byte write_slices's as long as this archive was written at the same level.  trust_sums: nothing is
         decoded -- a task is taken for unchanged when every fragment's adler32 equals this archive's index's, a 32-bit test that two
-        different contents can pass.  arc must not overlap this archive's tensor."""
-        return _write_slices(self, entries, arcname, arc, CSAMI_UPDATE_TRUST_SUMS if trust_sums else 0, True, opts)
+        different contents can pass.  arc must not overlap this archive's tensor.
+        digests: as in write_tensors -- the new archive's table, computed in this call from the entries' bytes.  base_digests: this
+        archive's table, as the call that wrote it (or digests()) handed it out.  trust_digests: nothing is decoded -- a task is taken
+        for unchanged when every fragment's BLAKE2s digest equals base_digests's at that fragment's place in this archive's index."""
+        flags = (CSAMI_UPDATE_TRUST_SUMS if trust_sums else 0) | (CSAMI_UPDATE_TRUST_DIGESTS if trust_digests else 0)
+        return _write_slices(self, entries, arcname, arc, flags, True, opts, digests=digests, base_digests=base_digests)
 
     def _by(self, bufs, names, take):
         """the selection's files table and, per entry of it, the caller's base buffer, its address and size, and the slice of it (None,

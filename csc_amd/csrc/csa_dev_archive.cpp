@@ -17,6 +17,7 @@
 #include "csa_waves.h"
 #include "csa_dev_read.h"
 #include "csa_dev_write.h"
+#include "csa_dev_digest.h"
 
 using namespace csa;
 
@@ -55,7 +56,7 @@ csadev::Slice whole_slice(uint64_t n) { return n ? csadev::Slice{0, n, n, 1} : c
 uint64_t decoder_need(uint64_t raw) { return std::min<uint64_t>(std::max<uint64_t>(raw, 1u << 20), 1ull << 30) + (24ull << 20); }
 
 struct DevFilePlan { Index::const_iterator it; uint64_t offset, size; };
-struct DevFrag { uint32_t file; uint32_t checksum; uint64_t posblock, size, posfile; };
+struct DevFrag { uint32_t file; uint32_t checksum; uint64_t posblock, size, posfile, idx; };   // idx: its place in the index, all fragments counted
 struct DevTask { uint64_t bid = 0, total = 0, raw = 0, stop = 0; std::vector<DevFrag> frags; };   // stop: max(posblock + size) over `frags`, <= raw
 struct DevLayout {
     std::vector<DevFilePlan> files;
@@ -66,6 +67,9 @@ struct DevLayout {
     std::vector<csadev::Slice> slices;
     std::vector<uint64_t> slice_bytes;
     uint64_t touched_frags = 0, touched_bytes = 0;
+    // CSAMI_DeviceReadDigests: the index's fragments, and which of the selected ones are empty (no task holds those)
+    uint64_t index_frags = 0;
+    std::vector<std::pair<uint64_t, uint32_t>> empty_idx;      // (place in the index, entry)
 };
 
 // A task's raw size: max(posblock + size) over ALL fragments of its bid.  false if any sum of the index wraps.
@@ -92,6 +96,8 @@ bool dev_layout(const Index &index, const std::map<uint64_t, uint64_t> &raw, con
     uint64_t off = 0;
     L.sliced = slices != nullptr;
     for (Index::const_iterator it = index.begin(); it != index.end(); ++it) {
+        uint64_t idx = L.index_frags;
+        L.index_frags += it->second.frags.size();
         if (!sel.has(it->first.c_str())) continue;
         uint64_t size = 0;
         const uint32_t fi = (uint32_t)L.files.size();
@@ -106,7 +112,8 @@ bool dev_layout(const Index &index, const std::map<uint64_t, uint64_t> &raw, con
             L.slice_bytes.push_back(bytes);
         }
         for (const CSAFrag &f : it->second.frags) {
-            if (!f.size) continue;
+            const uint64_t at = idx++;
+            if (!f.size) { L.empty_idx.push_back(std::make_pair(at, fi)); continue; }
             if (L.sliced) {
                 if (csadev::slice_next(sl, f.posfile) >= f.posfile + f.size) continue;
                 L.touched_frags++;
@@ -120,7 +127,7 @@ bool dev_layout(const Index &index, const std::map<uint64_t, uint64_t> &raw, con
                 L.tasks.back().raw = raw.at(f.bid);
             }
             DevTask &t = L.tasks[m->second];
-            t.frags.push_back(DevFrag{fi, f.checksum, f.posblock, f.size, f.posfile});
+            t.frags.push_back(DevFrag{fi, f.checksum, f.posblock, f.size, f.posfile, at});
             if (!add_ok(t.total, f.size, &t.total)) return false;
             t.stop = std::max(t.stop, f.posblock + f.size);               // (checked by dev_task_sizes)
         }
@@ -387,6 +394,63 @@ private:
     }
 };
 
+thread_local double g_digest_ms[2] = {0, 0};         // CSAMI_DeviceDigestKernelMs
+
+// One digest pass (csa_dev_digest.h): the leaf and fragment tables of the fragments added, their device copies and their two launches
+// -- k_digest_leaves, one lane per 16 KiB leaf, and k_digest_roots, one lane per fragment, which stores fragment i's digest to
+// out[frags[i].out] and compares it with expect[frags[i].expect] -- and one word per fragment read back.
+struct DigestPass {
+    std::vector<csadev::DigestLeaf> leaves;
+    std::vector<csadev::DigestFrag> frags;
+    uint64_t bytes = 0;
+    // a fragment of `size` bytes that is the packed bytes [at, at + size) of the (checked) slice sl of the buffer `buf`; size == 0:
+    // the empty fragment, nothing of buf or sl is looked at.  false: more leaves than a launch takes.
+    bool add(const uint8_t *buf, const csadev::Slice &sl, uint64_t at, uint64_t size, uint64_t out, uint64_t expect)
+    {
+        const uint64_t first = leaves.size(), n = std::max<uint64_t>(csadev::piece_count(size, csadev::kDigestLeaf), 1);
+        if (first + n > 0x7FFFFFFFull || frags.size() >= 0x7FFFFFFFull) return false;
+        csadev::digest_split(buf, sl, at, size, [&](const csadev::DigestLeaf &l) { leaves.push_back(l); });
+        frags.push_back(csadev::DigestFrag{out, expect, (uint32_t)first, (uint32_t)n});
+        bytes += size;
+        return true;
+    }
+    // a fragment that lies at src, contiguous
+    bool add(const uint8_t *src, uint64_t size, uint64_t out, uint64_t expect)
+    {
+        return add(src, csadev::Slice{0, size, size, size ? 1u : 0u}, 0, size, out, expect);
+    }
+    // differs[i]: 1 where fragment i was compared and its digest is not the expected one.  ds is added to.  (The tables' bytes are
+    // in no statistic: the write's upload_bytes stays what it is without a digest table.)
+    bool run(DevTimer &tm, CSADevDigest *out, const CSADevDigest *expect, CSADevDigestStats &ds, std::vector<uint32_t> &differs)
+    {
+        differs.assign(frags.size(), 0);
+        if (frags.empty()) return true;
+        const uint32_t nl = (uint32_t)leaves.size(), nf = (uint32_t)frags.size();
+        DevBuf d_leaves, d_frags, d_dig, d_diff;
+        if (!d_leaves.upload(leaves.data(), nl * sizeof(csadev::DigestLeaf)) || !d_frags.upload(frags.data(), nf * sizeof(csadev::DigestFrag))
+            || !d_dig.alloc((uint64_t)nl * sizeof(csadev::DigestWords)) || !d_diff.alloc(nf * sizeof(uint32_t))) return false;
+        double ms[2] = {0, 0};
+        if (!tm.timed(&ms[0], ds.launches, [&] { launch_digest_leaves(d_leaves.p, d_dig.p, nl, tm.st); })
+            || !tm.timed(&ms[1], ds.launches, [&] { launch_digest_roots(d_frags.p, d_dig.p, out, expect, d_diff.p, nf, tm.st); })
+            || !HIP_OK(hipMemcpy(differs.data(), d_diff.p, nf * sizeof(uint32_t), hipMemcpyDeviceToHost))) return false;
+        g_digest_ms[0] += ms[0]; g_digest_ms[1] += ms[1];
+        ds.kernel_ms += ms[0] + ms[1];
+        ds.frags += nf; ds.leaves += nl; ds.digested_bytes += bytes;
+        for (uint32_t i = 0; i < nf; i++)
+            if (differs[i]) { ds.mismatches++; ds.first_mismatch = std::min<uint64_t>(ds.first_mismatch, frags[i].out); }
+        return true;
+    }
+};
+
+// what a call that digests hands down: the two tables (either may be NULL) and its statistics
+struct DigestCall { CSADevDigest *out; const CSADevDigest *expect; CSADevDigestStats ds; };
+
+bool ranges_meet(const void *a, uint64_t an, const void *b, uint64_t bn)
+{
+    const uint64_t a0 = (uint64_t)(uintptr_t)a, b0 = (uint64_t)(uintptr_t)b;
+    return an && bn && a && b && a0 <= b0 + (bn - 1) && b0 <= a0 + (an - 1);
+}
+
 // The coded streams of a wave's tasks, staged for CSCMI_DecodeDeviceBatch (csa_worker.cpp:59-90 for every task at once): one
 // k_gather_extents launch brings every task's 10 property bytes -- they may span archive blocks -- into a 16-byte slot, and the stream
 // of every task of more than one archive block into one piece of d_gat; a stream of one block is decoded where it lies.  The
@@ -477,6 +541,7 @@ struct ReadBufs {
     const csadev::Slice *bslices = nullptr;    // per entry, checked: what of the caller's buffer ptrs[i][0, bsizes[i]) is the entry's side -- the packed bytes it
     const uint64_t *bsizes = nullptr;          // selects take the entry (a layout with L.sliced: its packed slice); count 0: nothing, as where ptrs[i] is NULL
     CSADevSpreadStats *spread = nullptr;       // never null without L.sliced: the piece counts are added here
+    DigestCall *dg = nullptr;                  // CSAMI_DeviceReadDigests: every delivered fragment is also digested, and compared where dg->expect is given
     uint8_t *at(uint32_t file) const { return ptrs ? ptrs[file] : nullptr; }
 };
 
@@ -541,6 +606,7 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
     FragTables T(L.sliced ? FragTables::kSliced : FragTables::kSpread);
     std::vector<uint32_t> ff_file;
     std::vector<uint64_t> ff_posfile;
+    DigestPass DP;
     for (size_t k = 0; k < count; k++) {
         const DevTask &t = L.tasks[first + k];
         for (const DevFrag &f : t.frags) {
@@ -559,6 +625,7 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
                 return CSCMI_DEVICE_ERROR;
             ff_file.push_back(f.file);
             ff_posfile.push_back(f.posfile);
+            if (B.dg && !DP.add(src, n, f.idx, B.dg->expect ? f.idx : kDigestNone)) return CSCMI_DEVICE_ERROR;
         }
     }
     const LaunchSlot slot = {tm, &A.kernel_ms[1], &A.kernel_ms[2], S.launches};
@@ -578,8 +645,11 @@ int dev_read_wave(CSADevArchive &A, const DevLayout &L, size_t first, size_t cou
         if (!T.sum(slot, true, nullptr, res)) return CSCMI_DEVICE_ERROR;
         S.readback_bytes += res.size() * sizeof(FragResult);
     }
+    std::vector<uint32_t> differs(res.size(), 0);
+    if (B.dg && !DP.run(tm, B.dg->out, B.dg->expect, B.dg->ds, differs)) return CSCMI_DEVICE_ERROR;
+    if (B.dg) S.readback_bytes += differs.size() * sizeof(uint32_t);
     for (size_t i = 0; i < res.size(); i++)
-        if (!res[i].ok) {
+        if (!res[i].ok || differs[i]) {
             fprintf(stderr, "******** %s extraction/verify failed\n", L.files[ff_file[i]].it->first.c_str());   // csa_io.h:332,398
             failed[ff_file[i]]++;
             S.verify_failures++;
@@ -676,6 +746,20 @@ int dev_read_run(CSADevArchive *a, const DevLayout &L, const ReadBufs &B, const 
     if (!tm.ok) return CSCMI_DEVICE_ERROR;
     int worst = 0;
     S.readback_bytes = a->open_readback;
+    if (B.dg && !L.empty_idx.empty()) {                                       // the zero-size fragments: no task holds them
+        DigestPass DP;
+        std::vector<uint32_t> differs;
+        for (const auto &e : L.empty_idx)
+            if (!DP.add(nullptr, 0, e.first, B.dg->expect ? e.first : csadev::kDigestNone)) return CSCMI_DEVICE_ERROR;
+        if (!DP.run(tm, B.dg->out, B.dg->expect, B.dg->ds, differs)) return CSCMI_DEVICE_ERROR;
+        S.readback_bytes += differs.size() * sizeof(uint32_t);
+        for (size_t i = 0; i < differs.size(); i++)
+            if (differs[i]) {
+                fprintf(stderr, "******** %s extraction/verify failed\n", L.files[L.empty_idx[i].second].it->first.c_str());
+                failed[L.empty_idx[i].second]++;
+                S.verify_failures++;
+            }
+    }
     for (size_t first = 0; first < L.tasks.size() && worst != CSCMI_DEVICE_ERROR;) {
         // the task's decoded bytes and (at most) a copy of its stream, plus what its decoder holds
         // (stopped early: the decoded bytes are `stop`; the dictionary and the stream's copy are what they were)
@@ -970,6 +1054,40 @@ int CSAMI_DeviceReadSlices(CSADevArchive *a, const char *const *names, int nname
     });
 }
 
+int CSAMI_DeviceReadDigests(CSADevArchive *a, const CSAOptions *opt, CSADevDigest *digests_out, uint64_t digests_cap, const CSADevDigest *expect,
+                            CSADevReadStats *st, CSADevDigestStats *ds)
+{
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
+    DigestCall dg = {digests_out, expect, CSADevDigestStats()};
+    memset(&dg.ds, 0, sizeof(dg.ds));
+    g_digest_ms[0] = g_digest_ms[1] = 0;
+    if (ds) *ds = dg.ds;
+    std::vector<uint64_t> sizes;
+    std::vector<csadev::Slice> bs;
+    const ReadCall c = {a, nullptr, 0, opt, nullptr, 0, false, nullptr, false, false, false, st, nullptr};
+    const int rc = dev_read_call(c, (CSADevSpreadStats *)nullptr, [&](const DevLayout &L, ReadBufs &B, CSADevSpreadStats &X, bool &) {
+        const uint64_t bytes = L.index_frags * sizeof(CSADevDigest);
+        if ((!digests_out && !expect) || ranges_meet(digests_out, bytes, a->arc, a->arc_size) || ranges_meet(expect, bytes, a->arc, a->arc_size)
+            || ranges_meet(digests_out, bytes, expect, bytes)) return -1;
+        if (digests_out && digests_cap < L.index_frags) return WRITE_ERROR;
+        for (const DevFilePlan &f : L.files) {
+            sizes.push_back(f.size);
+            bs.push_back(whole_slice(f.size));
+        }
+        B.bslices = bs.data(); B.bsizes = sizes.data(); B.spread = &X;
+        B.dg = &dg;
+        dg.ds.first_mismatch = UINT64_MAX;
+        return 0;
+    });
+    if (ds) *ds = dg.ds;
+    return rc;
+}
+
+void CSAMI_DeviceDigestKernelMs(double ms[2])
+{
+    ms[0] = g_digest_ms[0]; ms[1] = g_digest_ms[1];
+}
+
 void CSAMI_DeviceKernelMs(const CSADevArchive *a, double ms[3])
 {
     for (int i = 0; i < 3; i++) ms[i] = a ? a->kernel_ms[i] : 0;
@@ -1071,6 +1189,8 @@ int CSAMI_PlanDeviceSlices(const uint8_t *raw_index, uint64_t raw_size, uint64_t
 // k_gather_extents; tables and walks: csa_dev_read.h, csa_dev_write.h) and in CSCMI_EncodeDeviceBatch.  All of them are one path
 // over a device pointer and a slice per entry (CSAMI_DeviceWriteSlices): CSAMI_DeviceWrite and CSAMI_DeviceWriteFrom hand in whole
 // entries; where a slice has rows, a task's fragments are gathered across the run borders by k_frag_rows.
+// CSAMI_DeviceUpdateDigests is that path with the fragment digests (csa_dev_digest.h): one DigestPass over the plan's fragments before the
+// waves, for the table the call hands out and for the comparison with the base's table under CSAMI_UPDATE_TRUST_DIGESTS.
 // CSAMI_DeviceUpdate is that path with a base archive: the tasks of the plan that are tasks of the base (update_candidates) and whose
 // bytes are still the base's (dev_check_wave) are placed from the base instead of encoded; CSAMI_DeviceWriteSlices is it without one.
 // ---------------------------------------------------------------------------------------------
@@ -1107,12 +1227,15 @@ struct UpdTask {
     bool candidate = false;                    // the host step found its base task, and no later step has ruled it out yet
     bool have_sums = false;                    // its fragments' checksums are the caller's bytes' (the check under TRUST_SUMS summed them)
     std::vector<uint32_t> base_sums;           // candidate: the base index's checksum of each of its fragments, in the task's order
+    std::vector<uint64_t> base_pos;            //            and each one's place in the base index (= in the base's digest table)
+    bool digest_changed = false;               // CSAMI_UPDATE_TRUST_DIGESTS: a fragment's digest is not the base table's
     std::vector<Extent> ext;                   // candidate: the base stream's archive blocks, clipped to the base buffer
     uint64_t stream = 0;                       //            and their bytes, the 10 property bytes included
 };
 struct UpdateCtx {
     CSADevArchive *base = nullptr;
-    bool trust = false;
+    bool trust = false;                        // nothing is decoded: CSAMI_UPDATE_TRUST_SUMS, CSAMI_UPDATE_TRUST_DIGESTS
+    bool digests = false;                      // CSAMI_UPDATE_TRUST_DIGESTS: the digest pass decides, the base's checksums decide nothing
     std::vector<UpdTask> tasks;
     CSADevUpdateStats U;
     double ms = 0;                             // HIP-event time of the check waves' launches
@@ -1123,19 +1246,23 @@ struct UpdateCtx {
 // it holds a byte and the set of its fragments (name, offset in the entry, size, posblock) is the set of ALL fragments of the base
 // index with that bid; UINT64_MAX where there is none.  One map from (name, offset) to the base's fragments there, one look per
 // fragment of the plan: no task is compared with another.  Sets posblock of every fragment of the plan (csa_io.h:239); sums[i]
-// gets the base's checksums of a candidate's fragments, in the task's order.  Returns the number of candidates.
-uint32_t update_candidates(const Index &base, AddPlan &P, std::vector<uint64_t> &bids, std::vector<std::vector<uint32_t>> &sums)
+// gets the base's checksums of a candidate's fragments, in the task's order, and pos[i] (pos != NULL) their places in the base index.
+// Returns the number of candidates.
+uint32_t update_candidates(const Index &base, AddPlan &P, std::vector<uint64_t> &bids, std::vector<std::vector<uint32_t>> &sums,
+                           std::vector<std::vector<uint64_t>> *pos = nullptr)
 {
-    struct BaseFrag { uint64_t bid, size, posblock; uint32_t checksum; };
+    struct BaseFrag { uint64_t bid, size, posblock; uint32_t checksum; uint64_t idx; };
+    uint64_t idx = 0;
     std::map<std::pair<std::string, uint64_t>, std::vector<BaseFrag>> where;
     std::map<uint64_t, uint64_t> nfrags;
     for (const auto &kv : base)
         for (const CSAFrag &f : kv.second.frags) {
-            where[std::make_pair(kv.first, (uint64_t)f.posfile)].push_back(BaseFrag{f.bid, f.size, f.posblock, f.checksum});
+            where[std::make_pair(kv.first, (uint64_t)f.posfile)].push_back(BaseFrag{f.bid, f.size, f.posblock, f.checksum, idx++});
             nfrags[f.bid]++;
         }
     bids.assign(P.tasks.size(), UINT64_MAX);
     sums.assign(P.tasks.size(), std::vector<uint32_t>());
+    if (pos) pos->assign(P.tasks.size(), std::vector<uint64_t>());
     uint32_t n = 0;
     for (size_t ti = 0; ti < P.tasks.size(); ti++) {
         Task &t = P.tasks[ti];
@@ -1144,6 +1271,7 @@ uint32_t update_candidates(const Index &base, AddPlan &P, std::vector<uint64_t> 
         if (!t.total) continue;
         uint64_t bid = UINT64_MAX;
         std::vector<uint32_t> cs;
+        std::vector<uint64_t> at;
         for (const FilePiece &f : t.files) {
             const BaseFrag *hit = nullptr;
             auto w = where.find(std::make_pair(f.it->first, f.off));
@@ -1153,10 +1281,12 @@ uint32_t update_candidates(const Index &base, AddPlan &P, std::vector<uint64_t> 
             if (!hit) break;
             bid = hit->bid;
             cs.push_back(hit->checksum);
+            at.push_back(hit->idx);
         }
         if (cs.size() != t.files.size() || nfrags[bid] != t.files.size()) continue;
         bids[ti] = bid;
         sums[ti].swap(cs);
+        if (pos) (*pos)[ti].swap(at);
         n++;
     }
     return n;
@@ -1524,7 +1654,7 @@ int dev_check_wave(WriteCtx &W, UpdateCtx &U, AddPlan &P, const std::vector<size
         std::vector<FragResult> res;
         if (!T.sum(slot, true, &W.S.upload_bytes, res)) return CSCMI_DEVICE_ERROR;
         W.S.readback_bytes += res.size() * sizeof(FragResult);
-        for (size_t i = 0; i < res.size(); i++) { ff_piece[i]->checksum = res[i].adler; differs[i] = !res[i].ok; }
+        for (size_t i = 0; i < res.size(); i++) { ff_piece[i]->checksum = res[i].adler; differs[i] = !U.digests && !res[i].ok; }
     } else {
         std::vector<FragDiff> rd;
         if (!T.compare(slot, &W.S.upload_bytes, rd)) return CSCMI_DEVICE_ERROR;
@@ -1536,6 +1666,7 @@ int dev_check_wave(WriteCtx &W, UpdateCtx &U, AddPlan &P, const std::vector<size
         if (differs[i]) { UpdTask &u = U.tasks[ff_task[i]]; u.candidate = false; u.status = CSA_UPD_CHANGED; }
     for (size_t k = 0; k < count; k++) {
         UpdTask &u = U.tasks[cand[first + k]];
+        if (U.digests && u.candidate && u.digest_changed) { u.candidate = false; u.status = CSA_UPD_CHANGED; }
         if (u.candidate) u.status = CSA_UPD_REUSED;
         else if (U.trust && u.status == CSA_UPD_CHANGED) u.have_sums = true;
         u.candidate = false;
@@ -1543,9 +1674,119 @@ int dev_check_wave(WriteCtx &W, UpdateCtx &U, AddPlan &P, const std::vector<size
     return 0;
 }
 
+// What the write, the update and CSAMI_DeviceDigestSlices refuse in the caller's sources (-1): the slices, each inside its buffer and
+// selecting exactly its entry's bytes; sl[i] is entry i's checked slice, and hull[i] / hull_size[i] its hull, which is all that is
+// loaded (slices == NULL: every entry whole -- all of a buffer of esize bytes).  G gets the selected and the hull bytes.
+int check_sources(const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices, const CSADevFile *files, uint32_t n_files,
+                  std::vector<csadev::Slice> &sl, std::vector<const void *> &hull, std::vector<uint64_t> &hull_size, CSADevGatherStats &G)
+{
+    sl.assign(n_files, csadev::Slice{0, 0, 0, 0});
+    hull.assign(n_files, nullptr);
+    hull_size.assign(n_files, 0);
+    for (uint32_t i = 0; i < n_files; i++) {
+        const uint64_t esize = (uint64_t)files[i].esize;                     // (plan_write: not negative)
+        sl[i] = slices ? dev_slice(slices[i]) : whole_slice(esize);
+        uint64_t bytes, at;
+        if (!csadev::slice_check(sl[i], slices ? sizes[i] : esize, &bytes) || bytes != esize) return -1;
+        if (!sl[i].count) continue;
+        if (!ptrs[i] || !add_ok((uintptr_t)ptrs[i], sl[i].offset, &at)) return -1;
+        hull[i] = (const void *)(uintptr_t)at;
+        hull_size[i] = (sl[i].count - 1) * sl[i].stride + sl[i].run;         // (checked by slice_check)
+        G.selected_bytes += bytes;                                           // (plan_write: the sizes sum to at most 2^60)
+        if (!add_ok(G.hull_bytes, hull_size[i], &G.hull_bytes)) return -1;
+    }
+    return 0;
+}
+
+// Where each fragment of the plan will stand in the index the write packs -- the entries in name order, an entry's fragments in the
+// order the tasks hand them out (csarc.cpp:371-386) -- and so in the digest table: place[task][piece].  Returns their number.
+uint64_t plan_frag_places(AddPlan &P, std::vector<std::vector<uint64_t>> &place)
+{
+    std::map<const Entry *, uint64_t> count, first;
+    for (const Task &t : P.tasks)
+        for (const FilePiece &f : t.files) count[&f.it->second]++;
+    uint64_t n = 0;
+    for (const auto &kv : P.index) { first[&kv.second] = n; n += count[&kv.second]; }
+    place.assign(P.tasks.size(), std::vector<uint64_t>());
+    for (size_t ti = 0; ti < P.tasks.size(); ti++)
+        for (const FilePiece &f : P.tasks[ti].files) place[ti].push_back(first[&f.it->second]++);
+    return n;
+}
+
+// The digest pass of a write, an update or CSAMI_DeviceDigestSlices: with `all`, every fragment of the plan where it lies in the
+// caller's buffers, its digest to out[place] (out == NULL: nowhere); else the candidates' alone.  A candidate's fragments are compared
+// with `expect` at their places in the base index (U == NULL or expect == NULL: nothing is compared), and a candidate one of whose
+// fragments differs is marked.  0 or CSCMI_DEVICE_ERROR.
+int dev_digest_plan(AddPlan &P, const void *const *ptrs, const csadev::Slice *slices, const std::vector<std::vector<uint64_t>> &place, bool all,
+                    UpdateCtx *U, DevTimer &tm, DigestCall &dg)
+{
+    DigestPass DP;
+    std::vector<size_t> ff_task;
+    for (size_t ti = 0; ti < P.tasks.size(); ti++) {
+        const bool compared = U && dg.expect && U->tasks[ti].candidate;
+        if (!all && !compared) continue;
+        size_t fi = 0;
+        for (const FilePiece &f : P.tasks[ti].files) {
+            const uint32_t row = f.it->second.row;
+            if (!DP.add((const uint8_t *)ptrs[row], slices[row], f.off, f.size, place[ti][fi], compared ? U->tasks[ti].base_pos[fi] : csadev::kDigestNone))
+                return CSCMI_DEVICE_ERROR;
+            ff_task.push_back(ti);
+            fi++;
+        }
+    }
+    std::vector<uint32_t> differs;
+    if (!DP.run(tm, dg.out, dg.expect, dg.ds, differs)) return CSCMI_DEVICE_ERROR;
+    for (size_t i = 0; i < differs.size(); i++)
+        if (differs[i]) U->tasks[ff_task[i]].digest_changed = true;
+    return 0;
+}
+
 }   // namespace
 
 extern "C" {
+
+int CSAMI_DeviceWriteFragCount(const CSADevFile *files, uint32_t n_files, const char *arcname, const CSAOptions *opt, uint64_t *n_frags)
+{
+    (void)arcname;
+    AddPlan P;
+    const int rc = plan_write(P, files, n_files, opt, nullptr);
+    if (rc == -1) return -1;
+    uint64_t n = 0;
+    for (const Task &t : P.tasks) n += t.files.size();
+    if (n_frags) *n_frags = n;
+    return rc;
+}
+
+int CSAMI_DeviceDigestSlices(const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices, const CSADevFile *files, uint32_t n_files,
+                             const char *arcname, const CSAOptions *opt, CSADevDigest *digests_out, uint64_t digests_cap, CSADevDigestStats *ds)
+{
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
+    DigestCall dg = {digests_out, nullptr, CSADevDigestStats()};
+    memset(&dg.ds, 0, sizeof(dg.ds));
+    g_digest_ms[0] = g_digest_ms[1] = 0;
+    if (ds) *ds = dg.ds;
+    if (!arcname || (n_files && (!ptrs || !files || !sizes != !slices))) return -1;
+    AddPlan P;
+    int rc = plan_write(P, files, n_files, opt, nullptr);
+    if (rc) return rc;
+    std::vector<csadev::Slice> sl;
+    std::vector<const void *> hull;
+    std::vector<uint64_t> hull_size;
+    std::vector<std::vector<uint64_t>> place;
+    CSADevGatherStats G;
+    memset(&G, 0, sizeof(G));
+    if (check_sources(ptrs, sizes, slices, files, n_files, sl, hull, hull_size, G) != 0) return -1;
+    const uint64_t n_frags = plan_frag_places(P, place);
+    if ((n_frags && !digests_out) || CSAMI_CheckBuffers(hull.data(), hull_size.data(), n_files, digests_out, n_frags * sizeof(CSADevDigest), 0, nullptr) != 0)
+        return -1;
+    if (digests_cap < n_frags) return WRITE_ERROR;
+    DevTimer tm;
+    if (!tm.ok) return CSCMI_DEVICE_ERROR;
+    dg.ds.first_mismatch = UINT64_MAX;
+    rc = dev_digest_plan(P, ptrs, sl.data(), place, true, nullptr, tm, dg);
+    if (ds) *ds = dg.ds;
+    return rc;
+}
 
 int CSAMI_DeviceWritePlan(const CSADevFile *files, uint32_t n_files, const char *arcname, const CSAOptions *opt,
                           uint32_t *n_tasks, uint32_t *max_frags, uint64_t *raw_bytes)
@@ -1613,16 +1854,30 @@ int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint6
                        CSADevWriteStats *st, CSADevGatherStats *gather_stats, CSADevUpdateStats *update_stats, CSADevUpdateTask *tasks,
                        uint32_t task_cap)
 {
+    return CSAMI_DeviceUpdateDigests(base, nullptr, 0, ptrs, sizes, slices, files, n_files, arcname, arc_dev, arc_cap, flags, opt, st, gather_stats,
+                                     update_stats, tasks, task_cap, nullptr, 0, nullptr);
+}
+
+int CSAMI_DeviceUpdateDigests(CSADevArchive *base, const CSADevDigest *base_digests, uint64_t n_base_digests, const void *const *ptrs,
+                              const uint64_t *sizes, const CSADevSlice *slices, CSADevFile *files, uint32_t n_files, const char *arcname,
+                              void *arc_dev, uint64_t arc_cap, uint32_t flags, const CSAOptions *opt, CSADevWriteStats *st,
+                              CSADevGatherStats *gather_stats, CSADevUpdateStats *update_stats, CSADevUpdateTask *tasks, uint32_t task_cap,
+                              CSADevDigest *digests_out, uint64_t digests_cap, CSADevDigestStats *ds)
+{
     const double t0 = now_s();
     if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
     WriteCtx W;
     UpdateCtx U;
+    DigestCall dg = {digests_out, base_digests, CSADevDigestStats()};
     memset(&W.S, 0, sizeof(W.S));
     memset(&W.G, 0, sizeof(W.G));
     memset(&U.U, 0, sizeof(U.U));
+    memset(&dg.ds, 0, sizeof(dg.ds));
+    g_digest_ms[0] = g_digest_ms[1] = 0;
     if (st) *st = W.S;
     if (gather_stats) *gather_stats = W.G;
     if (update_stats) *update_stats = U.U;
+    if (ds) *ds = dg.ds;
     for (double &m : g_write_ms) m = 0;
     // ---- everything the host can refuse, before any launch
     uint64_t a1;
@@ -1632,28 +1887,37 @@ int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint6
     if (rc) return rc;
     // the slices, each inside its buffer and selecting exactly its entry's bytes; the hulls, which are all that is loaded
     // (slices == NULL: every entry whole -- all of a buffer of esize bytes)
-    std::vector<csadev::Slice> sl(n_files);
-    std::vector<const void *> hull(n_files, nullptr);
-    std::vector<uint64_t> hull_size(n_files, 0);
+    std::vector<csadev::Slice> sl;
+    std::vector<const void *> hull;
+    std::vector<uint64_t> hull_size;
     CSADevGatherStats G = W.G;
-    for (uint32_t i = 0; i < n_files; i++) {
-        const uint64_t esize = (uint64_t)files[i].esize;                     // (plan_write: not negative)
-        sl[i] = slices ? dev_slice(slices[i]) : whole_slice(esize);
-        uint64_t bytes, at;
-        if (!csadev::slice_check(sl[i], slices ? sizes[i] : esize, &bytes) || bytes != esize) return -1;
-        if (!sl[i].count) continue;
-        if (!ptrs[i] || !add_ok((uintptr_t)ptrs[i], sl[i].offset, &at)) return -1;
-        hull[i] = (const void *)(uintptr_t)at;
-        hull_size[i] = (sl[i].count - 1) * sl[i].stride + sl[i].run;         // (checked by slice_check)
-        G.selected_bytes += bytes;                                           // (plan_write: the sizes sum to at most 2^60)
-        if (!add_ok(G.hull_bytes, hull_size[i], &G.hull_bytes)) return -1;
-    }
+    if (check_sources(ptrs, sizes, slices, files, n_files, sl, hull, hull_size, G) != 0) return -1;
     if (CSAMI_CheckBuffers(hull.data(), hull_size.data(), n_files, arc_dev, arc_cap, 0, nullptr) != 0) return -1;
     if (base && arc_cap && base->arc_size) {                                 // the base is read while arc is written: updating in place is out of scope
         const uint64_t b0 = (uint64_t)(uintptr_t)base->arc, x0 = (uint64_t)(uintptr_t)arc_dev;
         if (x0 <= b0 + (base->arc_size - 1) && b0 <= x0 + (arc_cap - 1)) return -1;
     }
-    if (arc_cap < kHeaderSize) return WRITE_ERROR;
+    // the digest tables: the flags, the base table's length, and where the two lie
+    std::vector<std::vector<uint64_t>> place;
+    const uint64_t n_frags = plan_frag_places(P, place);
+    const uint64_t out_bytes = digests_out ? n_frags * sizeof(CSADevDigest) : 0, base_bytes = base_digests ? n_base_digests * sizeof(CSADevDigest) : 0;
+    U.digests = (flags & CSAMI_UPDATE_TRUST_DIGESTS) != 0;
+    if (U.digests && ((flags & CSAMI_UPDATE_TRUST_SUMS) || !base_digests)) return -1;
+    if (base && base_digests) {
+        uint64_t nb = 0;
+        for (const auto &kv : base->index) nb += kv.second.frags.size();
+        if (n_base_digests != nb) return -1;
+    }
+    for (int k = 0; k < 2; k++) {
+        const void *tp = k ? (const void *)base_digests : (const void *)digests_out;
+        const uint64_t tb = k ? base_bytes : out_bytes;
+        if (!tb) continue;
+        if (ranges_meet(tp, tb, arc_dev, arc_cap) || (base && ranges_meet(tp, tb, base->arc, base->arc_size))
+            || CSAMI_CheckBuffers(hull.data(), hull_size.data(), n_files, tp, tb, 0, nullptr) != 0) return -1;
+    }
+    if (ranges_meet(digests_out, out_bytes, base_digests, base_bytes)) return -1;
+    if (arc_cap < kHeaderSize || (digests_out && digests_cap < n_frags)) return WRITE_ERROR;
+    dg.ds.first_mismatch = UINT64_MAX;
     if (const char *e = getenv("CSA_DEVWRITE_SLACK")) { W.slack = (int64_t)strtoull(e, nullptr, 10); if (W.slack < 0) W.slack = -1; }
     W.ptrs = ptrs; W.slices = sl.data(); W.arc = (uint8_t *)arc_dev; W.arc_cap = arc_cap;
     W.G = G;
@@ -1668,11 +1932,12 @@ int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint6
         const double tc = now_s();
         W.upd = &U;
         U.base = base;
-        U.trust = (flags & CSAMI_UPDATE_TRUST_SUMS) != 0;
+        U.trust = (flags & (CSAMI_UPDATE_TRUST_SUMS | CSAMI_UPDATE_TRUST_DIGESTS)) != 0;
         U.tasks.resize(P.tasks.size());
         std::vector<uint64_t> bids;
         std::vector<std::vector<uint32_t>> sums;
-        U.U.candidates = update_candidates(base->index, P, bids, sums);
+        std::vector<std::vector<uint64_t>> pos;
+        U.U.candidates = update_candidates(base->index, P, bids, sums, &pos);
         static const std::vector<Extent> kNoBlocks;
         std::vector<size_t> cand;
         for (size_t i = 0; i < P.tasks.size(); i++) {
@@ -1681,9 +1946,15 @@ int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint6
             u.base_bid = bids[i];
             u.candidate = true;
             u.base_sums.swap(sums[i]);
+            u.base_pos.swap(pos[i]);
             auto ab = base->abindex.find(bids[i]);
             if (!dev_stream_extents(ab == base->abindex.end() ? kNoBlocks : ab->second, base->arc_size, u.ext, u.stream)) return CSCMI_DEVICE_ERROR;
             cand.push_back(i);
+        }
+        // the digest pass: every fragment of the plan for the table this call hands out, the candidates' against the base table
+        if (digests_out || U.digests) {
+            if (!U.digests) dg.expect = nullptr;
+            rc = dev_digest_plan(P, ptrs, sl.data(), place, digests_out != nullptr, &U, W.tm, dg);
         }
         // waves as CSAMI_DeviceRead sizes them (a wave that only sums holds no decoder and no scratch)
         const size_t cwidth = P.o.device_streams > 0 ? (size_t)P.o.device_streams : std::max<size_t>(cand.size(), 1);
@@ -1701,6 +1972,9 @@ int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint6
         }
         U.U.check_kernel_ms = U.ms;
         U.U.seconds_check = now_s() - tc;
+    } else if (digests_out) {
+        dg.expect = nullptr;
+        rc = dev_digest_plan(P, ptrs, sl.data(), place, true, nullptr, W.tm, dg);
     }
 
     // ---- waves of consecutive task ids, largest first (csarc.cpp:355): the plan's order and the archive's
@@ -1773,6 +2047,7 @@ int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint6
     if (st) *st = W.S;
     if (gather_stats) *gather_stats = W.G;
     if (update_stats) *update_stats = U.U;
+    if (ds) *ds = dg.ds;
     return rc;
 }
 

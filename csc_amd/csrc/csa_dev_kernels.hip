@@ -24,6 +24,10 @@
 //   k_frag_compare_rows   k_frag_compare for CSAMI_DeviceCompareSlices: the piece against such rows instead of one range
 //   k_block_table         one lane per task stream of a wave (write only): the archive-block table AsyncWriter would have made of
 //                         the encoder's Write calls (csa_io.h:145-201), read off the stream's framing (csa_dev_write.h)
+//   k_digest_leaves       one LANE per <= 16 KiB leaf of a fragment: its BLAKE2s tree-mode leaf digest (csa_dev_digest.h) -- a leaf is a
+//                         serial chain of up to 256 compressions, so the parallelism is across leaves
+//   k_digest_roots        one lane per fragment: the root over its leaves' digests, stored to the digest table and compared with an
+//                         expected table where one is given; one word a fragment is all the host reads back
 //
 // Every address in the tables was validated by the host before the launch; a workgroup touches src[0, len) and dst[0, len) of its
 // piece and nothing else.
@@ -32,6 +36,7 @@
 
 #include "csa_dev_read.h"
 #include "csa_dev_write.h"
+#include "csa_dev_digest.h"
 
 using namespace csadev;
 
@@ -275,4 +280,36 @@ void launch_block_table(const void *jobs, uint32_t njobs, void *scratch, void *r
 {
     hipLaunchKernelGGL(k_block_table, dim3(1), dim3(kTableThreads), 0, st, (const BlockTableJob *)jobs, njobs, (uint64_t *)scratch,
                        (BlockTableRes *)res, (uint64_t *)sizes);
+}
+
+// One lane per leaf.  The chaining value, one message block and the working vector live in registers (no scratch); a lane loads
+// its own 64-byte blocks, 16 KiB from its neighbours'.
+__global__ __launch_bounds__(kDigestThreads) void k_digest_leaves(const DigestLeaf *leaves, DigestWords *out, uint32_t nleaves)
+{
+    const uint32_t i = blockIdx.x * kDigestThreads + threadIdx.x;
+    if (i >= nleaves) return;
+    const DigestLeaf lf = leaves[i];
+    DigestWords d;
+    digest_leaf(lf, d);
+    out[i] = d;
+}
+
+__global__ __launch_bounds__(kDigestThreads) void k_digest_roots(const DigestFrag *frags, const DigestWords *leaves, uint8_t *out, const uint8_t *expect,
+                                                                 uint32_t *differs, uint32_t nfrags)
+{
+    const uint32_t i = blockIdx.x * kDigestThreads + threadIdx.x;
+    if (i >= nfrags) return;
+    differs[i] = digest_root(frags[i], leaves, out, expect);
+}
+
+void launch_digest_leaves(const void *leaves, void *out, uint32_t nleaves, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_digest_leaves, dim3(nleaves ? (nleaves + kDigestThreads - 1) / kDigestThreads : 1), dim3(kDigestThreads), 0, st,
+                       (const DigestLeaf *)leaves, (DigestWords *)out, nleaves);
+}
+
+void launch_digest_roots(const void *frags, const void *leaves, void *out, const void *expect, void *differs, uint32_t nfrags, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_digest_roots, dim3(nfrags ? (nfrags + kDigestThreads - 1) / kDigestThreads : 1), dim3(kDigestThreads), 0, st,
+                       (const DigestFrag *)frags, (const DigestWords *)leaves, (uint8_t *)out, (const uint8_t *)expect, (uint32_t *)differs, nfrags);
 }

@@ -23,6 +23,8 @@ void launch_frag_spread(const void *pieces, void *sums, uint32_t npieces, hipStr
 void launch_frag_compare_rows(const void *pieces, void *sums, void *firsts, uint32_t npieces, hipStream_t st);
 void launch_frag_fold(const void *frags, const void *sums, void *out, uint32_t nfrags, hipStream_t st);
 void launch_frag_fold_diff(const void *frags, const void *sums, const void *firsts, void *out, uint32_t nfrags, hipStream_t st);
+void launch_digest_leaves(const void *leaves, void *out, uint32_t nleaves, hipStream_t st);
+void launch_digest_roots(const void *frags, const void *leaves, void *out, const void *expect, void *differs, uint32_t nfrags, hipStream_t st);
 void launch_block_table(const void *jobs, uint32_t njobs, void *scratch, void *res, void *sizes, hipStream_t st);
 
 #define HIP_OK(x) ((x) == hipSuccess)

@@ -621,8 +621,7 @@ int CSAMI_DeviceCompareSlices(CSADevArchive *a, const char *const *names, int nn
  * walk finds a reused stream that does not end at its length the call returns -1 (in verify: unreachable for an intact decoder).
  * gather_stats and st->retries count encoded tasks only; st->tasks, frags, blocks, raw_bytes and archive_bytes mean what they mean
  * for the write.  tasks[i], i < min(task_cap, st->tasks), says what became of task i of the new plan.
- * Out of scope: updating in place (arc inside the base buffer), reusing part of a task, the host paths, and a strong hash in the
- * place of adler32. */
+ * Out of scope: updating in place (arc inside the base buffer), reusing part of a task, and the host paths. */
 #define CSAMI_UPDATE_TRUST_SUMS 1u
 typedef struct CSADevUpdateTask { uint64_t base_bid; uint32_t status; uint32_t reserved; } CSADevUpdateTask;   /* per task of the NEW plan, in id order */
 /* status */
@@ -649,6 +648,85 @@ int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint6
  * CSA_TOO_MANY_FRAGMENTS as there. */
 int CSAMI_PlanDeviceUpdate(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const CSADevFile *files, uint32_t n_files,
                            const CSAOptions *o, uint64_t *base_bids, uint32_t cap, uint32_t *n_tasks, uint32_t *n_candidates);
+
+/* ---- fragment digests: a strong hash beside adler32, so that an update can trust and not decode; not in the reference ----
+ *
+ * CSAMI_UPDATE_TRUST_SUMS rests on the format's own 32-bit sum, and the `.csa` has to stay byte for byte `csarc a -t1`'s, so a
+ * stronger hash cannot go into the archive.  It goes into a side table in HBM: one 32-byte digest per fragment of the index, in
+ * INDEX ORDER -- the entries in byte-wise name order, the fragments of an entry as CSA_List reports them (offset order), zero-size
+ * fragments included.  Every write and update can produce the table; the next update consumes it in the place of a decode.
+ *
+ * The digest of a fragment of n bytes is BLAKE2s-256 in tree mode, unkeyed, no salt, no personalisation: fan-out 0, maximal depth
+ * 2, leaf length 16384, inner length 32, digest length 32.  L = max(1, ceil(n / 16384)) leaves; leaf i is the fragment's packed
+ * bytes [16384 i, min(n, 16384 (i + 1))), hashed with node offset i, node depth 0 and the last-node flag on leaf L - 1 only; the root
+ * is hashed over the L leaf digests, node offset 0, node depth 1, last-node flag set.  A fragment of size 0 is one empty leaf.
+ * Python: hashlib.blake2s(leaf, digest_size=32, fanout=0, depth=2, leaf_size=16384, inner_size=32, node_offset=i, node_depth=0,
+ * last_node=(i == L - 1)), and the same call over the leaf digests with node_depth=1, node_offset=0, last_node=True
+ * (csc_amd.csa.fragment_digest).  The leaf grid is the 16 KiB grid of the piece tables.
+ *
+ * Kernels (csa_dev_digest.h, csa_dev_kernels.hip).  k_digest_leaves: one lane per leaf -- a leaf is a serial chain of up to 256
+ * compressions, so the parallelism is across leaves -- over a table of 40 bytes a leaf.  A source is contiguous bytes at any
+ * alignment, or the runs of a periodic slice, digested straight from the runs (no packed copy is made); nothing outside the
+ * fragment's bytes is loaded, not even by an aligned window, and no gap byte.  k_digest_roots: one lane per fragment over its
+ * leaves' digests; it stores the digest to the table and, where an expected table is given, compares the 32 bytes on the device.
+ * One word a fragment is read back; no digest byte crosses the bus in either direction.  Both tables may have any alignment.
+ * A call digests all its fragments in one leaf launch and one root launch, whatever the number of waves: ds->launches, never
+ * st->launches -- every existing statistic is what it is without the tables.
+ *
+ * What CSAMI_UPDATE_TRUST_DIGESTS still trusts: that the base's streams are intact, as under CSAMI_UPDATE_TRUST_SUMS -- the table
+ * speaks about the bytes the streams were made from, not about the streams; CSAMI_DeviceReadDigests checks them once -- and that
+ * the base was written at this call's level. */
+typedef struct CSADevDigest { uint8_t b[32]; } CSADevDigest;
+typedef struct CSADevDigestStats {
+    uint64_t frags, leaves, digested_bytes;   /* what the digest kernels ran over */
+    uint64_t launches;                        /* theirs: two a pass */
+    uint64_t mismatches;                      /* compared fragments whose digest differs from the expected table's */
+    uint64_t first_mismatch;                  /* the lowest index, in the table this call writes (or would write), of such a fragment; UINT64_MAX: none */
+    double kernel_ms;
+} CSADevDigestStats;
+#define CSAMI_UPDATE_TRUST_DIGESTS 2u
+/* host only, no GPU: the fragments, and so the table entries, that a write of this table makes.  Refusals: CSAMI_DeviceWritePlan's. */
+int CSAMI_DeviceWriteFragCount(const CSADevFile *files, uint32_t n_files, const char *arcname, const CSAOptions *o, uint64_t *n_frags);
+/* The table a write of these entries would produce, with nothing written and nothing encoded.  Arguments and refusals are
+ * CSAMI_DeviceWriteSlices's minus the archive (sizes == slices == NULL: every entry whole); -1 also where digests_out overlaps a
+ * hull or is NULL with fragments to digest; digests_cap (entries) < the fragment count: WRITE_ERROR with nothing launched. */
+int CSAMI_DeviceDigestSlices(const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices, const CSADevFile *files,
+                             uint32_t n_files, const char *arcname, const CSAOptions *o, CSADevDigest *digests_out, uint64_t digests_cap,
+                             CSADevDigestStats *ds);
+/* CSAMI_DeviceUpdate with the tables: CSAMI_DeviceUpdate IS this call with both tables NULL, so there stays one write path; with
+ * base == NULL it is CSAMI_DeviceWriteSlices that also hands out the table.
+ * digests_out (may be NULL; digests_cap entries): the table of the archive this call writes, always computed in this call from the
+ * caller's bytes, never copied from the base table.  The archive bytes and every statistic of st, gather_stats and update_stats
+ * are exactly what the call without it gives.
+ * base_digests (may be NULL; n_base_digests entries): the table of `base`, as the call that wrote the base or
+ * CSAMI_DeviceReadDigests handed it out.
+ * CSAMI_UPDATE_TRUST_DIGESTS: nothing is decoded.  Each candidate's fragments are digested where they lie and compared on the device
+ * with base_digests at the base fragments' index positions; reused means every fragment's digest is equal, else the task is
+ * CSA_UPD_CHANGED.  The check waves are CSAMI_UPDATE_TRUST_SUMS's (the property bytes, the sum pass, the fold: the new index's
+ * checksums of reused fragments are still sums taken in this call, not the base's), except that the base index's checksums decide
+ * nothing.  ds->mismatches counts the candidates' fragments whose digest differs.
+ * Refused with -1, nothing launched and all statistics zeroed, besides what CSAMI_DeviceUpdate refuses: both trust flags;
+ * TRUST_DIGESTS with base_digests == NULL; base and base_digests given and n_base_digests other than the base index's fragment
+ * count; either table overlapping arc, the base buffer, a caller's hull or the other table.  digests_cap < the plan's fragment
+ * count returns WRITE_ERROR before any launch. */
+int CSAMI_DeviceUpdateDigests(CSADevArchive *base, const CSADevDigest *base_digests, uint64_t n_base_digests,
+                              const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices,
+                              CSADevFile *files, uint32_t n_files, const char *arcname, void *arc_dev, uint64_t arc_cap,
+                              uint32_t flags, const CSAOptions *o, CSADevWriteStats *st, CSADevGatherStats *gather_stats,
+                              CSADevUpdateStats *update_stats, CSADevUpdateTask *tasks, uint32_t task_cap,
+                              CSADevDigest *digests_out, uint64_t digests_cap, CSADevDigestStats *ds);
+/* `csarc t` of the whole archive (no selection) that also writes the table of the decoded fragments: how an archive that comes from
+ * disk enters the chain, and how a base's streams are checked once.  It is CSAMI_DeviceRead with dst == NULL, wave for wave, with a
+ * digest pass over each wave's delivered fragments (and one over the zero-size fragments, which no task holds); a fragment none
+ * of whose bytes was delivered is neither digested nor compared, as it is not summed.  digests_out may be NULL (compare only).
+ * expect (may be NULL): a table of the archive's fragment count; every digested fragment is compared with it, mismatches are counted
+ * in ds, and for the return value, st->verify_failures and the entry's failed fragments a mismatch counts exactly as a failed
+ * checksum of that fragment does (a fragment that fails both counts once).  -1 with nothing launched: a NULL, a table overlapping
+ * the archive or the other table; digests_cap < the archive's fragment count: WRITE_ERROR with nothing launched. */
+int CSAMI_DeviceReadDigests(CSADevArchive *a, const CSAOptions *o, CSADevDigest *digests_out, uint64_t digests_cap,
+                            const CSADevDigest *expect, CSADevReadStats *st, CSADevDigestStats *ds);
+/* HIP-event milliseconds of this thread's last digesting call by kernel: [0] k_digest_leaves, [1] k_digest_roots; ds->kernel_ms is their sum */
+void CSAMI_DeviceDigestKernelMs(double ms[2]);
 
 /* YYYYMMDDHHMMSS <-> time_t, csa_common.cpp:3-39 */
 int64_t CSA_DecimalTime(int64_t unix_seconds);
