@@ -399,7 +399,7 @@ int write_arena(EncInstance *e, const uint8_t *h_arena, uint32_t used)
 
 int report_device_error(uint32_t err)
 {
-    // anything else is the watchdog of the multi-wavefront parser (csc_kernels_dp2.inc): the value says which wait gave up
+    // anything else is the watchdog of a many-wavefront form (d4_spin, bt_spin, hp_spin; ERR_QUEUE_STALL): the value says which wait gave up
     fprintf(stderr, "csc-mi355x: device encoder error 0x%x (%s)\n", err,
             err == ERR_ARENA_FULL ? "output arena exhausted" : err == ERR_BAD_TYPE ? "bad block type" : "parse wavefronts lost step");
     return CSCMI_DEVICE_ERROR;

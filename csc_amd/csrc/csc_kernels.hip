@@ -14,13 +14,15 @@
 //    fetches/updates its 8 probabilities in 8 lanes before the (serial)
 //    range-coder arithmetic.  Where the protocol leaves room, more wavefronts
 //    of the workgroup take part: the lazy levels run a parse wavefront feeding
-//    a coder wavefront through an LDS token ring (csc_kernels_lz.inc), the
-//    advanced parser of the hash-table levels runs up to four parse wavefronts
-//    that take the DP nodes of a window in turn (csc_kernels_dp2.inc).  Small
-//    adaptive tables, the DP nodes and the word trie live in LDS; window, hash
-//    tables / binary tree and p_lit live in HBM.  Independent streams (the
-//    archiver's -p / per-extension tasks) run as independent workgroups on
-//    other CUs / GPUs.
+//    a coder wavefront through an LDS token ring (csc_kernels_lz.inc), with an
+//    inserter wavefront ahead of it over a wide bucket (csc_kernels_hp.inc);
+//    the advanced parser runs as a pipeline of wavefront roles in the level-3
+//    geometry (csc_kernels_dp4.inc) and behind an inserter wavefront over the
+//    binary tree (csc_kernels_bt.inc), and as one wavefront a stream everywhere
+//    else.  Small adaptive tables, the DP nodes and the word trie live in LDS;
+//    window, hash tables / binary tree and p_lit live in HBM.  Independent
+//    streams (the archiver's -p / per-extension tasks) run as independent
+//    workgroups on other CUs / GPUs.
 //
 // No MFMA here: there is no dense contraction anywhere on this path.
 #include <hip/hip_runtime.h>
@@ -56,11 +58,13 @@ static __device__ __constant__ uint32_t d_logtable[513];
 __device__ static const uint32_t kDltIndex[5] = {1, 2, 3, 4, 8};   // csc_typedef.h:36
 
 // ------------------------------------------------------------------------------------------
-// LDS image of one stream while k_encode_runs is resident (< 40 KiB: four streams per CU fit in 160 KiB)
+// LDS image of one stream while k_encode_runs is resident: four streams per CU fit in its 160 KiB (static_assert below the struct)
+constexpr uint32_t kLdsPerCU = 160u * 1024u;
 constexpr uint32_t kTokRing = 2048;
-constexpr uint32_t kDpWaves = 4;          // parse wavefronts per stream the advanced parser can use (csc_kernels_dp2.inc)
-// Advanced parser on two parse wavefronts (csc_kernels_dp2.inc): what the wavefront that visited DP node k leaves for the
-// visitor of node k + 1, and the control words of a DP window.
+constexpr uint32_t kDpWaves = 4;          // rows of cd2 / rp42 (Sc::wv picks one): row 0 every parse wavefront (one-wavefront forms, the pipeline form's spine,
+                                          // the level-5 parser), row 2 the level-5 post wavefront; rows 1 and 3 have no user of their own (see cd2)
+// The turn-taking and chain forms of the advanced parser (rounds 1-5, retired in round 6): what the wavefront that visited DP node k left for the
+// visitor of node k + 1, and the control words of a DP window.  No code reads them any more; see EncLds::dp for why the bytes are still there.
 struct DpEdge {
     uint32_t lit, p1;          // price of reaching node k + 1 by a literal / by rep0len1 from node k (0xFFFFFFFF = no such edge)
     uint32_t state, reach;     // coder state of node k; max over visited j of j + longest candidate (the reference's apend - 1)
@@ -88,11 +92,11 @@ struct EncLds {
     uint32_t rep[4];                          // rep_dist_[4] (live)
     union {
         uint32_t cd2[kDpWaves][32];               // candidate distances of the position being searched: 0-3 rep, 4 HT2, 5 HT3, 6 BT head, 7.. bucket
-                                                  // ([wavefront]: the advanced parser of the hash-table configurations runs several parse wavefronts)
-        struct { uint32_t cd2_row0[32]; uint32_t cmp_pos[16], cmp_lim[16], cmp_res[16]; };   // wide-bucket / binary-tree configurations run one
-                                                  // wavefront: their compare scratch lies over the unused rows
+                                                  // ([Sc::wv]: row 0 the parse wavefront, row 2 the level-5 post wavefront, which keeps its node's rep distances there)
+        struct { uint32_t cd2_row0[32]; uint32_t cmp_pos[16], cmp_lim[16], cmp_res[16]; };   // the one-wavefront wide-bucket / binary-tree configurations:
+                                                  // their compare scratch lies over rows 1 and 2 (no post wavefront there), which is why the rows stay
     };
-    uint32_t rp42[kDpWaves][4];                     // the four rep-index prices of the position being priced ([wavefront])
+    uint32_t rp42[kDpWaves][4];                     // the four rep-index prices of the position being priced ([Sc::wv], as cd2)
     // The parser's DP nodes (APUnit, csc_lz.h:33-41) as a 256-slot ring + a per-node log.  A node is
     // relabelled only from nodes before it and only up to good_len - 1 <= 254 positions ahead, so
     // the live frontier (price, label, coder state, rep distances) fits a ring indexed by node & 255;
@@ -121,10 +125,16 @@ struct EncLds {
             uint32_t hand[16];                // coder-side scalars handed between the two wavefronts
         };
     };
-    DpShared dp;                              // advanced parser, two parse wavefronts: control words + edge mailboxes
+    // Retired with the turn-taking and chain forms and read by nothing; sc_load still zeroes five of its words.  It stays for the machine code's sake:
+    // without it `stage` and whatever a many-wavefront image puts behind EncLds move, and without the five stores alone the single-stream lazy kernel is
+    // allocated differently -- the level-1 / 2 / 5 kernels of the second code object change by thousands of lines (one more VGPR in the wide-bucket form,
+    // one more spilled SGPR in the lazy one; profiles/encoder_residue.md).  Four streams a CU fit with or without its 664 bytes, so it goes only in a change
+    // that measures those levels.
+    DpShared dp;
     // the sub-block being parsed: stage[j] = wnd[stage_base + j - 16] (16 bytes of history, 48 of look-ahead)
     uint32_t stage[(kMinBlock + 64) / 4];
 };
+static_assert(4 * sizeof(EncLds) <= kLdsPerCU, "the one-wavefront forms run four streams a CU");
 
 // wave-uniform scalar state of the stream (SGPR/VGPR resident; spilled back to EncState at exit)
 struct Sc {
@@ -151,7 +161,10 @@ struct Sc {
     uint32_t lane;
     uint32_t stage_base, stage_end;   // window positions covered by L->stage: [stage_base - 16, stage_end)
     uint32_t cand_len_v, cand_dist_v; // mfcand_[1..]: candidate j lives in lane j of these two VGPRs
-    uint32_t wv, dp_seq, dp_idle, dp_seq_seen;              // which parse wavefront this is (0 master, 1 helper: scratch row in cd2 / rp42); DP windows opened so far
+    uint32_t wv;                     // pipeline form: the wavefront's role number (d4_role); everywhere: the cd2 / rp42 row it works in -- 0 the parser, 2 the level-5 post wavefront
+    // Always 0, read by nothing: the window counters of the turn-taking form (retired in round 6).  They stay because taking them out moves the register
+    // allocation of the kernels in both code objects (profiles/encoder_residue.md) -- a change of machine code that has to be measured, not a cleanup.
+    uint32_t dp_seq, dp_idle, dp_seq_seen;
     uint32_t st_find, st_slide, st_bt, st_lit, st_match;
     uint32_t pipe_ok, piped, tok_headl, tok_tail_seen, pipe_seq, pair_ok;   // token pipe (parse side): active?, local head, last tail seen, hand-over number
 #ifdef CSCMI_TIMERS
@@ -872,13 +885,24 @@ DEV void compress_rle(Sc &c, const gu8 *src, uint32_t size)
     }
 }
 
-// level-5 form (csc_kernels_bt.inc): the finder wavefront (bt_finder) was measured slower; kept for the record, not dispatched
-constexpr bool kBtFinder = false;
-constexpr uint32_t kBtThreads = kBtFinder ? 448 : 256;
 DEV void sc_load_regs(Sc &c, EncState *S, EncLds *L);   // csc_kernels_blocks.inc: the register part of a context (the roles' own functions build theirs with it)
 #include "csc_kernels_mf.inc"
 #include "csc_kernels_lz.inc"
-#include "csc_kernels_dp2.inc"
+// What the many-wavefront forms of LZ::compress_advanced share (csc_kernels_dp4.inc, csc_kernels_bt.inc, csc_kernels_hp.inc): the ways a DP window ends,
+// fences, a compare-and-swap on an LDS word.
+// (Rounds 1-5 had a turn-taking form -- the nodes of a window taken by up to four parse wavefronts in turn -- and a chain form; round 6 retired both:
+// the pipeline form serves the level-3 geometry, and everything else runs one wavefront a stream.)
+enum : uint32_t { DP_CONT = 0, DP_EXIT_LIMIT = 1, DP_EXIT_LIT = 2, DP_EXIT_MATCH = 3, DP_SEEN_EXIT = 4, DP_ABORT = 5 };
+constexpr uint32_t kDpSpinLimit = 1u << 22;
+DEV void dp_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
+// the control words and mailboxes are LDS: a fence that leaves global loads in flight is enough on either side of them
+DEV void lds_fence() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup", "local"); }
+DEV uint32_t lds_cas(Sc &c, uint32_t *p, uint32_t expect, uint32_t val)
+{
+    uint32_t r = 0;
+    if (c.lane == 0) r = atomicCAS(p, expect, val);
+    return UNI(r);
+}
 #if CSCMI_TU != 1
 #include "csc_kernels_bt.inc"
 #include "csc_kernels_hp.inc"
@@ -897,7 +921,6 @@ DEV void bt_parser_call(Sc &, uint32_t) {}
 DEV void bt_inserter_call(Sc &) {}
 DEV void bt_post_call(Sc &) {}
 DEV void bt_coder_call(Sc &) {}
-DEV void bt_finder_call(Sc &) {}
 DEV void bt_init(Sc &, uint32_t) {}
 DEV void bt_inserter(Sc &) {}
 DEV void bt_post(Sc &) {}

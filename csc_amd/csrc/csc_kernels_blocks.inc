@@ -428,7 +428,7 @@ DEV void sc_load(Sc &c, EncState *S, EncLds *L)
         for (uint32_t i = c.lane; i < 512; i += 64) L->p2b[i] = d_p2bits[i];
         if (c.lane < 32) L->len_price[c.lane] = G->len_price[c.lane];
         if (c.lane < 4) L->rep[c.lane] = G->rep_dist[c.lane];
-        if (c.lane == 0) { L->pipe_cmd = 0; L->pipe_ack = 0; L->tok_head = 0; L->tok_tail = 0; L->dp.cmd = 0; L->dp.idle = 0; L->dp.abort = 0; L->dp.bstat[0] = 0; L->dp.dec = 0; }
+        if (c.lane == 0) { L->pipe_cmd = 0; L->pipe_ack = 0; L->tok_head = 0; L->tok_tail = 0; L->dp.cmd = 0; L->dp.idle = 0; L->dp.abort = 0; L->dp.bstat[0] = 0; L->dp.dec = 0; }      // (dp: see EncLds)
     }
 }
 
@@ -458,7 +458,7 @@ DEV void sc_store(Sc &c)
 // ==========================================================================================
 // k_encode_runs: the stream's serial protocol for a list of typed runs of one chunk
 // (CSCEncoder::Compress after block typing, csc_encoder_main.cpp:128-145; tail 9 = WriteEOF :154)
-// one workgroup = one stream (1, 2 or up to 4 wavefronts, see encode_stream).  FAST is the hash-table-only specialisation (levels
+// one workgroup = one stream (one wavefront, or the two / three / four / twelve of a many-wavefront form, see encode_stream).  FAST is the hash-table-only specialisation (levels
 // 1-4): the binary-tree code paths are compiled out and the vector replay path is taken.
 // (An earlier version paired the parser with a prefetch wavefront running ahead over the staged
 // sub-block; with the whole stream state resident in the 256 MiB Infinity Cache it bought nothing
@@ -498,19 +498,15 @@ DEV void encode_stream(EncState *S, const RunDesc *runs, uint32_t nruns, uint32_
     } else if (FORM == 3) {
         // binary tree: wavefront 1 is the inserter that runs ahead of the parser (csc_kernels_bt.inc)
         __syncthreads();
-        // four wavefronts, one a SIMD: 0 parser, 1 inserter, 2 post, 3 coder.  (The finder wavefront of round 5 -- the candidate search
-        // one request ahead of the parser, seven wavefronts launched -- was measured slower in all its forms, DESIGN.md section 4, and
-        // is not dispatched: kBtFinder.  Commit 70dda76 had left it switched on by accident: 0.56 -> 0.42 MB/s.)
-        if (kBtFinder) {
-            if (threadIdx.x >= 384) { bt_coder_call(c); return; }
-            if (threadIdx.x >= 256) return;
-            if (threadIdx.x >= 192) { bt_finder_call(c); return; }
-        } else if (threadIdx.x >= 192) { bt_coder_call(c); return; }       // wavefront 3: range / bit coder arithmetic + byte output (round 5)
+        // four wavefronts, one a SIMD: 0 parser, 1 inserter, 2 post, 3 coder.  (Round 5 also had a finder wavefront -- the candidate search one
+        // request ahead of the parser, seven wavefronts launched.  It was measured slower in every form; commit 70dda76 left it switched on
+        // by accident, which took silesia -m5 from 0.56 to 0.42 MB/s.  The code is gone; DESIGN.md section 4 has the full record.)
+        if (threadIdx.x >= 192) { bt_coder_call(c); return; }               // wavefront 3: range / bit coder arithmetic + byte output (round 5)
         if (threadIdx.x >= 128) { c.wv = 2; bt_post_call(c); return; }      // wavefront 2: per-length pricing + relaxation behind the parser
         if (threadIdx.x >= 64) { bt_inserter_call(c); return; }
         c.Q = bt_coderq(c);                // from here on this wavefront's coded bits go to the coder wavefront
     } else if (FAST) {
-        // advanced parser over hash tables: two parse wavefronts per stream (csc_kernels_dp2.inc)
+        // advanced parser over hash tables: the pipeline form's wavefronts (FORM 2, csc_kernels_dp4.inc), or one wavefront a stream
         __syncthreads();
         if (FORM == 2 && threadIdx.x >= 64) {                        // (the pipeline form's worker wavefronts: csc_kernels_dp4.inc, d4_role)
             c.wv = threadIdx.x >> 6;
@@ -576,12 +572,12 @@ __global__ __launch_bounds__(PARSER == 2 ? 128 : 64) void k_encode_runs_multi(En
 }
 #if CSCMI_TU != 1
 // Binary-tree configurations (level 5) under the advanced parser: parser, inserter and post wavefronts (csc_kernels_bt.inc)
-__global__ __launch_bounds__(kBtThreads) void k_encode_runs_bt(EncState *S, const RunDesc *runs, uint32_t nruns, uint32_t reset_arena)
+__global__ __launch_bounds__(256) void k_encode_runs_bt(EncState *S, const RunDesc *runs, uint32_t nruns, uint32_t reset_arena)
 {
     encode_stream<3, false, 3>(S, runs, nruns, reset_arena, &g_ldsbt.base, &g_ldsbt.x);
 }
 #ifndef CSCMI_DEV_ONE      // (CSCMI_DEV_ONE: analysis builds of ONE single-stream kernel, tools/enc_uniformity.py -- never linked)
-__global__ __launch_bounds__(kBtThreads)
+__global__ __launch_bounds__(256)
 void k_encode_runs_multi_bt(EncState *const *states, const RunDesc *const *runs, const uint32_t *nruns, const uint32_t *reset)
 {
     const uint32_t b = blockIdx.x;
@@ -605,7 +601,7 @@ void k_encode_runs_multi_hp(EncState *const *states, const RunDesc *const *runs,
 #if CSCMI_TU != 2
 // The advanced parser over hash tables as ONE wavefront a stream, four streams a CU (FORM 5): launches of more streams than the pipeline form holds (more than
 // 768: the 954-task split, the 2 048-task tree) and every configuration outside the level-3 geometry (level 4, custom props).  Round 6 retired the chain form
-// (eight wavefronts, csc_kernels_dp3.inc) and the turn-taking forms (four wavefronts, 256-VGPR "dense" instance) that served such configurations at few
+// (eight wavefronts) and the turn-taking forms (four wavefronts, 256-VGPR "dense" instance) that served such configurations at few
 // streams: no BASELINE configuration reached them, their code objects were half of this file's build time.
 __global__ __launch_bounds__(64)
 void k_encode_runs_multi_one(EncState *const *states, const RunDesc *const *runs, const uint32_t *nruns, const uint32_t *reset)
@@ -797,20 +793,16 @@ __global__ __launch_bounds__(64) void k_stage_filter(EncState *S, uint32_t kind,
 // host-callable launchers (csc_host.cpp keeps no HIP kernel syntax)
 #if defined(CSCMI_DEV_ONE)
 // (CSCMI_DEV_ONE == 3: the analysis build of the one-wavefront level-3 form, k_encode_runs_multi_one)
-#elif CSCMI_TU == 2
-// ---- second code object: the lazy levels and the binary-tree / wide-bucket configurations ----
-hipError_t upload_tables_other()
-{
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(d_p2bits), kP2Bits, sizeof(kP2Bits));
-    if (e != hipSuccess) return e;
-    return hipMemcpyToSymbol(HIP_SYMBOL(d_logtable), kLogTable, sizeof(kLogTable));
-}
+#else
+#if CSCMI_TU != 1
+// ---- the lazy levels and the binary-tree / wide-bucket configurations (the second code object where there are two): whatever the
+// launchers below do not start themselves ends here, `kind` as they got it ----
 void launch_encode_runs_multi_other(int kind, uint32_t nstreams, EncState *const *states, const RunDesc *const *runs,
                                     const uint32_t *nruns, const uint32_t *reset, hipStream_t st)
 {
-    // kind & 16: binary tree without a bucket under the advanced parser -- the inserter form while two workgroups a CU hold every stream
+    // kind & 16: binary tree without a bucket under the advanced parser -- the inserter form (csc_kernels_bt.inc) while one workgroup a CU holds every stream
     if ((kind & 16) && nstreams <= kBtMultiMax) {
-        hipLaunchKernelGGL(k_encode_runs_multi_bt, dim3(nstreams), dim3(kBtThreads), 0, st, states, runs, nruns, reset);
+        hipLaunchKernelGGL(k_encode_runs_multi_bt, dim3(nstreams), dim3(256), 0, st, states, runs, nruns, reset);
         return;
     }
     // kind & 32: lazy parser over a bucket of up to eight -- parser + coder + inserter wavefronts while three workgroups a CU hold every stream
@@ -818,29 +810,40 @@ void launch_encode_runs_multi_other(int kind, uint32_t nstreams, EncState *const
         hipLaunchKernelGGL(k_encode_runs_multi_hp, dim3(nstreams), dim3(192), 0, st, states, runs, nruns, reset);
         return;
     }
-    kind &= 7;
-    switch (kind) {
+#ifndef CSCMI_DEV_M3ONLY
+    switch (kind & 7) {
     case 2 | 4: hipLaunchKernelGGL((k_encode_runs_multi<2, true>), dim3(nstreams), dim3(128), 0, st, states, runs, nruns, reset); break;
     case 3: hipLaunchKernelGGL((k_encode_runs_multi<3, false>), dim3(nstreams), dim3(64), 0, st, states, runs, nruns, reset); break;
     default: hipLaunchKernelGGL((k_encode_runs_multi<2, false>), dim3(nstreams), dim3(128), 0, st, states, runs, nruns, reset); break;
     }
+#endif
 }
 void launch_encode_runs_other(int kind, EncState *S, const RunDesc *runs, uint32_t nruns, uint32_t reset_arena, hipStream_t st)
 {
     if (kind & 16) {
-        hipLaunchKernelGGL(k_encode_runs_bt, dim3(1), dim3(kBtThreads), 0, st, S, runs, nruns, reset_arena);
+        hipLaunchKernelGGL(k_encode_runs_bt, dim3(1), dim3(256), 0, st, S, runs, nruns, reset_arena);
         return;
     }
     if (kind & 32) {
         hipLaunchKernelGGL(k_encode_runs_hp, dim3(1), dim3(192), 0, st, S, runs, nruns, reset_arena);
         return;
     }
-    kind &= 7;
-    switch (kind) {
+#ifndef CSCMI_DEV_M3ONLY
+    switch (kind & 7) {
     case 2 | 4: hipLaunchKernelGGL((k_encode_runs<2, true>), dim3(1), dim3(128), 0, st, S, runs, nruns, reset_arena); break;
     case 3: hipLaunchKernelGGL((k_encode_runs<3, false>), dim3(1), dim3(64), 0, st, S, runs, nruns, reset_arena); break;
     default: hipLaunchKernelGGL((k_encode_runs<2, false>), dim3(1), dim3(128), 0, st, S, runs, nruns, reset_arena); break;
     }
+#endif
+}
+#endif
+#if CSCMI_TU == 2
+// (each code object has its own copy of the constant tables)
+hipError_t upload_tables_other()
+{
+    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(d_p2bits), kP2Bits, sizeof(kP2Bits));
+    if (e != hipSuccess) return e;
+    return hipMemcpyToSymbol(HIP_SYMBOL(d_logtable), kLogTable, sizeof(kLogTable));
 }
 #else
 #if CSCMI_TU == 1
@@ -865,15 +868,13 @@ void launch_analyze(EncState *S, uint32_t chunk_size, const double *ent_coef, hi
     uint32_t nblk = (chunk_size + kMinBlock - 1) / kMinBlock;
     hipLaunchKernelGGL(k_analyze, dim3(nblk), dim3(256), 0, st, S, chunk_size, ent_coef);
 }
-// (development: tools/ab_variant.sh three -DCSCMI_ONE_DYNLDS=13312 -- dynamic LDS that is never touched, to hold the one-wavefront form at THREE streams a CU instead of four)
-#ifndef CSCMI_ONE_DYNLDS
-#define CSCMI_ONE_DYNLDS 0
-#endif
 void launch_encode_runs_multi(int kind, uint32_t nstreams, EncState *const *states, const RunDesc *const *runs,
                               const uint32_t *nruns, const uint32_t *reset, hipStream_t st)
 {
     // kind = parser (2 lazy/greedy, 3 advanced) | 4 if the configuration is hash-table-only | 8 if it has the level-3 geometry
     // (bucket <= 2, good_len <= 16): the pipeline form while one workgroup a CU holds every stream (~110 KiB of LDS each)
+    // | 16 / | 32: see launch_encode_runs_multi_other.  csc_host.cpp sets 16 only without | 4 and 32 only with parser 2, so a kind of 3 | 4 never carries
+    // either: the switch below may come before those tests
     // (Beyond 1024 streams not every stream is resident at once whatever the form: the hardware starts a waiting workgroup where one
     // ends -- the reference's hand-off of the next task to the worker that finishes, csarc.cpp:361-398.  Measured on the 2 048-task
     // tree: the one-wavefront form, 1 024 streams resident, 7.0 s; the pipeline form, 256 resident and each four times faster, 10.4 s.)
@@ -885,33 +886,10 @@ void launch_encode_runs_multi(int kind, uint32_t nstreams, EncState *const *stat
         hipLaunchKernelGGL(k_encode_runs_multi_dp4, dim3(nstreams), dim3(64 * kD4Waves), 0, st, states, runs, nruns, reset);
         return;
     }
-    // | 16: binary tree without a bucket under the advanced parser: the inserter form (csc_kernels_bt.inc)
-    const int kind_all = kind;
-    (void)kind_all;
-#if CSCMI_TU != 1
-    if ((kind & 16) && nstreams <= kBtMultiMax) {
-        hipLaunchKernelGGL(k_encode_runs_multi_bt, dim3(nstreams), dim3(kBtThreads), 0, st, states, runs, nruns, reset);
-        return;
-    }
-    if ((kind & 32) && nstreams <= kHpMultiMax) {
-        hipLaunchKernelGGL(k_encode_runs_multi_hp, dim3(nstreams), dim3(192), 0, st, states, runs, nruns, reset);
-        return;
-    }
-#endif
-    kind &= 7;
-    switch (kind) {
-    case 3 | 4: {
-        // (outside the level-3 geometry, or more streams than the pipeline form holds: one wavefront a stream)
-        hipLaunchKernelGGL(k_encode_runs_multi_one, dim3(nstreams), dim3(64), CSCMI_ONE_DYNLDS, st, states, runs, nruns, reset);
-        break;
-    }
-#if CSCMI_TU == 1
-    default: launch_encode_runs_multi_other(kind_all, nstreams, states, runs, nruns, reset, st); break;
-#elif !defined(CSCMI_DEV_M3ONLY)
-    case 2 | 4: hipLaunchKernelGGL((k_encode_runs_multi<2, true>), dim3(nstreams), dim3(128), 0, st, states, runs, nruns, reset); break;
-    case 3: hipLaunchKernelGGL((k_encode_runs_multi<3, false>), dim3(nstreams), dim3(64), 0, st, states, runs, nruns, reset); break;
-    default: hipLaunchKernelGGL((k_encode_runs_multi<2, false>), dim3(nstreams), dim3(128), 0, st, states, runs, nruns, reset); break;
-#endif
+    switch (kind & 7) {
+    // (outside the level-3 geometry, or more streams than the pipeline form holds: one wavefront a stream)
+    case 3 | 4: hipLaunchKernelGGL(k_encode_runs_multi_one, dim3(nstreams), dim3(64), 0, st, states, runs, nruns, reset); break;
+    default: launch_encode_runs_multi_other(kind, nstreams, states, runs, nruns, reset, st); break;
     }
 }
 void launch_encode_eof(EncState *S, hipStream_t st) { hipLaunchKernelGGL(k_encode_eof, dim3(1), dim3(64), 0, st, S); }
@@ -927,28 +905,10 @@ void launch_encode_runs(int kind, EncState *S, const RunDesc *runs, uint32_t nru
         hipLaunchKernelGGL(k_encode_runs_dp4, dim3(1), dim3(64 * kD4Waves), 0, st, S, runs, nruns, reset_arena);
         return;
     }
-    const int kind_all = kind;
-    (void)kind_all;
-#if CSCMI_TU != 1
-    if (kind & 16) {
-        hipLaunchKernelGGL(k_encode_runs_bt, dim3(1), dim3(kBtThreads), 0, st, S, runs, nruns, reset_arena);
-        return;
-    }
-    if (kind & 32) {
-        hipLaunchKernelGGL(k_encode_runs_hp, dim3(1), dim3(192), 0, st, S, runs, nruns, reset_arena);
-        return;
-    }
-#endif
-    kind &= 7;
-    switch (kind) {
+    switch (kind & 7) {      // (3 | 4 never carries | 16 or | 32: see launch_encode_runs_multi)
     case 3 | 4: hipLaunchKernelGGL((k_encode_runs<3, true>), dim3(1), dim3(64), 0, st, S, runs, nruns, reset_arena); break;
-#if CSCMI_TU == 1
-    default: launch_encode_runs_other(kind_all, S, runs, nruns, reset_arena, st); break;
-#elif !defined(CSCMI_DEV_M3ONLY)
-    case 2 | 4: hipLaunchKernelGGL((k_encode_runs<2, true>), dim3(1), dim3(128), 0, st, S, runs, nruns, reset_arena); break;
-    case 3: hipLaunchKernelGGL((k_encode_runs<3, false>), dim3(1), dim3(64), 0, st, S, runs, nruns, reset_arena); break;
-    default: hipLaunchKernelGGL((k_encode_runs<2, false>), dim3(1), dim3(128), 0, st, S, runs, nruns, reset_arena); break;
-#endif
+    default: launch_encode_runs_other(kind, S, runs, nruns, reset_arena, st); break;
     }
 }
 #endif   // CSCMI_TU == 2
+#endif   // CSCMI_DEV_ONE

@@ -51,11 +51,13 @@ struct BtX {
     // parser -> post wavefront (bt_post): the nodes whose lengths are to be priced and relaxed, numbered 1, 2, ... through the kernel
     uint32_t sb_ack2, post_done, lp_int, has_post, has_coder;
     uint32_t hS[2], h_reset, hand[20];    // what the roles' own functions build their contexts from (end of this file)
-    // parser -> finder wavefront (bt_finder): "the candidates of sub-block offset fq_pos under these rep distances"; the answer is
-    // found[fq_pos & 1] once fa_seq == fq_seq.  The finder also works AHEAD: after an answer it computes the request it expects next.
+    // The words of round 5's finder wavefront (request, answer, two answer slots).  Its code is gone and nothing reads them; bt_init still zeroes nine of
+    // them.  Taking the words and those stores out leaves every instruction of the level-5 kernels but bt_init's as it is and only moves what lies behind
+    // them in LDS -- and silesia -m5 ran 0.85 % slower in that layout, alternating with this one, three runs each, in one call (profiles/encoder_residue.md; two builds of
+    // identical kernels differed by up to 0.3 % there).  So they stay until a change that measures level 5 in several calls takes them out.
     uint32_t fq_seq, fq_pos, fq_epoch, fq_sb, fq_rep[4];
     uint32_t fa_seq, sb_ack3, has_finder, f_hits, f_reqs, f_pad[3];
-    struct Found { uint32_t tag[8]; uint32_t n, a0l, a0d, has1, valid, pad[3]; uint32_t cl[64], cd[64]; } found[2];    // tag: pos, epoch, sub-block, rep[4], 0
+    struct Found { uint32_t tag[8]; uint32_t n, a0l, a0d, has1, valid, pad[3]; uint32_t cl[64], cd[64]; } found[2];
     struct Post { uint32_t seq, k, n, a0l, state, base_price, flags, pad, r[4], cl[64], cd[64]; } post[4];
     uint32_t shadow[64][2];               // the batch's own ring slots as they were before the batch
     uint32_t r_d2[kBtRec], r_d3[kBtRec], r_dfar[kBtRec], r_dhead[kBtRec];   // distances: HT2, HT3, far head (0 = none), tree head as the position saw it
@@ -68,6 +70,7 @@ struct BtX {
 struct EncLdsBt { EncLds base; BtX x; CoderQ q; };
 // the LDS image of a stream in this form, file-scope so that the roles' own functions (end of this file) address it directly
 __shared__ EncLdsBt g_ldsbt;
+static_assert(sizeof(EncLdsBt) <= kLdsPerCU, "a stream of this form has a CU's LDS to itself at the most");
 struct BtSb { uint32_t sb0, pos0, btpos0, size; };
 
 DEV BtX *btx(Sc &c) { return reinterpret_cast<BtX *>(c.X); }
@@ -442,26 +445,15 @@ DEV uint32_t bt_find_match_slow(Sc &c, BtX *X, uint32_t slot, uint32_t wpos, uin
 }
 
 // find_match over the record of the position: the rep candidates here, the hash side from the record's row
-// `ahead` (the finder wavefront working on a request it only expects): the parser's position is not moved, and a record that is not
-// there yet, or a new request of the parser, ends the attempt (-> kBtNone)
-DEV uint32_t bt_find_match(Sc &c, uint32_t wpos, uint32_t limit, uint32_t rep0, uint32_t rep1, uint32_t rep2, uint32_t rep3, RepCache16 &rc,
-                           bool ahead = false, uint32_t served = 0)
+DEV uint32_t bt_find_match(Sc &c, uint32_t wpos, uint32_t limit, uint32_t rep0, uint32_t rep1, uint32_t rep2, uint32_t rep3, RepCache16 &rc)
 {
     BtX *X = btx(c);
     TM_DECL;
     const uint32_t p = wpos - c.stage_base;
-    if (!ahead) {
-        lds_vstore(&X->m_pos, p);
-        uint32_t spins = 0;
-        while (lds_vload(&X->ins_head) <= p)
-            if (!bt_spin(c, X, spins, 1)) return 0;
-    } else {
-        uint32_t tries = 0;
-        while (lds_vload(&X->ins_head) <= p) {
-            if (lds_vload(&X->fq_seq) != served || lds_vload(&X->abort) || lds_vload(&X->quit) || ++tries > 4096u) return kBtNone;
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
+    lds_vstore(&X->m_pos, p);
+    uint32_t spins = 0;
+    while (lds_vload(&X->ins_head) <= p)
+        if (!bt_spin(c, X, spins, 1)) return 0;
     lds_fence();
     TM_ADD(c, 0);
     const uint32_t slot = p & (kBtRec - 1);
@@ -544,142 +536,6 @@ DEV uint32_t bt_find_match(Sc &c, uint32_t wpos, uint32_t limit, uint32_t rep0, 
         }
     }
     TM_ADD(c, 2);
-    return n;
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// FINDER wavefront (round 5).  find_match(k) needs of node k's label only the four rep distances, and those are nearly always the
-// ones of node k - 1: a literal / rep0len1 edge keeps them (csc_lz.cpp:301-313), and neighbouring nodes reached over match edges from
-// the same node with the same distance share them too.  So the candidate search -- record wait, rep lengths (sixteen positions a round
-// trip), acceptance: 40 % of the parser's time in round 4 -- runs on a wavefront of its own, one request AHEAD of the parser: after
-// answering the request for position p under rep distances R it computes what it expects to be asked next -- (p + 1, R); or, when
-// p's longest candidate reaches good_len (a certain way out by that match, csc_lz.cpp:290), (p + length, R with the match's
-// distance in front) -- and the parser's next request, if it is that one, is answered at once.  A result is used only if its tag
-// (position, rep distances, sub-block, long-match event count) equals the request's: anything computed for a future that did not
-// happen -- or from records the inserter was rewriting (bt_slide events) or from a stage the next sub-block overwrote -- is ignored.
-DEV bool bt_found_is(BtX::Found *F, uint32_t lane, uint32_t pos, uint32_t epoch, uint32_t sb, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3)
-{
-    const uint32_t want = lane == 0 ? pos : lane == 1 ? epoch : lane == 2 ? sb : lane == 3 ? r0 : lane == 4 ? r1 : lane == 5 ? r2 : lane == 6 ? r3 : 0u;
-    const uint32_t have = F->tag[lane & 7u];
-    return lds_vload(&F->valid) != 0 && __ballot(lane < 7 && have != want) == 0;
-}
-// one search into *F; -> false: given up (ahead only).  The answer to request rq stands in found[rq & 1], what is computed ahead for
-// request rq + 1 goes into the other slot: never the one the parser may still be reading.
-DEV bool bt_finder_search(Sc &c, BtX *X, BtX::Found *F, uint32_t pos, uint32_t epoch, uint32_t sb, uint32_t size, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3,
-                          RepCache16 &rc, bool ahead, uint32_t served)
-{
-    lds_vstore(&F->valid, 0);
-    lds_fence();
-    const uint32_t n = bt_find_match(c, c.stage_base + pos, size - pos, r0, r1, r2, r3, rc, ahead, served);
-    if (n == kBtNone || c.error) return false;
-    const uint32_t lane = c.lane;
-    F->cl[lane] = c.cand_len_v; F->cd[lane] = c.cand_dist_v;
-    const uint32_t a0l = n ? rdlane(c.cand_len_v, n - 1) : 1u, a0d = n ? rdlane(c.cand_dist_v, n - 1) : 0u;
-    const uint32_t has1 = (n && rdlane(c.cand_len_v, 0) == 1 && rdlane(c.cand_dist_v, 0) == 1) ? 1u : 0u;
-    const uint32_t tg = lane == 0 ? pos : lane == 1 ? epoch : lane == 2 ? sb : lane == 3 ? r0 : lane == 4 ? r1 : lane == 5 ? r2 : lane == 6 ? r3 : 0u;
-    if (lane < 8) F->tag[lane] = tg;
-    if (lane == 0) { F->n = n; F->a0l = a0l; F->a0d = a0d; F->has1 = has1; }
-    lds_fence();
-    // (the tag's epoch / sub-block were read BEFORE the search: a result that straddles an event or a sub-block change carries the old ones)
-    lds_vstore(&F->valid, 1);
-    return true;
-}
-DEV void bt_finder(Sc &c)
-{
-    BtX *X = btx(c);
-    uint32_t seen_sb = 0;
-    for (;;) {
-        uint32_t s;
-        while ((s = lds_vload(&X->sb_seq)) == seen_sb) {
-            if (lds_vload(&X->quit) || lds_vload(&X->abort)) goto out;
-            __builtin_amdgcn_s_sleep(2);
-        }
-        seen_sb = s;
-        dp_fence();
-        const uint32_t sb0 = lds_vload(&X->sb0), size = lds_vload(&X->size);
-        c.stage_base = sb0; c.stage_end = sb0 + size + 40;
-        RepCache16 rc;
-        rc.wpos0 = 0; rc.res = 0; rc.r0 = rc.r1 = rc.r2 = rc.r3 = 0; rc.valid = false;
-        uint32_t served = lds_vload(&X->fa_seq);
-        lds_vstore(&X->found[0].valid, 0); lds_vstore(&X->found[1].valid, 0);
-        lds_fence();
-        lds_vstore(&X->sb_ack3, s);
-        bool have_pred = false;
-        uint32_t pp = 0, q0 = 0, q1 = 0, q2 = 0, q3 = 0;
-        for (;;) {
-            if (lds_vload(&X->abort)) goto out;
-            if (lds_vload(&X->sb_seq) != seen_sb || lds_vload(&X->quit)) break;
-            const uint32_t rq = lds_vload(&X->fq_seq);
-            if (rq != served) {
-                lds_fence();
-                const uint32_t pos = lds_vload(&X->fq_pos), ep = lds_vload(&X->fq_epoch);
-                const uint32_t r0 = lds_vload(&X->fq_rep[0]), r1 = lds_vload(&X->fq_rep[1]), r2 = lds_vload(&X->fq_rep[2]), r3 = lds_vload(&X->fq_rep[3]);
-                TM_DECL;
-                BtX::Found *F = &X->found[rq & 1u];
-                const bool hit = bt_found_is(F, c.lane, pos, ep, seen_sb, r0, r1, r2, r3);
-                if (hit) lds_vstore(&X->m_pos, pos);           // (the inserter paces itself by the parser's true position)
-                else if (!bt_finder_search(c, X, F, pos, ep, seen_sb, size, r0, r1, r2, r3, rc, false, rq)) goto out;
-                if (c.lane == 0) { X->f_reqs++; X->f_hits += hit ? 1u : 0u; }
-                lds_fence();
-                served = rq;
-                lds_vstore(&X->fa_seq, rq);
-                // what the parser will ask next, most likely
-                const uint32_t n = lds_vload(&F->n), a0l = lds_vload(&F->a0l), a0d = lds_vload(&F->a0d);
-                have_pred = true;
-                if (n && a0l >= c.good_len) {
-                    // a way out by this match (csc_lz.cpp:290): the next window opens behind it, the match's distance in front (:127-154)
-                    pp = pos + a0l;
-                    if (a0d > 4) { q0 = a0d - 4; q1 = r0; q2 = r1; q3 = r2; }
-                    else { q0 = a0d == 1 ? r0 : a0d == 2 ? r1 : a0d == 3 ? r2 : r3; q1 = a0d > 1 ? r0 : r1; q2 = a0d > 2 ? r1 : r2; q3 = a0d > 3 ? r2 : r3; }
-                    if (a0l > 129) have_pred = false;          // (a long-match event follows: whatever is computed now is thrown away)
-                } else { pp = pos + 1; q0 = r0; q1 = r1; q2 = r2; q3 = r3; }
-                if (pp >= size) have_pred = false;
-                TM_ADD(c, 4);
-                continue;
-            }
-            if (have_pred) {
-                have_pred = false;
-                TM_DECL;
-                const uint32_t ep = lds_vload(&X->ev_ack);
-                if (lds_vload(&X->ev_seq) == ep)
-                    (void)bt_finder_search(c, X, &X->found[(served + 1u) & 1u], pp, ep, seen_sb, size, q0, q1, q2, q3, rc, true, served);
-                if (c.error) goto out;
-                TM_ADD(c, 5);
-                continue;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    }
-out:
-#ifdef CSCMI_TIMERS
-    if (c.lane == 0) for (int q = 0; q < 2; q++) atomicAdd(&c.S->stats.tm[14 + q], c.tm[4 + q]);
-#endif
-    return;
-}
-// parser side: the candidates of the position under these rep distances -> cand_len_v / cand_dist_v, count
-DEV uint32_t bt_found(Sc &c, uint32_t wpos, uint32_t r0, uint32_t r1, uint32_t r2, uint32_t r3, uint32_t sb)
-{
-    BtX *X = btx(c);
-    TM_DECL;
-    const uint32_t p = wpos - c.stage_base;
-    const uint32_t ep = lds_vload(&X->ev_ack);
-    const uint32_t lane = c.lane;
-    // the request in one store: lanes 1..7 = pos, epoch, sub-block, rep distances; then the sequence number
-    const uint32_t w = lane == 1 ? p : lane == 2 ? ep : lane == 3 ? sb : lane == 4 ? r0 : lane == 5 ? r1 : lane == 6 ? r2 : r3;
-    if (lane >= 1 && lane < 8) (&X->fq_seq)[lane] = w;
-    static_assert(offsetof(BtX, fq_rep) == offsetof(BtX, fq_seq) + 16 && offsetof(BtX, fq_pos) == offsetof(BtX, fq_seq) + 4, "request words follow fq_seq: pos, epoch, sb, rep[4]");
-    lds_fence();
-    const uint32_t rq = lds_vload(&X->fq_seq) + 1;
-    lds_vstore(&X->fq_seq, rq);
-    uint32_t spins = 0;
-    while (lds_vload(&X->fa_seq) != rq)
-        if (!bt_spin(c, X, spins, 8)) return 0;
-    lds_fence();
-    TM_ADD(c, 0);
-    BtX::Found *F = &X->found[rq & 1u];
-    c.cand_len_v = F->cl[lane]; c.cand_dist_v = F->cd[lane];
-    const uint32_t n = lds_vload(&F->n);
-    TM_ADD(c, 1);
     return n;
 }
 
@@ -813,8 +669,6 @@ DEV void lz_compress_advanced_bt(Sc &c, uint32_t size)
     // the post wavefront takes the per-length pricing and the relaxation when the kernel has one and a node's length table fits
     // its lanes (FindMatchWithPrice beyond 64 lengths goes through the appt arrays, which alias the back-trace's)
     const bool split = lds_vload(&X->has_post) != 0 && c.good_len <= 64;
-    const bool finder = kBtFinder && split && lds_vload(&X->has_finder) != 0;      // the candidate search on a wavefront of its own, one request ahead (bt_finder)
-    uint32_t seen_sb_f = 0;
     RepCache16 rc;
     rc.wpos0 = 0; rc.res = 0; rc.r0 = rc.r1 = rc.r2 = rc.r3 = 0; rc.valid = false;
     uint32_t pseq = lds_vload(&X->post_done);
@@ -827,9 +681,8 @@ DEV void lz_compress_advanced_bt(Sc &c, uint32_t size)
         dp_fence();
         const uint32_t s = lds_vload(&X->sb_seq) + 1;
         lds_vstore(&X->sb_seq, s);
-        seen_sb_f = s;
         uint32_t spins = 0;
-        while (lds_vload(&X->sb_ack) != s || (split && lds_vload(&X->sb_ack2) != s) || (finder && lds_vload(&X->sb_ack3) != s))
+        while (lds_vload(&X->sb_ack) != s || (split && lds_vload(&X->sb_ack2) != s))
             if (!bt_spin(c, X, spins, 3)) return;
     }
     for (uint32_t i = 0; i < size && !c.error;) {
@@ -872,7 +725,7 @@ DEV void lz_compress_advanced_bt(Sc &c, uint32_t size)
                     // FindMatchWithPrice (:584-625) in two halves: the candidates and what the ways out / the two length-1 edges need
                     // here, the per-length prices and their relaxation on the post wavefront
                     c.st_find++;
-                    const uint32_t n = finder ? bt_found(c, c.wnd_curpos, r0, r1, r2, r3, seen_sb_f) : bt_find_match(c, c.wnd_curpos, size - i - apcur, r0, r1, r2, r3, rc);
+                    const uint32_t n = bt_find_match(c, c.wnd_curpos, size - i - apcur, r0, r1, r2, r3, rc);
                     if (c.error) return;
                     TM_DECL;
                     const uint32_t t = mf_state_prices(c, cur_state);
@@ -1004,7 +857,7 @@ DEV void bt_init(Sc &c, uint32_t reset_arena)               // every wavefront, 
         X->sb_seq = 0; X->sb_ack = 0; X->quit = 0; X->abort = 0; X->m_pos = 0; X->ins_head = 0;
         X->ev_seq = 0; X->ev_ack = 0; X->st_bt = 0; X->st_undo = 0;
         X->sb_ack2 = 0; X->post_done = 0; X->lp_int = 0; X->has_post = blockDim.x >= 192 ? 1u : 0u; X->has_coder = blockDim.x >= 256 ? 1u : 0u;
-        X->fq_seq = 0; X->fa_seq = 0; X->sb_ack3 = 0; X->has_finder = (kBtFinder && blockDim.x >= 448) ? 1u : 0u; X->f_hits = 0; X->f_reqs = 0;
+        X->fq_seq = 0; X->fa_seq = 0; X->sb_ack3 = 0; X->has_finder = 0; X->f_hits = 0; X->f_reqs = 0;      // (see BtX)
         X->found[0].valid = 0; X->found[1].valid = 0;
         for (int q = 0; q < 4; q++) X->post[q].seq = 0;
         CoderQ *Q = &g_ldsbt.q;
@@ -1148,7 +1001,6 @@ DEV void bt_parser_call(Sc &c, uint32_t size)
 }
 __device__ __noinline__ void bt_inserter_nl() { Sc c; bt_ctx(c); bt_inserter(c); }
 __device__ __noinline__ void bt_post_nl() { Sc c; bt_ctx(c); c.wv = 2; bt_post(c); }
-__device__ __noinline__ void bt_finder_nl() { Sc c; bt_ctx(c); c.wv = 3; bt_finder(c); }
 __device__ __noinline__ void bt_coder_nl()
 {
     Sc c;
@@ -1164,5 +1016,4 @@ __device__ __noinline__ void bt_coder_nl()
 }
 DEV void bt_inserter_call(Sc &) { bt_inserter_nl(); }
 DEV void bt_post_call(Sc &) { bt_post_nl(); }
-DEV void bt_finder_call(Sc &) { bt_finder_nl(); }
 DEV void bt_coder_call(Sc &) { bt_coder_nl(); }

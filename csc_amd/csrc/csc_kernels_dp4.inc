@@ -53,6 +53,7 @@ constexpr uint32_t kD4Requested = 0xFFFFFFFFu;
 #define D4_IDLE_MUL 1                      // (development: tools/ab_variant.sh idle2 -DD4_IDLE_MUL=2 -- how much the workers' idle polls cost the wavefronts that work)
 #endif
 constexpr int kD4IdleSleep = 4 * D4_IDLE_MUL;            // s_sleep argument (x 64 cycles) of a worker that found nothing to do
+constexpr uint32_t kDpInf = 0xFFFFFFFFu;    // price of a DP node no edge has reached
 constexpr uint32_t kD4RefreshAt = 32;     // ask for a re-based mask once a rep's mask is this many positions old
 constexpr uint32_t kD4MaxGood = 16;       // good_len up to which a node's length table fits the record's 16 lanes
 constexpr uint32_t kD6Ring = 128;         // literal records between the spine and the wavefront that codes their trees (d6_trees)
@@ -132,6 +133,7 @@ struct EncLds4 { EncLds base; Dp4X x; CoderQ q; };
 // ONE object for every kernel of the pipeline form: d4_window and its helpers are real functions (not inlined) and reach the
 // stream's LDS image through it
 __shared__ EncLds4 g_lds4;
+static_assert(sizeof(EncLds4) <= kLdsPerCU, "a stream of the pipeline form has a CU's LDS to itself at the most");
 
 // record meta word: match length (capped at 64 = "at least 64") | considered << 8 | dropped by bound[] << 9 | pushable << 10
 //                   | distance-slot price in units of 128 << 12 (6 bits) | entry id << 20

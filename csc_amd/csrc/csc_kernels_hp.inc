@@ -42,6 +42,7 @@ struct HpX {
 struct EncLdsHp { EncLds base; HpX x; };
 // the LDS image of a stream in this form, file-scope so that the roles' own functions address it directly
 __shared__ EncLdsHp g_ldshp;
+static_assert(3 * sizeof(EncLdsHp) <= kLdsPerCU, "kHpMultiMax counts on three workgroups a CU");
 struct HpSb { uint32_t sb0, pos0, size; };
 
 DEV HpX *hpx(Sc &c) { return reinterpret_cast<HpX *>(c.X); }

@@ -1,5 +1,5 @@
 // csc_kernels_lz.inc -- LZ parsers (csc_lz.cpp): the one-wavefront forms and the token pipe (parse wavefront -> coder
-// wavefront) of the lazy levels.  The multi-wavefront advanced parser is csc_kernels_dp2.inc.
+// wavefront) of the lazy levels.  The many-wavefront forms of the advanced parser are csc_kernels_dp4.inc (level-3 geometry) and csc_kernels_bt.inc (binary tree).
 // Included by csc_kernels.hip inside namespace cscmi.
 
 // LZ::encode_nonlit, csc_lz.cpp:127-154 (u.dist: 1..4 = rep index+1, >= 5 = distance+4)

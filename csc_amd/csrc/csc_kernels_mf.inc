@@ -726,16 +726,6 @@ DEV uint32_t mf_rep_prefix16(Sc &c, uint32_t wpos, uint32_t limit, uint32_t rep0
 {
     const Rep16At t = rep16_at(c, wpos, limit, rep0, rep1, rep2, rep3);
     const uint32_t lim = t.lim, ai = t.ai;
-#ifdef CSCMI_REP16_LOOP
-    uint32_t n = 0;
-    bool go = lim > 0;
-    while (go) {
-        const uint64_t x = stage_load8(c.L->stage, ai + n) ^ load8u((const gu8 *)t.q + t.sh + n);
-        if (x) { n += (uint32_t)__builtin_ctzll(x) >> 3; go = false; }
-        else { n += 8; go = n < lim; }
-    }
-    return umin(n, lim);
-#else
     // At most TWO round trips (round 6): the first 8 bytes of every candidate; then, if any candidate is still equal, the other 24 bytes of all of them at
     // once (six more aligned words a lane from the window, six from the stage, three 8-byte comparisons, the first difference by selects).  The loop this
     // replaces fetched 8 bytes a turn and turned as long as ANY of the 64 candidates was still equal -- on text three or four dependent HBM / L2 round trips a
@@ -769,7 +759,6 @@ DEV uint32_t mf_rep_prefix16(Sc &c, uint32_t wpos, uint32_t limit, uint32_t rep0
         n = n == 8u ? m : n;
     }
     return umin(n, lim);
-#endif
 }
 
 // the lazy parser's preference predicate, csc_mf.cpp:508-516 and :570-582

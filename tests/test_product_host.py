@@ -177,3 +177,22 @@ def test_every_encoder_form_is_in_the_dispatch_matrix():
         if f["threshold"] and f["multi"] != f["over"]:
             t = test_gpu_forms.THRESHOLDS[f["threshold"]]
             assert {(row, t), (row, t + 1)} <= set(test_gpu_forms.THRESHOLD_CASES), row
+
+
+def test_kernel_sources_are_the_makefiles_dependency_list():
+    """what csc_kernels.hip #includes by quoted name -- itself or through a file it includes (csc_kernels_dp4.inc pulls in its _dev
+    companion) -- is exactly the Makefile's KERNEL_SRC minus csc_kernels.hip, and every one of them exists: a file missing from that
+    list means a stale library after an edit of it"""
+    csrc = os.path.join(ROOT, "csc_amd", "csrc")
+    listed = re.search(r"^KERNEL_SRC\s*:=\s*(.*)$", open(os.path.join(csrc, "Makefile")).read(), flags=re.M).group(1).split()
+    assert listed.count("csc_kernels.hip") == 1 and len(set(listed)) == len(listed), listed
+    for f in listed:
+        assert os.path.isfile(os.path.join(csrc, f)), f
+    included, todo = set(), ["csc_kernels.hip"]
+    while todo:
+        for f in re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(csrc, todo.pop())).read(), flags=re.M):
+            assert f.endswith((".inc", ".h")) and os.path.isfile(os.path.join(csrc, f)), f
+            if f not in included:
+                included.add(f)
+                todo.append(f)
+    assert sorted(included) == sorted(set(listed) - {"csc_kernels.hip"}), (sorted(included), sorted(listed))
