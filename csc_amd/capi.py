@@ -96,7 +96,10 @@ class BytesReader:
         return bytearray(self.data[self.pos:self.pos + n])
 
     def ptr(self):
-        return C.byref(self.stream)
+        """(a pointer object, not byref: C.cast keeps the object it casts alive, and through it the stream, its callback and this
+        reader -- a temporary reader handed to a call as C.cast(BytesReader(...).ptr(), C.c_void_p) is otherwise held by nothing but
+        its own callback's reference cycle, which the collector may free while the library still calls it)"""
+        return C.pointer(self.stream)
 
 
 class BytesWriter:
@@ -122,7 +125,8 @@ class BytesWriter:
         return size
 
     def ptr(self):
-        return C.byref(self.stream)
+        """(a pointer object, not byref: see BytesReader.ptr)"""
+        return C.pointer(self.stream)
 
 
 class CscLib:

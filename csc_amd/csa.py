@@ -133,6 +133,16 @@ class CSADevDigestStats(C.Structure):
                 "mismatches": self.mismatches, "first_mismatch": self.first_mismatch, "digest_kernel_ms": self.kernel_ms}
 
 
+class CSADevMoveStats(C.Structure):
+    _fields_ = [("moves", C.c_uint64), ("moved_bytes", C.c_uint64), ("parked_moves", C.c_uint64), ("parked_bytes", C.c_uint64),
+                ("held_stream_bytes", C.c_uint64), ("launches", C.c_uint64), ("kernel_ms", C.c_double)]
+
+    def as_dict(self):
+        """(the names the write's statistics also have get a prefix: the dicts are merged)"""
+        return {"moves": self.moves, "moved_bytes": self.moved_bytes, "parked_moves": self.parked_moves, "parked_bytes": self.parked_bytes,
+                "held_stream_bytes": self.held_stream_bytes, "move_launches": self.launches, "move_kernel_ms": self.kernel_ms}
+
+
 LIST_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int64, C.c_int, C.POINTER(CSAFrag))
 
 SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", "CSA_ReadIndex",
@@ -146,7 +156,7 @@ SYMBOLS = ["CSA_OptionsInit", "CSA_Add", "CSA_Extract", "CSA_Test", "CSA_List", 
            "CSAMI_CheckSlices", "CSAMI_DeviceReadIntoSlices", "CSAMI_DeviceCompareSlices",
            "CSAMI_DeviceUpdate", "CSAMI_PlanDeviceUpdate",
            "CSAMI_DeviceWriteFragCount", "CSAMI_DeviceDigestSlices", "CSAMI_DeviceUpdateDigests", "CSAMI_DeviceReadDigests",
-           "CSAMI_DeviceDigestKernelMs"]
+           "CSAMI_DeviceDigestKernelMs", "CSAMI_DeviceUpdateInPlace", "CSAMI_DeviceMoveKernelMs"]
 
 CSA_MAX_FRAGMENTS = 127
 CSA_TOO_MANY_FRAGMENTS = -94
@@ -278,6 +288,13 @@ def lib():
         L.CSAMI_DeviceReadDigests.restype = C.c_int
         L.CSAMI_DeviceDigestKernelMs.argtypes = [C.POINTER(C.c_double)]
         L.CSAMI_DeviceDigestKernelMs.restype = None
+        # (CSAMI_DeviceUpdateDigests's arguments with buf_cap behind the handle, no arc, and the move statistics at the end)
+        L.CSAMI_DeviceUpdateInPlace.argtypes = ([C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64] + L.CSAMI_DeviceUpdate.argtypes[1:7]
+                                                + L.CSAMI_DeviceUpdate.argtypes[9:]
+                                                + [C.c_void_p, C.c_uint64, C.POINTER(CSADevDigestStats), C.POINTER(CSADevMoveStats)])
+        L.CSAMI_DeviceUpdateInPlace.restype = C.c_int
+        L.CSAMI_DeviceMoveKernelMs.argtypes = [C.POINTER(C.c_double)]
+        L.CSAMI_DeviceMoveKernelMs.restype = None
         _lib = L
     return _lib
 
@@ -611,6 +628,14 @@ def device_digest_kernel_ms():
     return tuple(ms)
 
 
+def device_move_kernel_ms():
+    """HIP-event milliseconds of this thread's last DeviceArchive.update_in_place by launch: (the park copy, k_move_extents' left phase,
+    its right phase)"""
+    ms = (C.c_double * 3)()
+    lib().CSAMI_DeviceMoveKernelMs(ms)
+    return tuple(ms)
+
+
 def check_buffers(ptrs: Sequence[int], sizes: Sequence[int], excl=(0, 0), disjoint: bool = False):
     """CSAMI_CheckBuffers (host only): the address checks write_tensors, extract_into and compare make before anything is launched.
     ptrs, sizes: addresses and byte counts; excl: (address, size) of the range none may overlap -> (rc, lowest refused index or None)"""
@@ -922,12 +947,76 @@ class DeviceArchive:
         "status"}] per task of the new plan.  entries: write_slices's; an entry without "slice" is its whole tensor.  The new
         archive is byte for byte write_slices's as long as this archive was written at the same level.  trust_sums: nothing is
         decoded -- a task is taken for unchanged when every fragment's adler32 equals this archive's index's, a 32-bit test that two
-        different contents can pass.  arc must not overlap this archive's tensor.
+        different contents can pass.  arc must not overlap this archive's tensor (update_in_place is the call for that).
         digests: as in write_tensors -- the new archive's table, computed in this call from the entries' bytes.  base_digests: this
         archive's table, as the call that wrote it (or digests()) handed it out.  trust_digests: nothing is decoded -- a task is taken
         for unchanged when every fragment's BLAKE2s digest equals base_digests's at that fragment's place in this archive's index."""
         flags = (CSAMI_UPDATE_TRUST_SUMS if trust_sums else 0) | (CSAMI_UPDATE_TRUST_DIGESTS if trust_digests else 0)
         return _write_slices(self, entries, arcname, arc, flags, True, opts, digests=digests, base_digests=base_digests)
+
+    def update_in_place(self, entries, buf=None, arcname: str = "out.csa", trust_sums=False, digests=False, base_digests=None,
+                        trust_digests=False, **opts):
+        """update with the new archive in the place of this one (CSAMI_DeviceUpdateInPlace) -> (rc, uint8 CUDA view buf[:archive_bytes],
+        stats dict): update's, with the move statistics merged in.  buf: the 1-d uint8 CUDA tensor whose first bytes are this archive
+        -- the same data_ptr() as the opened tensor and at least its numel(), else ValueError; default: the opened tensor itself.
+        The new archive may grow into the room behind the old one, up to buf.numel().  On success this object stays open on the
+        view and describes the new archive: no reopen.  Every refusal (rc != 0 other than CSCMI_DEVICE_ERROR) leaves buf and this
+        object as they were; there is nothing to reallocate, so nothing is tried twice."""
+        import torch
+        if buf is None:
+            buf = self._arc
+        if not _is_bytes_tensor(buf):
+            raise TypeError("buf: a contiguous 1-d torch.uint8 CUDA tensor")
+        if buf.data_ptr() != self._arc.data_ptr() or buf.numel() < self._arc.numel():
+            raise ValueError("buf: it begins at the opened archive's first byte and is at least as large")
+        files, table = [], (CSADevSlice * max(len(entries), 1))()
+        for a, e in zip(table, entries):
+            t = e["tensor"]
+            if not (t is None or _is_bytes_tensor(t)):
+                raise TypeError("tensor: a contiguous 1-d torch.uint8 CUDA tensor, or None")
+            s = e.get("slice") or ((0, int(t.numel())) if t is not None else (0, 0, 0, 0))
+            a.offset, a.run, a.stride, a.count = (s[0], s[1], s[1], 1 if s[1] else 0) if len(s) == 2 else s
+            files.append({"name": e["name"], "esize": a.run * a.count if a.count else 0, "edate": e["edate"], "eattr": e["eattr"]})
+        if base_digests is not None and not _is_digest_table(base_digests):
+            raise TypeError("base_digests: a contiguous torch.uint8 CUDA tensor [n, 32]")
+        live = [e["tensor"] for e in entries]                      # alive across the call
+        ptrs = (C.c_void_p * max(len(live), 1))(*[t.data_ptr() if t is not None and t.numel() else None for t in live])
+        sizes = (C.c_uint64 * max(len(live), 1))(*[0 if t is None else int(t.numel()) for t in live])
+        out = None
+        if _is_digest_table(digests):
+            out = digests
+        elif digests is not False and digests is not None:
+            if digests is not True:
+                raise TypeError("digests: True, or a contiguous torch.uint8 CUDA tensor [n, 32] to write the table into")
+            rc, out = _digest_table(files, arcname, buf.device, opts)
+            if rc != 0:
+                return rc, None, {"files": []}
+        rc, nt, _, _ = device_write_plan(files, arcname, **opts)
+        if rc != 0:
+            return rc, None, {"files": []}
+        flags = (CSAMI_UPDATE_TRUST_SUMS if trust_sums else 0) | (CSAMI_UPDATE_TRUST_DIGESTS if trust_digests else 0)
+        o = options(**opts)
+        st, gs, us, ds, ms = CSADevWriteStats(), CSADevGatherStats(), CSADevUpdateStats(), CSADevDigestStats(), CSADevMoveStats()
+        tasks = (CSADevUpdateTask * max(nt, 1))()
+        arr, keep = _write_table(files)
+        torch.cuda.synchronize()                   # the buffers were filled on torch's stream, the library launches on its own
+        rc = lib().CSAMI_DeviceUpdateInPlace(
+            self._h, int(buf.numel()), None if base_digests is None else C.c_void_p(base_digests.data_ptr() or 0),
+            0 if base_digests is None else int(base_digests.shape[0]), ptrs, sizes, table, arr, len(keep), arcname.encode(), flags, C.byref(o),
+            C.byref(st), C.byref(gs), C.byref(us), tasks, nt, None if out is None else C.c_void_p(out.data_ptr() or 0),
+            0 if out is None else int(out.shape[0]), C.byref(ds), C.byref(ms))
+        d = {}
+        for x in (st, gs, us, ds, ms):
+            d.update(x.as_dict())
+        d["files"] = [_file_dict(a, f["name"]) for a, f in zip(arr, files)]
+        d["tasks"] = [t.as_dict() for t in tasks[:min(nt, int(st.tasks))]]
+        if out is not None:
+            d["digests"] = out
+        if rc != 0:
+            return rc, None, d
+        self._buf = buf                                # (the view's storage)
+        self._arc = buf[:st.archive_bytes]
+        return rc, self._arc, d
 
     def _by(self, bufs, names, take):
         """the selection's files table and, per entry of it, the caller's base buffer, its address and size, and the slice of it (None,

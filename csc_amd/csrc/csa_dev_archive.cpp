@@ -18,6 +18,7 @@
 #include "csa_dev_read.h"
 #include "csa_dev_write.h"
 #include "csa_dev_digest.h"
+#include "csa_dev_move.h"
 
 using namespace csa;
 
@@ -1193,6 +1194,8 @@ int CSAMI_PlanDeviceSlices(const uint8_t *raw_index, uint64_t raw_size, uint64_t
 // waves, for the table the call hands out and for the comparison with the base's table under CSAMI_UPDATE_TRUST_DIGESTS.
 // CSAMI_DeviceUpdate is that path with a base archive: the tasks of the plan that are tasks of the base (update_candidates) and whose
 // bytes are still the base's (dev_check_wave) are placed from the base instead of encoded; CSAMI_DeviceWriteSlices is it without one.
+// CSAMI_DeviceUpdateInPlace is the update whose new archive takes the base's place in the caller's buffer: the same body (dev_update)
+// with the steps in the order that puts every refusal before the first store, and the reused streams moved by k_move_extents.
 // ---------------------------------------------------------------------------------------------
 namespace {
 
@@ -1397,10 +1400,18 @@ int dev_place(WriteCtx &W, const std::vector<Placed> &items, const uint8_t *hdr,
     return 0;
 }
 
-// One wave: tasks [first, first + count) of the plan.  0, WRITE_ERROR, CSCMI_DEVICE_ERROR, or -1 (CSAMI_DeviceUpdate: a reused
-// stream does not end at its length).  A task CSAMI_DeviceUpdate reuses is neither gathered nor summed nor encoded: its stream is
-// placed from the base archive beside the encoded ones, and its block table taken where it was placed.
-int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
+// The front half of a wave, tasks [first, first + count) of the plan, which the write and the update in place share: where each
+// task's raw bytes lie, the gather and the sums, the encode into scratch of this layer.  jobs[job_of[k]] is task first + k's (a
+// reused task has none); the scratch lives as long as this object.
+struct WaveStreams {
+    DevBuf d_gat, d_scr;
+    std::list<DevBuf> more;
+    std::vector<CSCMIDevEncode> jobs;
+    std::vector<size_t> job_of;
+    int encode(WriteCtx &W, AddPlan &P, size_t first, size_t count);       // 0 or CSCMI_DEVICE_ERROR
+};
+
+int WaveStreams::encode(WriteCtx &W, AddPlan &P, size_t first, size_t count)
 {
     using namespace csadev;
     auto reused = [&](size_t k) { return W.upd && W.upd->reused(first + k); };
@@ -1437,7 +1448,6 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
         }
     }
     if (npieces > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
-    DevBuf d_gat;
     if (gat_bytes && !d_gat.alloc(gat_bytes)) return CSCMI_DEVICE_ERROR;
 
     // 2. gather and sum in one pass: the fragments of the gathered tasks, whose pieces are stored, first -- through k_frag_rows if
@@ -1475,8 +1485,8 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
     }
 
     // 3. encode: csa_worker.cpp:23-56 for every task of the wave that is not reused at once, into scratch of this layer
-    std::vector<CSCMIDevEncode> jobs;
-    std::vector<size_t> job_of(count, SIZE_MAX);
+    jobs.clear();
+    job_of.assign(count, SIZE_MAX);
     uint64_t scr_bytes = 0;
     std::vector<uint64_t> scr_off(count, 0);
     for (size_t k = 0; k < count; k++) {
@@ -1484,8 +1494,6 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
         scr_off[k] = scr_bytes;
         scr_bytes += (stream_cap(W, P.tasks[first + k].total) + 255) & ~255ull;
     }
-    DevBuf d_scr;
-    std::list<DevBuf> more;
     if (!d_scr.alloc(scr_bytes)) return CSCMI_DEVICE_ERROR;
     for (size_t k = 0; k < count; k++) {
         if (reused(k)) continue;
@@ -1500,8 +1508,60 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
         job_of[k] = jobs.size();
         jobs.push_back(j);
     }
-    int rc = jobs.empty() ? 0 : dev_encode(W, jobs, more);
+    return jobs.empty() ? 0 : dev_encode(W, jobs, more);
+}
+
+// One k_block_table launch over `bj` (job i is task task[i] of the plan, a reused one where reused[i]) and what the host reads
+// back of it: br[i], and the block sizes of all jobs back to back in `sizes`.  0, CSCMI_DEVICE_ERROR, or -1: a reused stream does
+// not end at its length.
+int dev_block_tables(WriteCtx &W, const std::vector<csadev::BlockTableJob> &bj, const std::vector<size_t> &task, const std::vector<uint8_t> &reused,
+                     std::vector<csadev::BlockTableRes> &br, std::vector<uint64_t> &sizes)
+{
+    using namespace csadev;
+    const size_t count = bj.size();
+    uint64_t slots = 0;
+    for (const BlockTableJob &j : bj) slots += j.max_blocks;
+    br.assign(count, BlockTableRes{0, 0});
+    DevBuf d_bj, d_slots, d_res, d_sizes;
+    if (!dev_upload(W, d_bj, bj.data(), bj.size() * sizeof(BlockTableJob)) || !d_slots.alloc(slots * 8) || !d_res.alloc(count * sizeof(BlockTableRes))
+        || !d_sizes.alloc(slots * 8)) return CSCMI_DEVICE_ERROR;
+    if (!W.tm.timed(&g_write_ms[2], W.S.launches, [&] { launch_block_table(d_bj.p, (uint32_t)count, d_slots.p, d_res.p, d_sizes.p, W.tm.st); }))
+        return CSCMI_DEVICE_ERROR;
+    if (!HIP_OK(hipMemcpy(br.data(), d_res.p, count * sizeof(BlockTableRes), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+    W.S.readback_bytes += count * sizeof(BlockTableRes);
+    uint64_t nb = 0;
+    for (size_t k = 0; k < count; k++) {
+        if (br[k].status != kTableOk || br[k].nblocks > bj[k].max_blocks) {
+            if (reused[k]) {
+                fprintf(stderr, "csa-mi355x: task %zu: the stream reused from the base archive does not end at its length (block table status %u)\n",
+                        task[k], br[k].status);
+                return -1;
+            }
+            fprintf(stderr, "csa-mi355x: task %zu: its stream does not end where its encoder said (block table status %u)\n", task[k], br[k].status);
+            return CSCMI_DEVICE_ERROR;
+        }
+        nb += br[k].nblocks;
+    }
+    sizes.resize(nb);
+    if (nb && !HIP_OK(hipMemcpy(sizes.data(), d_sizes.p, nb * 8, hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+    W.S.readback_bytes += nb * 8;
+    W.S.blocks += nb;
+    return 0;
+}
+
+// One wave: tasks [first, first + count) of the plan.  0, WRITE_ERROR, CSCMI_DEVICE_ERROR, or -1 (CSAMI_DeviceUpdate: a reused
+// stream does not end at its length).  A task CSAMI_DeviceUpdate reuses is neither gathered nor summed nor encoded: its stream is
+// placed from the base archive beside the encoded ones, and its block table taken where it was placed.
+int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
+{
+    using namespace csadev;
+    auto reused = [&](size_t k) { return W.upd && W.upd->reused(first + k); };
+    // 1. - 3. gather, sum, encode
+    WaveStreams E;
+    int rc = E.encode(W, P, first, count);
     if (rc) return rc;
+    const std::vector<CSCMIDevEncode> &jobs = E.jobs;
+    const std::vector<size_t> &job_of = E.job_of;
 
     // 4. placement (csa_io.h:559-573; id == task index, csarc.cpp:393-394): it needs the streams' sizes alone
     std::vector<Placed> items(count);
@@ -1528,34 +1588,13 @@ int dev_write_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count)
         bj[k] = BlockTableJob{stream, produced, props.csc_blocksize, (uint32_t)mb, slots};
         slots += mb;
     }
-    std::vector<BlockTableRes> br(count);
+    std::vector<BlockTableRes> br;
     std::vector<uint64_t> sizes;
-    {
-        DevBuf d_bj, d_slots, d_res, d_sizes;
-        if (!dev_upload(W, d_bj, bj.data(), bj.size() * sizeof(BlockTableJob)) || !d_slots.alloc(slots * 8) || !d_res.alloc(count * sizeof(BlockTableRes))
-            || !d_sizes.alloc(slots * 8)) return CSCMI_DEVICE_ERROR;
-        if (!W.tm.timed(&g_write_ms[2], W.S.launches, [&] { launch_block_table(d_bj.p, (uint32_t)count, d_slots.p, d_res.p, d_sizes.p, W.tm.st); }))
-            return CSCMI_DEVICE_ERROR;
-        if (!HIP_OK(hipMemcpy(br.data(), d_res.p, count * sizeof(BlockTableRes), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-        W.S.readback_bytes += count * sizeof(BlockTableRes);
-        uint64_t nb = 0;
-        for (size_t k = 0; k < count; k++) {
-            if (br[k].status != kTableOk || br[k].nblocks > bj[k].max_blocks) {
-                if (reused(k)) {
-                    fprintf(stderr, "csa-mi355x: task %zu: the stream reused from the base archive does not end at its length (block table status %u)\n",
-                            first + k, br[k].status);
-                    return -1;
-                }
-                fprintf(stderr, "csa-mi355x: task %zu: its stream does not end where its encoder said (block table status %u)\n", first + k, br[k].status);
-                return CSCMI_DEVICE_ERROR;
-            }
-            nb += br[k].nblocks;
-        }
-        sizes.resize(nb);
-        if (nb && !HIP_OK(hipMemcpy(sizes.data(), d_sizes.p, nb * 8, hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
-        W.S.readback_bytes += nb * 8;
-        W.S.blocks += nb;
-    }
+    std::vector<size_t> task(count);
+    std::vector<uint8_t> from_base(count);
+    for (size_t k = 0; k < count; k++) { task[k] = first + k; from_base[k] = reused(k); }
+    rc = dev_block_tables(W, bj, task, from_base, br, sizes);
+    if (rc) return rc;
 
     // 6. the tasks' extents
     size_t nx = 0;
@@ -1671,6 +1710,235 @@ int dev_check_wave(WriteCtx &W, UpdateCtx &U, AddPlan &P, const std::vector<size
         else if (U.trust && u.status == CSA_UPD_CHANGED) u.have_sums = true;
         u.candidate = false;
     }
+    return 0;
+}
+
+// ---- CSAMI_DeviceUpdateInPlace: the new archive takes the base's place in the caller's buffer ----
+// Nothing is stored into the buffer before every size is known and the last refusal has passed: the encoded streams are held in
+// scratch (dev_hold_wave), the reused ones are walked where they lie in the base (dev_reused_tables), the layout and the index are
+// made on the host, and only then the reused streams move (csa_dev_move.h, k_move_extents) and everything else is placed
+// (dev_move_and_place).
+
+thread_local double g_move_ms[3] = {0, 0, 0};          // CSAMI_DeviceMoveKernelMs: park, left, right
+
+struct HeldTask {
+    const uint8_t *stream = nullptr;           // an encoded task: its stream in held memory, `produced` bytes
+    uint64_t produced = 0;
+    uint8_t props[CSC_PROP_SIZE];
+    std::vector<uint64_t> blocks;              // every task: its archive blocks' sizes
+};
+struct InPlace {
+    uint64_t buf_cap = 0;
+    CSADevMoveStats M;
+    std::vector<HeldTask> held;                // per task of the plan
+    std::list<DevBuf> mem;                     // the held streams, one allocation a wave
+    uint64_t held_bytes = 0;
+    std::vector<uint64_t> at;                  // where each task's stream will begin
+};
+
+// One wave of the update in place: gather, sum and encode as dev_write_wave; the block tables of the encoded streams where they lie
+// in scratch; the streams compacted to their `produced` bytes into held memory with one k_gather_extents launch.  The wave's
+// oversized scratch goes with E.  At most five launches a wave.  0 or CSCMI_DEVICE_ERROR.
+int dev_hold_wave(WriteCtx &W, AddPlan &P, size_t first, size_t count, InPlace &IP)
+{
+    using namespace csadev;
+    WaveStreams E;
+    int rc = E.encode(W, P, first, count);
+    if (rc || E.jobs.empty()) return rc;
+    std::vector<BlockTableJob> bj;
+    std::vector<size_t> task;
+    uint64_t slots = 0, bytes = 0;
+    for (size_t k = 0; k < count; k++) {
+        if (E.job_of[k] == SIZE_MAX) continue;
+        const CSCMIDevEncode &j = E.jobs[E.job_of[k]];
+        const uint64_t mb = table_bound(j.produced, j.props.csc_blocksize);
+        if (mb > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
+        bj.push_back(BlockTableJob{(const uint8_t *)j.dst, (uint64_t)j.produced, j.props.csc_blocksize, (uint32_t)mb, slots});
+        task.push_back(first + k);
+        slots += mb;
+        bytes += ((uint64_t)j.produced + 15) & ~15ull;
+    }
+    std::vector<BlockTableRes> br;
+    std::vector<uint64_t> sizes;
+    rc = dev_block_tables(W, bj, task, std::vector<uint8_t>(bj.size(), 0), br, sizes);
+    if (rc) return rc;
+    IP.mem.emplace_back();
+    if (!IP.mem.back().alloc(bytes)) return CSCMI_DEVICE_ERROR;
+    IP.held_bytes += bytes;
+    IP.M.held_stream_bytes = std::max<uint64_t>(IP.M.held_stream_bytes, IP.held_bytes);
+    std::vector<CopyPiece> gp;
+    uint64_t off = 0;
+    size_t nx = 0;
+    for (size_t i = 0; i < bj.size(); i++) {
+        const CSCMIDevEncode &j = E.jobs[E.job_of[task[i] - first]];
+        HeldTask &h = IP.held[task[i]];
+        h.stream = (const uint8_t *)IP.mem.back().p + off;
+        h.produced = j.produced;
+        CSCEnc_WriteProperties(&j.props, h.props, 0);                          // csa_worker.cpp:38-42
+        uint64_t sum = 0;
+        for (uint32_t b = 0; b < br[i].nblocks; b++, nx++) { h.blocks.push_back(sizes[nx]); sum += sizes[nx]; }
+        if (sum != CSC_PROP_SIZE + h.produced) return CSCMI_DEVICE_ERROR;
+        piece_split((const uint8_t *)j.dst, (uint8_t *)IP.mem.back().p + off, h.produced, kGatherPiece, [&](uint64_t, const CopyPiece &p) { gp.push_back(p); });
+        off += (h.produced + 15) & ~15ull;
+    }
+    DevBuf d_gp;
+    if (gp.size() > 0x7FFFFFFFull || !dev_upload(W, d_gp, gp.data(), gp.size() * sizeof(CopyPiece))) return CSCMI_DEVICE_ERROR;
+    return W.tm.timed(&g_write_ms[3], W.S.launches, [&] { launch_gather_extents(d_gp.p, (uint32_t)gp.size(), W.tm.st); }) ? 0 : CSCMI_DEVICE_ERROR;
+}
+
+// The block tables of the reused streams, walked where they lie in the base: a stream of one base extent in place, one of several
+// staged back to back first (one k_gather_extents launch for all of them, as StagedStreams stages them for the read), kTableMaxJobs
+// streams a k_block_table launch.  0, CSCMI_DEVICE_ERROR, or -1: a stream does not end at its length.  Only reads the base.
+int dev_reused_tables(WriteCtx &W, UpdateCtx &U, AddPlan &P, InPlace &IP)
+{
+    using namespace csadev;
+    std::vector<size_t> R;
+    for (size_t i = 0; i < P.tasks.size(); i++) if (U.reused(i)) R.push_back(i);
+    if (R.empty()) return 0;
+    std::vector<uint64_t> gat_off(R.size(), 0);
+    uint64_t gat_bytes = 0;
+    std::vector<CopyPiece> gp;
+    for (size_t k = 0; k < R.size(); k++) {
+        const UpdTask &u = U.tasks[R[k]];
+        if (u.stream < CSC_PROP_SIZE) return -1;
+        if (u.ext.size() < 2) continue;
+        gat_off[k] = gat_bytes;
+        gat_bytes += (u.stream - CSC_PROP_SIZE + 255) & ~255ull;
+    }
+    DevBuf d_gat, d_gp;
+    if (gat_bytes) {
+        if (!d_gat.alloc(gat_bytes)) return CSCMI_DEVICE_ERROR;
+        for (size_t k = 0; k < R.size(); k++) {
+            const UpdTask &u = U.tasks[R[k]];
+            if (u.ext.size() < 2) continue;
+            uint64_t pos = 0;                                                    // position in the task's stream
+            for (const Extent &x : u.ext) {
+                const uint64_t skip = pos < CSC_PROP_SIZE ? std::min<uint64_t>(CSC_PROP_SIZE - pos, x.size) : 0;
+                if (x.size > skip)
+                    piece_split(U.base->arc + x.off + skip, (uint8_t *)d_gat.p + gat_off[k] + (pos + skip - CSC_PROP_SIZE), x.size - skip, kGatherPiece,
+                                [&](uint64_t, const CopyPiece &p) { gp.push_back(p); });
+                pos += x.size;
+            }
+        }
+        if (gp.size() > 0x7FFFFFFFull || !dev_upload(W, d_gp, gp.data(), gp.size() * sizeof(CopyPiece))) return CSCMI_DEVICE_ERROR;
+        if (!W.tm.timed(&g_write_ms[3], W.S.launches, [&] { launch_gather_extents(d_gp.p, (uint32_t)gp.size(), W.tm.st); })) return CSCMI_DEVICE_ERROR;
+    }
+    for (size_t first = 0; first < R.size(); first += kTableMaxJobs) {
+        const size_t count = std::min<size_t>(kTableMaxJobs, R.size() - first);
+        std::vector<BlockTableJob> bj;
+        std::vector<size_t> task;
+        uint64_t slots = 0;
+        for (size_t k = first; k < first + count; k++) {
+            const UpdTask &u = U.tasks[R[k]];
+            CSCProps props;                                                      // (the stream's 10 bytes are these props': dev_check_wave)
+            CSCEncProps_Init(&props, (uint32_t)std::min<uint64_t>(P.o.dict_size, P.tasks[R[k]].total), P.o.level);
+            const uint64_t produced = u.stream - CSC_PROP_SIZE, mb = table_bound(produced, props.csc_blocksize);
+            if (mb > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
+            const uint8_t *stream = u.ext.size() < 2 ? U.base->arc + u.ext[0].off + CSC_PROP_SIZE : (const uint8_t *)d_gat.p + gat_off[k];
+            bj.push_back(BlockTableJob{stream, produced, props.csc_blocksize, (uint32_t)mb, slots});
+            task.push_back(R[k]);
+            slots += mb;
+        }
+        std::vector<BlockTableRes> br;
+        std::vector<uint64_t> sizes;
+        const int rc = dev_block_tables(W, bj, task, std::vector<uint8_t>(count, 1), br, sizes);
+        if (rc) return rc;
+        size_t nx = 0;
+        for (size_t i = 0; i < count; i++) {
+            HeldTask &h = IP.held[task[i]];
+            uint64_t sum = 0;
+            for (uint32_t b = 0; b < br[i].nblocks; b++, nx++) { h.blocks.push_back(sizes[nx]); sum += sizes[nx]; }
+            if (sum != U.tasks[task[i]].stream) return -1;
+        }
+    }
+    return 0;
+}
+
+// One phase of the moves: the chunk table up, the state block zeroed, the launch, the error word back.
+int dev_move_phase(WriteCtx &W, const std::vector<csadev::MoveChunk> &chunks, DevBuf &d_chunks, DevBuf &d_state, size_t state_bytes, InPlace &IP, double *ms)
+{
+    uint32_t state[csadev::kMoveStateWords] = {0, 0, 0, 0};
+    const double before = *ms;
+    if (!W.tm.timed(ms, IP.M.launches, [&] {
+            launch_move_extents(d_chunks.p, (uint32_t)chunks.size(), W.arc, IP.buf_cap, d_state.p, state_bytes, W.tm.st); })) return CSCMI_DEVICE_ERROR;
+    IP.M.kernel_ms += *ms - before;
+    if (!HIP_OK(hipMemcpy(state, d_state.p, sizeof(state), hipMemcpyDeviceToHost))) return CSCMI_DEVICE_ERROR;
+    if (state[1]) {
+        fprintf(stderr, "csa-mi355x: k_move_extents: ticket %u gave up waiting for the chunks in front of it\n", state[1] - 1);
+        return CSCMI_DEVICE_ERROR;
+    }
+    return 0;
+}
+
+// The last refusal, then the stores: WRITE_ERROR with the buffer untouched if header, streams and index pass buf_cap; else the
+// reused streams move to their places (park, left phase, right phase) and one k_gather_extents launch places the held streams with
+// their property bytes, the parked streams, the index stream `job` and the header.  Every table and every byte of scratch is
+// there before the first launch, so that from then on only a failing launch can end the call.
+int dev_move_and_place(WriteCtx &W, UpdateCtx &U, AddPlan &P, InPlace &IP, const CSCMIDevEncode &job, const uint8_t *hdr)
+{
+    using namespace csadev;
+    uint64_t end;
+    if (!add_ok(W.arc_end, CSC_PROP_SIZE + (uint64_t)job.produced, &end) || end > IP.buf_cap) return WRITE_ERROR;
+    std::vector<Move> moves;
+    for (size_t i = 0; i < P.tasks.size(); i++) {
+        if (!U.reused(i)) continue;
+        uint64_t d = IP.at[i];
+        for (const Extent &x : U.tasks[i].ext) { moves.push_back(Move{x.off, d, x.size}); d += x.size; }
+    }
+    MovePlan MP;
+    plan_moves(moves, MP);
+    if (MP.phase[0].size() > 0x7FFFFFFFull || MP.phase[1].size() > 0x7FFFFFFFull) return CSCMI_DEVICE_ERROR;
+    IP.M.moves = MP.moves; IP.M.moved_bytes = MP.moved_bytes; IP.M.parked_moves = MP.parked_moves; IP.M.parked_bytes = MP.parked_bytes;
+    // scratch and tables
+    DevBuf d_park, d_pp, d_chunks[2], d_state, d_host, d_gp;
+    std::vector<CopyPiece> pp, gp;
+    std::vector<uint64_t> park_off;
+    uint64_t park_bytes = 0;
+    for (const Move &m : MP.parked) { park_off.push_back(park_bytes); park_bytes += (m.len + 15) & ~15ull; }
+    if (park_bytes && !d_park.alloc(park_bytes)) return CSCMI_DEVICE_ERROR;
+    auto put = [&](uint64_t, const CopyPiece &p) { gp.push_back(p); };
+    for (size_t k = 0; k < MP.parked.size(); k++) {
+        piece_split(W.arc + MP.parked[k].src, (uint8_t *)d_park.p + park_off[k], MP.parked[k].len, kGatherPiece, [&](uint64_t, const CopyPiece &p) { pp.push_back(p); });
+        piece_split((const uint8_t *)d_park.p + park_off[k], W.arc + MP.parked[k].dst, MP.parked[k].len, kGatherPiece, put);
+    }
+    // the bytes that come from the host: the header and the property bytes of every encoded stream and of the index stream
+    std::vector<uint8_t> host(hdr, hdr + kHeaderSize);
+    for (size_t i = 0; i < P.tasks.size(); i++)
+        if (!U.reused(i)) host.insert(host.end(), IP.held[i].props, IP.held[i].props + CSC_PROP_SIZE);
+    uint8_t iprops[CSC_PROP_SIZE];
+    CSCEnc_WriteProperties(&job.props, iprops, 0);
+    host.insert(host.end(), iprops, iprops + CSC_PROP_SIZE);
+    if (!dev_upload(W, d_host, host.data(), host.size())) return CSCMI_DEVICE_ERROR;
+    gp.push_back(CopyPiece{(const uint8_t *)d_host.p, W.arc, (uint32_t)kHeaderSize, 0});
+    uint64_t hp = kHeaderSize;
+    for (size_t i = 0; i < P.tasks.size(); i++) {
+        if (U.reused(i)) continue;
+        gp.push_back(CopyPiece{(const uint8_t *)d_host.p + hp, W.arc + IP.at[i], CSC_PROP_SIZE, 0});
+        piece_split(IP.held[i].stream, W.arc + IP.at[i] + CSC_PROP_SIZE, IP.held[i].produced, kGatherPiece, put);
+        hp += CSC_PROP_SIZE;
+    }
+    gp.push_back(CopyPiece{(const uint8_t *)d_host.p + hp, W.arc + W.arc_end, CSC_PROP_SIZE, 0});
+    piece_split((const uint8_t *)job.dst, W.arc + W.arc_end + CSC_PROP_SIZE, job.produced, kGatherPiece, put);
+    if (gp.size() > 0x7FFFFFFFull || pp.size() > 0x7FFFFFFFull || !dev_upload(W, d_gp, gp.data(), gp.size() * sizeof(CopyPiece))
+        || (!pp.empty() && !dev_upload(W, d_pp, pp.data(), pp.size() * sizeof(CopyPiece)))) return CSCMI_DEVICE_ERROR;
+    const size_t nflags = std::max(MP.phase[0].size(), MP.phase[1].size());
+    const size_t state_bytes = ((kMoveStateWords + nflags) * sizeof(uint32_t) + 15) & ~(size_t)15;
+    for (int ph = 0; ph < 2; ph++)
+        if (!MP.phase[ph].empty() && !dev_upload(W, d_chunks[ph], MP.phase[ph].data(), MP.phase[ph].size() * sizeof(MoveChunk))) return CSCMI_DEVICE_ERROR;
+    if (nflags && !d_state.alloc(state_bytes)) return CSCMI_DEVICE_ERROR;
+    // ---- from here on the buffer is written
+    if (!pp.empty()) {
+        const double before = g_move_ms[0];
+        if (!W.tm.timed(&g_move_ms[0], IP.M.launches, [&] { launch_gather_extents(d_pp.p, (uint32_t)pp.size(), W.tm.st); })) return CSCMI_DEVICE_ERROR;
+        IP.M.kernel_ms += g_move_ms[0] - before;
+    }
+    for (int ph = 0; ph < 2; ph++) {
+        if (MP.phase[ph].empty()) continue;
+        const int rc = dev_move_phase(W, MP.phase[ph], d_chunks[ph], d_state, state_bytes, IP, &g_move_ms[1 + ph]);
+        if (rc) return rc;
+    }
+    if (!W.tm.timed(&g_write_ms[3], W.S.launches, [&] { launch_gather_extents(d_gp.p, (uint32_t)gp.size(), W.tm.st); })) return CSCMI_DEVICE_ERROR;
+    W.arc_end = end;
     return 0;
 }
 
@@ -1858,14 +2126,15 @@ int CSAMI_DeviceUpdate(CSADevArchive *base, const void *const *ptrs, const uint6
                                      update_stats, tasks, task_cap, nullptr, 0, nullptr);
 }
 
-int CSAMI_DeviceUpdateDigests(CSADevArchive *base, const CSADevDigest *base_digests, uint64_t n_base_digests, const void *const *ptrs,
-                              const uint64_t *sizes, const CSADevSlice *slices, CSADevFile *files, uint32_t n_files, const char *arcname,
-                              void *arc_dev, uint64_t arc_cap, uint32_t flags, const CSAOptions *opt, CSADevWriteStats *st,
-                              CSADevGatherStats *gather_stats, CSADevUpdateStats *update_stats, CSADevUpdateTask *tasks, uint32_t task_cap,
-                              CSADevDigest *digests_out, uint64_t digests_cap, CSADevDigestStats *ds)
+// CSAMI_DeviceUpdateDigests, and with `ip` CSAMI_DeviceUpdateInPlace: the same refusals, plan, candidates, digest pass, check waves
+// and index; what differs is where the streams go, and when (arc_dev and arc_cap are then the base's buffer and ip->buf_cap).
+static int dev_update(CSADevArchive *base, const CSADevDigest *base_digests, uint64_t n_base_digests, const void *const *ptrs,
+                      const uint64_t *sizes, const CSADevSlice *slices, CSADevFile *files, uint32_t n_files, const char *arcname,
+                      void *arc_dev, uint64_t arc_cap, uint32_t flags, const CSAOptions *opt, CSADevWriteStats *st,
+                      CSADevGatherStats *gather_stats, CSADevUpdateStats *update_stats, CSADevUpdateTask *tasks, uint32_t task_cap,
+                      CSADevDigest *digests_out, uint64_t digests_cap, CSADevDigestStats *ds, InPlace *ip)
 {
     const double t0 = now_s();
-    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
     WriteCtx W;
     UpdateCtx U;
     DigestCall dg = {digests_out, base_digests, CSADevDigestStats()};
@@ -1882,6 +2151,7 @@ int CSAMI_DeviceUpdateDigests(CSADevArchive *base, const CSADevDigest *base_dige
     // ---- everything the host can refuse, before any launch
     uint64_t a1;
     if (!arcname || (!arc_dev && arc_cap) || !add_ok((uintptr_t)arc_dev, arc_cap, &a1) || (n_files && (!ptrs || !files || !sizes != !slices))) return -1;
+    if (ip && !base) return -1;
     AddPlan P;
     int rc = plan_write(P, files, n_files, opt, &W.S.raw_bytes);
     if (rc) return rc;
@@ -1893,7 +2163,8 @@ int CSAMI_DeviceUpdateDigests(CSADevArchive *base, const CSADevDigest *base_dige
     CSADevGatherStats G = W.G;
     if (check_sources(ptrs, sizes, slices, files, n_files, sl, hull, hull_size, G) != 0) return -1;
     if (CSAMI_CheckBuffers(hull.data(), hull_size.data(), n_files, arc_dev, arc_cap, 0, nullptr) != 0) return -1;
-    if (base && arc_cap && base->arc_size) {                                 // the base is read while arc is written: updating in place is out of scope
+    if (ip && arc_cap < base->arc_size) return -1;
+    if (!ip && base && arc_cap && base->arc_size) {                          // the base is read while arc is written: CSAMI_DeviceUpdateInPlace is the call for that
         const uint64_t b0 = (uint64_t)(uintptr_t)base->arc, x0 = (uint64_t)(uintptr_t)arc_dev;
         if (x0 <= b0 + (base->arc_size - 1) && b0 <= x0 + (arc_cap - 1)) return -1;
     }
@@ -1980,6 +2251,7 @@ int CSAMI_DeviceUpdateDigests(CSADevArchive *base, const CSADevDigest *base_dige
     // ---- waves of consecutive task ids, largest first (csarc.cpp:355): the plan's order and the archive's
     size_t width = P.o.device_streams > 0 ? (size_t)P.o.device_streams : csadev::kTableMaxJobs;
     width = std::min<size_t>(width, csadev::kTableMaxJobs);
+    if (ip) ip->held.resize(P.tasks.size());
     for (size_t first = 0; rc == 0 && first < P.tasks.size();) {
         // what the task's encoder holds (as encode_tasks reckons), a gathered copy of its input (at most) and its scratch stream;
         // a reused task holds nothing
@@ -1990,10 +2262,19 @@ int CSAMI_DeviceUpdateDigests(CSADevArchive *base, const CSADevDigest *base_dige
             CSCEncProps_Init(&p, (uint32_t)std::min<uint64_t>(P.o.dict_size, t.total), P.o.level);
             return (uint64_t)(CSCEnc_EstMemUsage(&p) + (24ull << 20) + t.total + stream_cap(W, t.total));
         });
-        rc = dev_write_wave(W, P, first, count);
+        rc = ip ? dev_hold_wave(W, P, first, count, *ip) : dev_write_wave(W, P, first, count);
         W.S.waves++;
         for (size_t k = first; k < first + count; k++) { W.S.tasks++; W.S.frags += P.tasks[k].files.size(); }
         first += count;
+    }
+    // in place: the reused streams' tables where they lie in the base, then -- every size is known -- the layout
+    if (ip && rc == 0) rc = dev_reused_tables(W, U, P, *ip);
+    if (ip && rc == 0) {
+        for (size_t i = 0; i < P.tasks.size(); i++) {
+            ip->at.push_back(W.arc_end);
+            std::vector<Extent> &ext = W.abindex[i];
+            for (uint64_t n : ip->held[i].blocks) { ext.push_back(Extent{W.arc_end, n}); W.arc_end += n; }
+        }
     }
     for (size_t i = 0; W.upd && i < P.tasks.size(); i++) {
         const UpdTask &u = U.tasks[i];
@@ -2029,7 +2310,18 @@ int CSAMI_DeviceUpdateDigests(CSADevArchive *base, const CSADevDigest *base_dige
             store_le(hdr + 8, W.arc_end, 8);
             store_le(hdr + 16, csize, 4);
             store_le(hdr + 20, raw.size(), 4);
-            rc = dev_place(W, std::vector<Placed>(1, Placed{&job[0], nullptr, nullptr, 0}), hdr);
+            rc = ip ? dev_move_and_place(W, U, P, *ip, job[0], hdr) : dev_place(W, std::vector<Placed>(1, Placed{&job[0], nullptr, nullptr, 0}), hdr);
+        }
+        if (rc == 0 && ip) {                                                 // the handle describes the new archive, as CSAMI_DeviceOpen would
+            Index index;
+            BlockIndex abindex;
+            std::map<uint64_t, uint64_t> task_raw;
+            if (!unpack_index(index, abindex, raw.data(), raw.size()) || !dev_task_sizes(index, task_raw)) rc = CSCMI_DEVICE_ERROR;
+            else {
+                base->index.swap(index); base->abindex.swap(abindex); base->task_raw.swap(task_raw);
+                base->arc_size = W.arc_end;
+                base->open_readback = kHeaderSize + CSC_PROP_SIZE + raw.size();
+            }
         }
         if (rc == 0) {
             W.S.index_raw_size = raw.size();
@@ -2049,6 +2341,41 @@ int CSAMI_DeviceUpdateDigests(CSADevArchive *base, const CSADevDigest *base_dige
     if (update_stats) *update_stats = U.U;
     if (ds) *ds = dg.ds;
     return rc;
+}
+
+int CSAMI_DeviceUpdateDigests(CSADevArchive *base, const CSADevDigest *base_digests, uint64_t n_base_digests, const void *const *ptrs,
+                              const uint64_t *sizes, const CSADevSlice *slices, CSADevFile *files, uint32_t n_files, const char *arcname,
+                              void *arc_dev, uint64_t arc_cap, uint32_t flags, const CSAOptions *opt, CSADevWriteStats *st,
+                              CSADevGatherStats *gather_stats, CSADevUpdateStats *update_stats, CSADevUpdateTask *tasks, uint32_t task_cap,
+                              CSADevDigest *digests_out, uint64_t digests_cap, CSADevDigestStats *ds)
+{
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
+    return dev_update(base, base_digests, n_base_digests, ptrs, sizes, slices, files, n_files, arcname, arc_dev, arc_cap, flags, opt, st, gather_stats,
+                      update_stats, tasks, task_cap, digests_out, digests_cap, ds, nullptr);
+}
+
+int CSAMI_DeviceUpdateInPlace(CSADevArchive *base, uint64_t buf_cap, const CSADevDigest *base_digests, uint64_t n_base_digests,
+                              const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices, CSADevFile *files, uint32_t n_files,
+                              const char *arcname, uint32_t flags, const CSAOptions *opt, CSADevWriteStats *st, CSADevGatherStats *gather_stats,
+                              CSADevUpdateStats *update_stats, CSADevUpdateTask *tasks, uint32_t task_cap, CSADevDigest *digests_out,
+                              uint64_t digests_cap, CSADevDigestStats *ds, CSADevMoveStats *ms)
+{
+    if (CSCMI_DeviceCheck() != 0) return CSCMI_DEVICE_ERROR;
+    InPlace IP;
+    IP.buf_cap = buf_cap;
+    memset(&IP.M, 0, sizeof(IP.M));
+    for (double &m : g_move_ms) m = 0;
+    if (ms) *ms = IP.M;
+    // (without a base there is no buffer: the statistics are zeroed as dev_update zeroes them on every refusal)
+    const int rc = dev_update(base, base_digests, n_base_digests, ptrs, sizes, slices, files, n_files, arcname, base ? const_cast<uint8_t *>(base->arc) : nullptr,
+                              base ? buf_cap : 0, flags, opt, st, gather_stats, update_stats, tasks, task_cap, digests_out, digests_cap, ds, &IP);
+    if (ms) *ms = IP.M;
+    return rc;
+}
+
+void CSAMI_DeviceMoveKernelMs(double ms[3])
+{
+    for (int i = 0; i < 3; i++) ms[i] = g_move_ms[i];
 }
 
 int CSAMI_PlanDeviceUpdate(const uint8_t *raw_index, uint64_t raw_size, uint64_t arc_size, const CSADevFile *files, uint32_t n_files,

@@ -28,6 +28,9 @@
 //                         serial chain of up to 256 compressions, so the parallelism is across leaves
 //   k_digest_roots        one lane per fragment: the root over its leaves' digests, stored to the digest table and compared with an
 //                         expected table where one is given; one word a fragment is all the host reads back
+//   k_move_extents        one workgroup per <= 32 KiB chunk of a move INSIDE the archive buffer (CSAMI_DeviceUpdateInPlace): memmove for a
+//                         whole move list in one launch -- a chunk into registers, a flag, a wait for the chunks whose sources its
+//                         destination meets, the stores (csa_dev_move.h)
 //
 // Every address in the tables was validated by the host before the launch; a workgroup touches src[0, len) and dst[0, len) of its
 // piece and nothing else.
@@ -37,6 +40,7 @@
 #include "csa_dev_read.h"
 #include "csa_dev_write.h"
 #include "csa_dev_digest.h"
+#include "csa_dev_move.h"
 
 using namespace csadev;
 
@@ -312,4 +316,67 @@ void launch_digest_roots(const void *frags, const void *leaves, void *out, const
 {
     hipLaunchKernelGGL(k_digest_roots, dim3(nfrags ? (nfrags + kDigestThreads - 1) / kDigestThreads : 1), dim3(kDigestThreads), 0, st,
                        (const DigestFrag *)frags, (const DigestWords *)leaves, (uint8_t *)out, (const uint8_t *)expect, (uint32_t *)differs, nfrags);
+}
+
+// memmove for a move list (csa_dev_move.h: the plan, the order, the thread's loads and stores).  `state` is one block the launcher
+// zeroes: the ticket counter, the error word, two words of padding, then one flag a chunk.
+//
+// A workgroup draws its ticket with one atomic add when it starts, and the ticket -- not blockIdx -- selects its chunk.  It loads
+// the whole chunk into registers, every wave waits for its loads, and behind the barrier one lane sets the chunk's flag: a global,
+// agent-scope atomic store.  What crosses workgroups is that flag alone, and what it orders is a write after a read: no byte one
+// workgroup stores is loaded by another in this launch (a load window may hold such bytes; the funnel shift drops them), so there
+// is no payload to release or acquire.  Then the lanes of the first wave poll the flags lo..hi of its chunk, lane-strided, relaxed
+// and agent-scope, with s_sleep between sweeps; behind a second barrier the workgroup stores.
+//
+// Progress, whatever the residency: a workgroup waits only for tickets LOWER than its own.  A lower ticket was drawn by a workgroup
+// that had started before this one drew its own, so it is running, and between its start and its flag there is no wait at all:
+// the flag store needs nothing from anyone.  So every flag a workgroup polls is set after a bounded time, whether one workgroup is
+// resident or all of them.  Nothing here waits for a higher ticket, there is no grid barrier and no cooperative launch.
+//
+// Every spin is bounded all the same: at kMoveSpins sweeps the workgroup sets the error word (its ticket + 1) and leaves without
+// storing.  The host reads the word back and returns CSCMI_DEVICE_ERROR: a mistake in the plan fails a test and holds no card.
+constexpr uint32_t kMoveSpins = 1u << 22;       // sweeps of >= 512 clocks each: about a second, a million times what a flag takes
+
+__global__ __launch_bounds__(kThreads) void k_move_extents(const MoveChunk *chunks, uint32_t nchunks, uint8_t *buf, uint64_t cap, uint32_t *state)
+{
+    __shared__ uint32_t s_ticket, s_go;
+    if (threadIdx.x == 0) s_ticket = __hip_atomic_fetch_add(state, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const uint32_t ticket = s_ticket;
+    if (ticket >= nchunks) return;                                       // (the same for the whole workgroup)
+    const MoveChunk c = chunks[ticket];
+    uint32_t *flags = state + kMoveStateWords;
+    MoveRegs r;
+    move_load(c, buf, buf, buf + cap, threadIdx.x, kThreads, r);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) __hip_atomic_store(flags + ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (threadIdx.x < 64) {
+        bool go = true;
+        if (c.lo != kMoveNone) {
+            for (uint32_t spins = 0;; spins++) {
+                bool set = true;
+                for (uint32_t j = c.lo + threadIdx.x; j <= c.hi; j += 64)
+                    set = set && __hip_atomic_load(flags + j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0;
+                if (__all(set)) break;
+                if (spins >= kMoveSpins) { go = false; break; }          // (uniform: __all's result and the counter are)
+                __builtin_amdgcn_s_sleep(8);
+            }
+        }
+        if (threadIdx.x == 0) {
+            s_go = go;
+            if (!go) __hip_atomic_store(state + 1, ticket + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    __syncthreads();
+    if (!s_go) return;
+    move_store(c, buf, threadIdx.x, kThreads, r);
+}
+
+// the state block zeroed, then the launch: one workgroup a chunk
+void launch_move_extents(const void *chunks, uint32_t nchunks, void *buf, uint64_t cap, void *state, size_t state_bytes, hipStream_t st)
+{
+    (void)hipMemsetAsync(state, 0, state_bytes, st);
+    hipLaunchKernelGGL(k_move_extents, dim3(nchunks ? nchunks : 1), dim3(kThreads), 0, st, (const MoveChunk *)chunks, nchunks, (uint8_t *)buf, cap,
+                       (uint32_t *)state);
 }

@@ -26,6 +26,7 @@ void launch_frag_fold_diff(const void *frags, const void *sums, const void *firs
 void launch_digest_leaves(const void *leaves, void *out, uint32_t nleaves, hipStream_t st);
 void launch_digest_roots(const void *frags, const void *leaves, void *out, const void *expect, void *differs, uint32_t nfrags, hipStream_t st);
 void launch_block_table(const void *jobs, uint32_t njobs, void *scratch, void *res, void *sizes, hipStream_t st);
+void launch_move_extents(const void *chunks, uint32_t nchunks, void *buf, uint64_t cap, void *state, size_t state_bytes, hipStream_t st);
 
 #define HIP_OK(x) ((x) == hipSuccess)
 

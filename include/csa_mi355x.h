@@ -621,7 +621,7 @@ int CSAMI_DeviceCompareSlices(CSADevArchive *a, const char *const *names, int nn
  * walk finds a reused stream that does not end at its length the call returns -1 (in verify: unreachable for an intact decoder).
  * gather_stats and st->retries count encoded tasks only; st->tasks, frags, blocks, raw_bytes and archive_bytes mean what they mean
  * for the write.  tasks[i], i < min(task_cap, st->tasks), says what became of task i of the new plan.
- * Out of scope: updating in place (arc inside the base buffer), reusing part of a task, and the host paths. */
+ * Updating in place (arc inside the base buffer) is CSAMI_DeviceUpdateInPlace's.  Out of scope: reusing part of a task, and the host paths. */
 #define CSAMI_UPDATE_TRUST_SUMS 1u
 typedef struct CSADevUpdateTask { uint64_t base_bid; uint32_t status; uint32_t reserved; } CSADevUpdateTask;   /* per task of the NEW plan, in id order */
 /* status */
@@ -727,6 +727,45 @@ int CSAMI_DeviceReadDigests(CSADevArchive *a, const CSAOptions *o, CSADevDigest 
                             const CSADevDigest *expect, CSADevReadStats *st, CSADevDigestStats *ds);
 /* HIP-event milliseconds of this thread's last digesting call by kernel: [0] k_digest_leaves, [1] k_digest_roots; ds->kernel_ms is their sum */
 void CSAMI_DeviceDigestKernelMs(double ms[2]);
+
+/* ---- the update in place: the new archive takes the base's place in the caller's buffer ----
+ * CSAMI_DeviceUpdateDigests without a second buffer: `base` was opened at the first byte of a buffer of buf_cap bytes (buf_cap >= the
+ * base's size), and on return 0 buf[0, st->archive_bytes) is byte for byte what CSAMI_DeviceUpdateDigests writes into a separate
+ * buffer for the same arguments.  Every other argument means what it means there -- flags, refusals and the three check modes
+ * (verify, CSAMI_UPDATE_TRUST_SUMS, CSAMI_UPDATE_TRUST_DIGESTS) included --, with [base's first byte, + buf_cap) in the place of
+ * both the base buffer and arc: no hull and neither digest table may meet it.  -1 also for base == NULL and buf_cap < the base's size.
+ * tasks[], update_stats, gather_stats, ds and digests_out are that call's; st is that call's except for launches, waves,
+ * kernel_ms, upload_bytes, readback_bytes and the times.  st->launches <= 5 * st->waves + 2 + ceil(reused tasks / 2048): a wave
+ * with a task to encode is at most three launches of gather, sums and fold, one k_block_table and one k_gather_extents that
+ * compacts its streams into held memory; the reused streams are one k_gather_extents (only where a base stream lies in more than
+ * one extent) and one k_block_table per 2048 of them; the final placement is one k_gather_extents.  The moves are ms->launches, at
+ * most three.
+ * On success the handle describes the new archive exactly as CSAMI_DeviceOpen(buf, st->archive_bytes) would: the next read or
+ * update on it needs no reopen.
+ * EVERY REFUSAL COMES BEFORE THE FIRST STORE INTO THE BUFFER: bad arguments, a failed plan, -1 for a reused stream whose
+ * block-table walk does not end at its length, and WRITE_ERROR where header, streams and index do not fit buf_cap.  After any of
+ * these the buffer is byte for byte the base and the handle still describes it.  The order that gives this: the check waves and
+ * the encode waves only read the base, and the encoded streams are held in scratch (ms->held_stream_bytes at its peak) until every
+ * size is known; then the reused streams move inside the buffer (k_move_extents) and the rest is placed.
+ * ONCE THE FIRST MOVE HAS BEEN LAUNCHED ONLY CSCMI_DEVICE_ERROR CAN COME BACK, AND THEN THE BUFFER IS LOST: it holds neither the
+ * base nor the new archive, and the handle must be closed. */
+typedef struct CSADevMoveStats {
+    uint64_t moves, moved_bytes;              /* after dropping src == dst and coalescing neighbours of one shift */
+    uint64_t parked_moves, parked_bytes;      /* of those: copied to scratch before the left phase, placed from there at the end */
+    uint64_t held_stream_bytes;               /* encoded streams kept in scratch until placement, at its peak */
+    uint64_t launches;                        /* this layer's: park, left, right */
+    double kernel_ms;
+} CSADevMoveStats;
+int CSAMI_DeviceUpdateInPlace(CSADevArchive *base, uint64_t buf_cap,
+                              const CSADevDigest *base_digests, uint64_t n_base_digests,
+                              const void *const *ptrs, const uint64_t *sizes, const CSADevSlice *slices,
+                              CSADevFile *files, uint32_t n_files, const char *arcname,
+                              uint32_t flags, const CSAOptions *o, CSADevWriteStats *st, CSADevGatherStats *gather_stats,
+                              CSADevUpdateStats *update_stats, CSADevUpdateTask *tasks, uint32_t task_cap,
+                              CSADevDigest *digests_out, uint64_t digests_cap, CSADevDigestStats *ds, CSADevMoveStats *ms);
+/* HIP-event milliseconds of this thread's last CSAMI_DeviceUpdateInPlace by launch: [0] the park copy, [1] k_move_extents' left
+ * phase, [2] its right phase; ms->kernel_ms is their sum */
+void CSAMI_DeviceMoveKernelMs(double ms[3]);
 
 /* YYYYMMDDHHMMSS <-> time_t, csa_common.cpp:3-39 */
 int64_t CSA_DecimalTime(int64_t unix_seconds);
