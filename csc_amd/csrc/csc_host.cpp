@@ -328,7 +328,7 @@ struct ThreadRes {
 thread_local ThreadRes t_res;
 #define t_batch (t_res.batch)
 constexpr int kMaxBatch = 2048;
-constexpr size_t kBatchPool = 64ull << 20;       // most a batch reads back per wait; >= the arena of the largest raw_blocksize (3 x 16 MiB + 1 MiB)
+constexpr size_t kBatchPool = 64ull << 20;       // most a batch reads back per wait, unless one stream's arena alone is larger (tiny csc_blocksize: arena_bytes)
 constexpr size_t kPinMin = 256 * 1024;
 
 // the calling thread's pinned read-back buffer, at least `need` bytes (nullptr: allocation failed)
@@ -395,6 +395,20 @@ int write_arena(EncInstance *e, const uint8_t *h_arena, uint32_t used)
         off += 16 + ((rec->size + 15) & ~15u);
     }
     return 0;
+}
+
+// Bytes of output arena a chunk can need.  A chunk of raw_blocksize bytes is budgeted B = 3 * raw_blocksize + 1 MiB of coded bytes, as
+// it always was.  emit_block (csc_kernels.hip) stores them as records of 16 + round16(size) bytes: full blocks of size == bsize while
+// a coder buffer fills -- at most B / bsize of them, each 16 + pad bytes over its payload, pad = round16(bsize) - bsize -- and the two
+// blocks of Coder::Flush, of any size up to bsize, each at most 16 + 15 bytes over its payload.  So
+//     cap = B + (B / bsize) * (16 + pad) + 2 * 31
+// which is B + 1.8 KiB at the default 64 KiB blocks and 32 B at bsize 1.  With raw_blocksize and bsize below 16 MiB (CSCEnc_Create
+// refuses the rest) this stays below 2^31, inside the device's 32-bit arena offsets.
+uint32_t arena_bytes(uint32_t raw_blocksize, uint32_t bsize)
+{
+    const uint64_t B = 3ull * raw_blocksize + kMB;
+    const uint64_t pad = ((bsize + 15u) & ~15u) - bsize;
+    return (uint32_t)(B + B / bsize * (16 + pad) + 2 * 31);
 }
 
 int report_device_error(uint32_t err)
@@ -507,7 +521,6 @@ int drain_batch(int n, CSCEncHandle *hs, const size_t *skip, hipStream_t st)
     for (int i = 0; i < n; i++) {
         if (skip && !skip[i]) continue;
         if (sm[2 * i + 1] != ERR_NONE) rc = report_device_error(sm[2 * i + 1]);
-        else if ((size_t)sm[2 * i] > kBatchPool) { fprintf(stderr, "csc-mi355x: a stream's coder blocks exceed the read-back pool\n"); rc = CSCMI_DEVICE_ERROR; }
     }
     if (rc) return rc;
     // the pool: what this batch reads back (a round's worth at most), not a fixed 64 MiB -- a CSCMI_FlushBatch needs a few KiB
@@ -668,7 +681,7 @@ CSCEncHandle CSCEnc_Create(const CSCProps *props, ISeqOutStream *outstream, ISzA
     h.lz_bt_cyc = props->bt_cyc; h.lz_ht_cyc = props->hash_width;
     h.mf_size = (uint64_t)kHT2Size + kHT3Size + ((uint64_t)h.ht_width << h.ht_bits);
     if (h.bt_bits) h.mf_size += ((uint64_t)1 << h.bt_bits) + (uint64_t)h.bt_size * 2;
-    h.arena_cap = 3 * props->raw_blocksize + kMB;
+    h.arena_cap = arena_bytes(props->raw_blocksize, props->csc_blocksize);
     h.filt_flags = (props->DLTFilter ? 1u : 0u) | (props->TXTFilter ? 2u : 0u) | (props->EXEFilter ? 4u : 0u);
 
     // ---- one device slab, zero-filled: memset(wnd_, 0, ..) csc_lz.cpp:50, the tables csc_mf.cpp:73, and the

@@ -101,6 +101,75 @@ void orc_trace_attach(CSCEncHandle h, struct OrcTrace *t);
 const uint32_t *orc_trace_rows(const struct OrcTrace *t, int kind, size_t *count);
 void orc_trace_free(struct OrcTrace *t);
 
+/* ---- census: how often the encoder took each named rare branch of the reference while a stream was encoded (tests/census_cases.py,
+ * tools/make_census_cases.py).  Off unless a counter array of ORC_EV_COUNT words is attached to the handle right after CSCEnc_Create
+ * (NULL detaches); per handle, so encodes on several threads do not share counters.  Detached, an event costs one predictable branch.
+ * Each event is defined where it is counted in orc_encoder.c, beside the reference lines of its branch. */
+enum OrcEvent {
+    /* coder */
+    ORC_EV_RC_CARRY_CACHE2,       /* a carry propagated through cache byte + >= 1 FF byte (rc_cachesize >= 2) */
+    ORC_EV_RC_CARRY_CACHE3,       /* ... through >= 2 FF bytes */
+    ORC_EV_RC_FF_RUN2,            /* rc_cachesize >= 2 flushed without a carry (FF bytes really written) */
+    ORC_EV_RC_SEAM,               /* an RC block filled */
+    ORC_EV_RC_SEAM_MID,           /* ... with bytes of the same RC_ShiftLow emission still to come */
+    ORC_EV_BC_SEAM,               /* a BC block filled */
+    ORC_EV_RC_BC_SEAM_PACKET,     /* both inside one packet (EncodeMatch is the only packet that feeds both coders) */
+    ORC_EV_FLUSH,
+    ORC_EV_FLUSH_STALE_NZ,        /* the byte Flush counts but never stores is not zero in the buffer */
+    ORC_EV_FLUSH_BSIZE_M1,        /* Flush arrives at rc_size + 1 == csc_blocksize: the short header goes missing */
+    ORC_EV_FLUSH_AFTER_SEAM,      /* Flush's five bytes end exactly on a seam (rc_size == 0) */
+    ORC_EV_FLUSH_BC_EMPTY,        /* Flush's two BC bytes end exactly on a seam: an empty BC block is written, which the decoder refuses */
+    /* model */
+    ORC_EV_LEN_CHAIN1,            /* match length 143 .. 285: the 143 escape once */
+    ORC_EV_LEN_CHAIN2,            /* >= 286: the p_longlen loop runs */
+    ORC_EV_LEN_PRICE_REBUILD,
+    /* MatchFinder::SlidePos */
+    ORC_EV_SP_SKIP,               /* i + 128 < len: four positions a step, no bucket / tree insert */
+    ORC_EV_SP_NOSHIFT,            /* h6 == lasth6: slot 0 overwritten without shifting the bucket */
+    ORC_EV_SP_BT_POS_WRAP,
+    ORC_EV_SP_BT_CYC,             /* descent ended by cyc >= bt_cyc */
+    ORC_EV_SP_GOOD_LEN_SPLICE,    /* clen >= good_len: the node takes the matched node's children */
+    ORC_EV_SP_CLIMIT_WND,         /* climit set by the window's end, not by the block */
+    /* MatchFinder::find_match */
+    ORC_EV_FM_REP_RANGE,          /* rep distance >= vld_rge skipped */
+    ORC_EV_FM_REP_GOOD_LEN,       /* a rep match >= good_len ends the search */
+    ORC_EV_FM_REP_WRAPPED,        /* rep compare position on the far side of the window's wrap */
+    ORC_EV_FM_CLIMIT_WND,         /* climit set by the window's end (any table) */
+    ORC_EV_FM_HT2_WPOS_EQ_DIST,   /* HT2's strict compare: wpos == dist names wnd_size, not 0 */
+    ORC_EV_FM_KBOUND_HT23,        /* a short match rejected by kBound: HT2 / HT3 */
+    ORC_EV_FM_KBOUND_BT_HEAD,     /* ... the head candidate beyond the tree range */
+    ORC_EV_FM_KBOUND_BT,          /* ... in the descent */
+    ORC_EV_FM_KBOUND_HT6,         /* ... in the bucket */
+    ORC_EV_FM_BT_HEAD_BEYOND,     /* head candidate with bt_size <= dist < vld_rge compared */
+    ORC_EV_FM_BT_CYC,             /* descent ended by cyc >= bt_cyc */
+    ORC_EV_FM_BT_GOOD_LEN_SPLICE,
+    ORC_EV_FM_CAND_OVERFLOW,      /* cnt + 2 < MF_CAND_LIMIT false: the slot is overwritten */
+    /* MatchFinder::FindMatchWithPrice */
+    ORC_EV_FMP_KBOUND_ZERO,       /* a length's entry zeroed by kBound */
+    /* lazy parser: the preference predicate (FindMatch's candidate choice and the lazy step), by deciding clause */
+    ORC_EV_LAZY_CLAUSE1, ORC_EV_LAZY_CLAUSE2, ORC_EV_LAZY_CLAUSE3, ORC_EV_LAZY_CLAUSE4, ORC_EV_LAZY_CLAUSE5,
+    ORC_EV_LAZY_SECOND_TWICE,     /* the later match preferred at two positions running */
+    /* advanced parser */
+    ORC_EV_AP_LITERAL_NO_WINDOW,  /* no candidate: a literal without opening a window */
+    ORC_EV_AP_EXIT_LITERAL,
+    ORC_EV_AP_EXIT_GOOD_LEN,
+    ORC_EV_AP_EXIT_APLIMIT_LEN,   /* a match that reaches aplimit */
+    ORC_EV_AP_LIMIT_TAIL,         /* aplimit < AP_LIMIT: the sub-block's tail */
+    ORC_EV_AP_REP0LEN1_CODED,     /* the back trace codes a rep0len1 */
+    ORC_EV_AP_CUR_EQ_LIMIT,       /* apcur == aplimit (argued dead in orc_encoder.c) */
+    ORC_EV_AP_FIRST_REP0LEN1,     /* a first node whose last candidate is rep0len1 (argued dead in orc_encoder.c) */
+    /* LZ::EncodeNormal */
+    ORC_EV_LZ_WND_WRAP,
+    ORC_EV_COUNT
+};
+void orc_census_attach(CSCEncHandle h, uint64_t *counts);
+const char *orc_census_name(int ev);
+
+/* ---- an ISeqOutStream that collects in C (zalloc.c), for streams of so many Write calls that a Python callback is too slow ---- */
+ISeqOutStream *orc_sink_new(void);
+const uint8_t *orc_sink_data(const ISeqOutStream *s, size_t *size);
+void orc_sink_free(ISeqOutStream *s);
+
 /* ---- stream synthesizer (orc_synth.c): a script of packets -> a stream body, through the oracle's coder and model ---- */
 enum {
     ORC_OP_BLOCK = 1, ORC_OP_LIT, ORC_OP_MATCH, ORC_OP_REP, ORC_OP_REP0LEN1, ORC_OP_END_RUN, ORC_OP_RESTART,

@@ -103,7 +103,13 @@ typedef struct OrcEnc {
 
     /* ---- walk trace (orc_trace_*; NULL unless a test attached one) ---- */
     struct OrcTrace *trace;
+
+    /* ---- census (orc_census_attach; NULL unless a test attached one): ORC_EV_COUNT counters ---- */
+    uint64_t *census;
 } OrcEnc;
+
+/* count one event of the census (orc_api.h, enum OrcEvent) */
+#define ORC_EV(e, ev) do { if (__builtin_expect((e)->census != NULL, 0)) (e)->census[ev]++; } while (0)
 
 ORC_INT int write_block(OrcEnc *e, uint8_t *buf, uint32_t size, int rc1bc0);
 ORC_INT void coder_reset_state(OrcEnc *e);

@@ -17,6 +17,7 @@
  *   orc_analyze_block .. orc_tables   single stages for intermediate goldens
  *   orc_trace_*                    what enc_compress (the chunk walk) and mf_test_find decided during an encode:
  *                                  rows per block, per candidate, per run; off unless a trace is attached to the handle
+ *   orc_census_*                   how often the encode took each named rare branch (enum OrcEvent): ORC_EV(...) where the branch is
  */
 #include <math.h>
 #include <setjmp.h>
@@ -64,9 +65,18 @@ ORC_INT void rc_shift_low(OrcEnc *e)
 {
     if ((uint32_t)e->rc_low < 0xFF000000u || (int32_t)(e->rc_low >> 32) != 0) {
         uint8_t temp = e->rc_cache;
+        if (e->census && e->rc_cachesize >= 2) {     /* :92 taken with FF bytes pending behind the cache byte */
+            if ((int32_t)(e->rc_low >> 32) == 0) ORC_EV(e, ORC_EV_RC_FF_RUN2);
+            else {
+                ORC_EV(e, ORC_EV_RC_CARRY_CACHE2);
+                if (e->rc_cachesize >= 3) ORC_EV(e, ORC_EV_RC_CARRY_CACHE3);
+            }
+        }
         do {
             e->rc_buf[e->rc_size++] = (uint8_t)(temp + (uint8_t)(e->rc_low >> 32));
-            if (e->rc_size == e->bsize) {
+            if (e->rc_size == e->bsize) {        /* :97-103 */
+                ORC_EV(e, ORC_EV_RC_SEAM);
+                if (e->rc_cachesize > 1) ORC_EV(e, ORC_EV_RC_SEAM_MID);      /* the loop (:94-106) has bytes of this emission left */
                 e->outsize += e->rc_size;
                 if (write_block(e, e->rc_buf, e->bsize, 1) != (int)e->bsize)
                     longjmp(e->on_error, -WRITE_ERROR);
@@ -84,6 +94,7 @@ ORC_INT void rc_shift_low(OrcEnc *e)
 static void bc_check_bound(OrcEnc *e)
 {
     if (e->bc_size == e->bsize) {
+        ORC_EV(e, ORC_EV_BC_SEAM);
         e->outsize += e->bc_size;
         if (write_block(e, e->bc_buf, e->bsize, 0) != (int)e->bsize)
             longjmp(e->on_error, -WRITE_ERROR);
@@ -115,12 +126,19 @@ ORC_INT void enc_direct(OrcEnc *e, uint32_t v, uint32_t l)
 ORC_INT void coder_flush(OrcEnc *e)
 {
     for (int i = 0; i < 5; i++) rc_shift_low(e);
+    if (e->census) {        /* :46-47 rc_size_++ over a byte nobody stored */
+        ORC_EV(e, ORC_EV_FLUSH);
+        if (e->rc_buf[e->rc_size] != 0) ORC_EV(e, ORC_EV_FLUSH_STALE_NZ);
+        if (e->rc_size + 1 == e->bsize) ORC_EV(e, ORC_EV_FLUSH_BSIZE_M1);     /* WriteBlock (csc_memio.cpp:88-95) then takes it for a full block */
+        if (e->rc_size == 0) ORC_EV(e, ORC_EV_FLUSH_AFTER_SEAM);
+    }
     e->rc_size++;
     for (int i = 0; i < 2; i++) {
         if (i == 1) e->bc_buf[e->bc_size++] = 0;
         else e->bc_buf[e->bc_size++] = (e->bc_curval << (8 - e->bc_curbits)) & 0xFF;
         bc_check_bound(e);
     }
+    if (e->bc_size == 0) ORC_EV(e, ORC_EV_FLUSH_BC_EMPTY);      /* :55-56 wrapped it: WriteBCData(bc_buf_, 0) at :61 */
     e->outsize += e->rc_size + e->bc_size;
     if (write_block(e, e->rc_buf, e->rc_size, 1) != (int)e->rc_size
         || write_block(e, e->bc_buf, e->bc_size, 0) != (int)e->bc_size)
@@ -199,6 +217,7 @@ static void encode_matchlen_1(OrcEnc *e, uint32_t len)
 ORC_INT void encode_matchlen_2(OrcEnc *e, uint32_t len)
 {
     if (len >= 143) {
+        ORC_EV(e, len >= 286 ? ORC_EV_LEN_CHAIN2 : ORC_EV_LEN_CHAIN1);   /* :149-156, the while of :152 entered or not */
         encode_matchlen_1(e, 143);
         len -= 143;
         while (len >= 143) { len -= 143; enc_bit(e, 0, &e->p_longlen); }
@@ -267,6 +286,7 @@ ORC_INT void encode_rep_match(OrcEnc *e, uint32_t rep_idx, uint32_t match_len)
 /* Model::len_price_rebuild, csc_model.cpp:234-270 */
 static void len_price_rebuild(OrcEnc *e)
 {
+    ORC_EV(e, ORC_EV_LEN_PRICE_REBUILD);
     for (int i = 0; i < 32; i++) {
         uint32_t ret = 0, len = (uint32_t)i, c;
         const uint32_t *p;
@@ -330,6 +350,7 @@ static uint32_t dist_slot(uint32_t dist)
 /* Model::EncodeMatch, csc_model.cpp:301-366 */
 ORC_INT void encode_match(OrcEnc *e, uint32_t dist, uint32_t len)
 {
+    uint64_t seams_rc = e->census ? e->census[ORC_EV_RC_SEAM] : 0, seams_bc = e->census ? e->census[ORC_EV_BC_SEAM] : 0;
     enc_bit(e, 1, &e->p_state[e->state * 3 + 0]);
     enc_bit(e, 1, &e->p_state[e->state * 3 + 1]);
     encode_matchlen_2(e, len);
@@ -352,6 +373,8 @@ ORC_INT void encode_match(OrcEnc *e, uint32_t dist, uint32_t len)
         do { enc_bit(e, (c >> 3) & 1, &p[c >> 4]); c <<= 1; } while (c < (1u << 8));
     }
     e->state = (e->state * 4 + 1) & 0x3F;
+    /* the one packet that feeds both coders (EncodeDirect at :352-356 between its EncodeBits) */
+    if (e->census && e->census[ORC_EV_RC_SEAM] != seams_rc && e->census[ORC_EV_BC_SEAM] != seams_bc) ORC_EV(e, ORC_EV_RC_BC_SEAM_PACKET);
 }
 
 /* Model::GetMatchDistPrice, csc_model.cpp:368-387 */
@@ -508,7 +531,7 @@ static void mf_slide_pos(OrcEnc *e, uint32_t wnd_pos, uint32_t len, uint32_t lim
         e->ht2[hash2(e->wnd + wpos)] = e->pos;
         e->ht3[hash3(e->wnd + wpos)] = e->pos;
 
-        if (i + 128 < len) { i += 4; e->pos += 4; e->bt_pos += 4; continue; }
+        if (i + 128 < len) { ORC_EV(e, ORC_EV_SP_SKIP); /* :145 */ i += 4; e->pos += 4; e->bt_pos += 4; continue; }
 
         if (e->ht_width) {
             h6 = hash6(e->wnd + wpos, e->ht_bits);
@@ -516,22 +539,26 @@ static void mf_slide_pos(OrcEnc *e, uint32_t wnd_pos, uint32_t len, uint32_t lim
             if (h6 != lasth6) {
                 uint32_t cands = UMIN(e->ht_width, e->ht_cyc);
                 for (uint32_t j = cands - 1; j > 0; j--) b[j] = b[j - 1];
-            }
+            } else ORC_EV(e, ORC_EV_SP_NOSHIFT);      /* :150 false */
             b[0] = e->pos;
             lasth6 = h6;
         }
 
         if (!e->bt_head) { e->pos++; i++; continue; }
         uint32_t hbt = hash6(e->wnd + wpos, e->bt_bits);
-        if (e->bt_pos >= e->bt_size) e->bt_pos -= e->bt_size;
+        if (e->bt_pos >= e->bt_size) { ORC_EV(e, ORC_EV_SP_BT_POS_WRAP); e->bt_pos -= e->bt_size; }   /* :161 */
         uint32_t dist = e->pos - e->bt_head[hbt];
         uint32_t *l = &e->bt_nodes[(size_t)e->bt_pos * 2], *r = &e->bt_nodes[(size_t)e->bt_pos * 2 + 1];
         uint32_t lenl = 0, lenr = 0;
         for (uint32_t cyc = 0;; cyc++) {
-            if (cyc >= e->bt_cyc || dist >= e->bt_size || dist >= e->vld_rge) { *l = *r = 0; break; }
+            if (cyc >= e->bt_cyc || dist >= e->bt_size || dist >= e->vld_rge) {
+                if (cyc >= e->bt_cyc) ORC_EV(e, ORC_EV_SP_BT_CYC);
+                *l = *r = 0; break;
+            }
             uint32_t cmp_pos = wrap_back(e, wpos, dist);
             uint32_t clen = UMIN(lenl, lenr);
             uint32_t climit = UMIN(limit - i, e->wnd_size - cmp_pos);
+            if (e->wnd_size - cmp_pos < limit - i) ORC_EV(e, ORC_EV_SP_CLIMIT_WND);
             if (clen >= climit) { *l = *r = 0; break; }
             uint32_t bt_npos = e->bt_pos >= dist ? e->bt_pos - dist : e->bt_pos + e->bt_size - dist;
             uint32_t *tlast = &e->bt_nodes[(size_t)bt_npos * 2];
@@ -540,7 +567,7 @@ static void mf_slide_pos(OrcEnc *e, uint32_t wnd_pos, uint32_t len, uint32_t lim
                 uint32_t climit2 = UMIN(e->good_len, climit);
                 clen++;
                 while (clen < climit2 && pcur[clen] == pmatch[clen]) clen++;
-                if (clen >= e->good_len) { *l = tlast[0]; *r = tlast[1]; break; }
+                if (clen >= e->good_len) { ORC_EV(e, ORC_EV_SP_GOOD_LEN_SPLICE); *l = tlast[0]; *r = tlast[1]; break; }
                 else if (clen >= climit2) { *l = *r = 0; break; }
             }
             if (pmatch[clen] < pcur[clen]) {
@@ -607,13 +634,16 @@ static uint32_t mf_find_match(OrcEnc *e, MFUnit *ret, const uint32_t *rep_dist, 
     if (e->ht_width) h6 = hash6(pcur, e->ht_bits);
     if (e->bt_head) hbt = hash6(pcur, e->bt_bits);
 
-#define PUSH_CAND(L, D) do { ret[cnt].len = (L); ret[cnt].dist = (D); if (cnt + 2 < MF_CAND_LIMIT) cnt++; } while (0)
+#define PUSH_CAND(L, D) do { ret[cnt].len = (L); ret[cnt].dist = (D); if (cnt + 2 < MF_CAND_LIMIT) cnt++; else ORC_EV(e, ORC_EV_FM_CAND_OVERFLOW); } while (0)
+#define CLIMIT_EV(cmp_pos) do { if (e->wnd_size - (cmp_pos) < limit) ORC_EV(e, ORC_EV_FM_CLIMIT_WND); } while (0)
 
     /* rep distances, :266-299 */
     for (uint32_t i = 0; i < 4; i++) {
-        if (rep_dist[i] >= e->vld_rge) continue;
+        if (rep_dist[i] >= e->vld_rge) { ORC_EV(e, ORC_EV_FM_REP_RANGE); continue; }
         uint32_t cmp_pos = wrap_back(e, wpos, rep_dist[i]);
         uint32_t climit = UMIN(limit, e->wnd_size - cmp_pos);
+        if (wpos < rep_dist[i]) ORC_EV(e, ORC_EV_FM_REP_WRAPPED);
+        CLIMIT_EV(cmp_pos);
         const uint8_t *pmatch = e->wnd + cmp_pos;
         if (minlen >= climit || pmatch[minlen] != pcur[minlen]) continue;
         uint32_t match_len = prefix_len(pcur, pmatch, climit);
@@ -621,7 +651,7 @@ static uint32_t mf_find_match(OrcEnc *e, MFUnit *ret, const uint32_t *rep_dist, 
         if (match_len > minlen) {
             minlen = match_len;
             PUSH_CAND(match_len, 1 + i);
-            if (match_len >= e->good_len) { dist = 0xFFFFFFFFu; break; }
+            if (match_len >= e->good_len) { ORC_EV(e, ORC_EV_FM_REP_GOOD_LEN); dist = 0xFFFFFFFFu; break; }
         }
     }
 
@@ -635,12 +665,14 @@ static uint32_t mf_find_match(OrcEnc *e, MFUnit *ret, const uint32_t *rep_dist, 
             uint32_t cmp_pos = t == 0 ? (wpos > dist ? wpos - dist : wpos + e->wnd_size - dist)
                                       : wrap_back(e, wpos, dist);
             uint32_t climit = UMIN(limit, e->wnd_size - cmp_pos);
+            if (t == 0 && wpos == dist) ORC_EV(e, ORC_EV_FM_HT2_WPOS_EQ_DIST);    /* :306, `>` where the other tables have `>=` */
+            CLIMIT_EV(cmp_pos);
             const uint8_t *pmatch = e->wnd + cmp_pos;
             if (minlen >= climit || pmatch[minlen] != pcur[minlen]) continue;
             uint32_t match_len = prefix_len(pcur, pmatch, climit);
             if (match_len > minlen) {
                 minlen = match_len;
-                if (match_len <= 6 && dist >= kBound[match_len]) continue;
+                if (match_len <= 6 && dist >= kBound[match_len]) { ORC_EV(e, ORC_EV_FM_KBOUND_HT23); continue; }
                 PUSH_CAND(match_len, 4 + dist);
                 if (match_len >= e->good_len) dist = 0xFFFFFFFFu;
             }
@@ -656,6 +688,8 @@ static uint32_t mf_find_match(OrcEnc *e, MFUnit *ret, const uint32_t *rep_dist, 
         if (dist >= e->bt_size && dist < e->vld_rge) {
             uint32_t cmp_pos = wrap_back(e, wpos, dist);
             uint32_t climit = UMIN(limit, e->wnd_size - cmp_pos);
+            ORC_EV(e, ORC_EV_FM_BT_HEAD_BEYOND);
+            CLIMIT_EV(cmp_pos);
             const uint8_t *pmatch = e->wnd + cmp_pos;
             if (!(minlen >= climit || pmatch[minlen] != pcur[minlen])) {
                 uint32_t match_len = prefix_len(pcur, pmatch, climit);
@@ -664,17 +698,21 @@ static uint32_t mf_find_match(OrcEnc *e, MFUnit *ret, const uint32_t *rep_dist, 
                     if (!(match_len <= 6 && dist >= kBound[match_len])) {
                         PUSH_CAND(match_len, 4 + dist);
                         if (match_len >= e->good_len) dist = 0xFFFFFFFFu;
-                    }
+                    } else ORC_EV(e, ORC_EV_FM_KBOUND_BT_HEAD);
                 }
             }
         }
         /* :404-451 descend + insert */
         uint32_t lenl = 0, lenr = 0;
         for (uint32_t cyc = 0;; cyc++) {
-            if (cyc >= e->bt_cyc || dist >= e->bt_size || dist >= e->vld_rge) { *l = *r = 0; break; }
+            if (cyc >= e->bt_cyc || dist >= e->bt_size || dist >= e->vld_rge) {
+                if (cyc >= e->bt_cyc) ORC_EV(e, ORC_EV_FM_BT_CYC);
+                *l = *r = 0; break;
+            }
             uint32_t cmp_pos = wrap_back(e, wpos, dist);
             uint32_t clen = UMIN(lenl, lenr);
             uint32_t climit = UMIN(limit, e->wnd_size - cmp_pos);
+            CLIMIT_EV(cmp_pos);
             if (clen >= climit) { *l = *r = 0; break; }
             uint32_t bt_npos = e->bt_pos >= dist ? e->bt_pos - dist : e->bt_pos + e->bt_size - dist;
             uint32_t *tlast = &e->bt_nodes[(size_t)bt_npos * 2];
@@ -685,8 +723,9 @@ static uint32_t mf_find_match(OrcEnc *e, MFUnit *ret, const uint32_t *rep_dist, 
                 if (clen > minlen) {
                     minlen = clen;
                     if (clen > 6 || dist < kBound[clen]) PUSH_CAND(clen, 4 + dist);
+                    else ORC_EV(e, ORC_EV_FM_KBOUND_BT);
                 }
-                if (clen >= e->good_len) { *l = tlast[0]; *r = tlast[1]; dist = 0xFFFFFFFFu; break; }
+                if (clen >= e->good_len) { ORC_EV(e, ORC_EV_FM_BT_GOOD_LEN_SPLICE); *l = tlast[0]; *r = tlast[1]; dist = 0xFFFFFFFFu; break; }
                 else if (clen >= climit) { *l = *r = 0; break; }
             }
             if (pmatch[clen] < pcur[clen]) {
@@ -713,11 +752,12 @@ static uint32_t mf_find_match(OrcEnc *e, MFUnit *ret, const uint32_t *rep_dist, 
         uint32_t cmp_pos = wrap_back(e, wpos, dist);
         uint32_t climit = UMIN(limit, e->wnd_size - cmp_pos);
         const uint8_t *pmatch = e->wnd + cmp_pos;
+        CLIMIT_EV(cmp_pos);
         if (minlen >= climit || pmatch[minlen] != pcur[minlen]) continue;
         uint32_t match_len = prefix_len(pcur, pmatch, climit);
         if (match_len > minlen) {
             minlen = match_len;
-            if (match_len <= 6 && dist >= kBound[match_len]) continue;
+            if (match_len <= 6 && dist >= kBound[match_len]) { ORC_EV(e, ORC_EV_FM_KBOUND_HT6); continue; }
             PUSH_CAND(match_len, 4 + dist);
             if (match_len >= e->good_len) { dist = 0xFFFFFFFFu; break; }
         }
@@ -727,14 +767,23 @@ static uint32_t mf_find_match(OrcEnc *e, MFUnit *ret, const uint32_t *rep_dist, 
         b[0] = e->pos;
     }
 #undef PUSH_CAND
+#undef CLIMIT_EV
     if (++e->pos >= 0xFFFFFFF0u) mf_normalize(e);
     return cnt;
 }
 
 /* the lazy parser's preference predicate, csc_mf.cpp:508-516 and :570-582 */
-static int second_better(MFUnit u1, MFUnit u2)
+static int second_better(OrcEnc *e, MFUnit u1, MFUnit u2)
 {
     static const uint32_t cof[] = {0, 4, 8, 12};
+    if (e->census && u2.len > 1) {      /* which clause of the || chain decides (the first one true) */
+        if (u2.len > u1.len + 3) ORC_EV(e, ORC_EV_LAZY_CLAUSE1);
+        else if (u2.len > u1.len && u2.dist <= 4) ORC_EV(e, ORC_EV_LAZY_CLAUSE2);
+        else if (u2.len + 2 > u1.len && u2.dist <= 4 && u1.dist > 4) ORC_EV(e, ORC_EV_LAZY_CLAUSE3);
+        else if (u2.len >= u1.len && (u2.dist >> cof[u2.len - u1.len]) <= u1.dist) ORC_EV(e, ORC_EV_LAZY_CLAUSE4);
+        else if (u2.len < u1.len && u2.len + 2 >= u1.len && u1.dist > 4
+                 && (u1.dist >> cof[u1.len - u2.len]) > u2.dist) ORC_EV(e, ORC_EV_LAZY_CLAUSE5);
+    }
     return u2.len > 1 && (
         (u2.len > u1.len + 3)
         || (u2.len > u1.len && u2.dist <= 4)
@@ -752,7 +801,7 @@ static MFUnit mf_find_best(OrcEnc *e, const uint32_t *rep_dist, uint32_t wnd_pos
     uint32_t best = 0;
     for (uint32_t i = 1; i <= n; i++) {
         if (!best) { best = i; continue; }
-        if (second_better(e->mfcand[best], e->mfcand[i])) best = i;
+        if (second_better(e, e->mfcand[best], e->mfcand[i])) best = i;
     }
     return e->mfcand[best];
 }
@@ -785,6 +834,27 @@ void orc_trace_free(struct OrcTrace *t)
     if (!t) return;
     for (int k = 0; k < 3; k++) free(t->rows[k]);
     free(t);
+}
+
+/* ---- census (orc_api.h): the counters are the caller's; the events are counted where their branches are ---- */
+void orc_census_attach(CSCEncHandle h, uint64_t *counts) { ((OrcEnc *)h)->census = counts; }
+const char *orc_census_name(int ev)
+{
+    static const char *const names[ORC_EV_COUNT] = {
+        "rc_carry_cache2", "rc_carry_cache3", "rc_ff_run2", "rc_seam", "rc_seam_mid", "bc_seam", "rc_bc_seam_packet",
+        "flush", "flush_stale_nz", "flush_bsize_m1", "flush_after_seam", "flush_bc_empty",
+        "len_chain1", "len_chain2", "len_price_rebuild",
+        "sp_skip", "sp_noshift", "sp_bt_pos_wrap", "sp_bt_cyc", "sp_good_len_splice", "sp_climit_wnd",
+        "fm_rep_range", "fm_rep_good_len", "fm_rep_wrapped", "fm_climit_wnd", "fm_ht2_wpos_eq_dist",
+        "fm_kbound_ht23", "fm_kbound_bt_head", "fm_kbound_bt", "fm_kbound_ht6",
+        "fm_bt_head_beyond", "fm_bt_cyc", "fm_bt_good_len_splice", "fm_cand_overflow",
+        "fmp_kbound_zero",
+        "lazy_clause1", "lazy_clause2", "lazy_clause3", "lazy_clause4", "lazy_clause5", "lazy_second_twice",
+        "ap_literal_no_window", "ap_exit_literal", "ap_exit_good_len", "ap_exit_aplimit_len", "ap_limit_tail",
+        "ap_rep0len1_coded", "ap_cur_eq_limit", "ap_first_rep0len1",
+        "lz_wnd_wrap",
+    };
+    return ev >= 0 && ev < ORC_EV_COUNT ? names[ev] : NULL;
 }
 static void trace_cand(OrcEnc *e, uint32_t table, uint32_t dist, uint32_t wpos, uint32_t limit, const uint8_t *src, int hit)
 {
@@ -855,7 +925,7 @@ static void mf_find_priced(OrcEnc *e, uint32_t state, MFUnit *ret, const uint32_
         }
         while (lpos < e->mfcand[i].len) {
             lpos++;
-            if (lpos <= 6 && rdist >= kBound[lpos]) { ret[lpos].dist = 0; continue; }
+            if (lpos <= 6 && rdist >= kBound[lpos]) { ORC_EV(e, ORC_EV_FMP_KBOUND_ZERO); ret[lpos].dist = 0; continue; }
             ret[lpos].dist = e->mfcand[i].dist;
             ret[lpos].len = distprice + match_len_price(e, lpos - 2);
         }
@@ -900,7 +970,8 @@ static void lz_compress_normal(OrcEnc *e, uint32_t size, int lazy)
             continue;
         }
         u2 = mf_find_best(e, e->rep_dist, e->wnd_curpos + 1, size - i - 1);
-        if (second_better(u1, u2)) {
+        if (second_better(e, u1, u2)) {
+            if (got_u1) ORC_EV(e, ORC_EV_LAZY_SECOND_TWICE);      /* :181-187 taken again for the match it just preferred */
             encode_literal(e, e->wnd[e->wnd_curpos]);
             mf_slide_pos(e, e->wnd_curpos, 1, size - i - 1);
             i++; e->wnd_curpos++;
@@ -929,7 +1000,7 @@ static void lz_ap_backward(OrcEnc *e, int end)
         if (ap[next].dist == 0) {
             encode_literal(e, ap[i].lit);
         } else if (ap[next].dist <= 4) {
-            if (next - i == 1 && ap[next].dist == 1) encode_rep0len1(e);
+            if (next - i == 1 && ap[next].dist == 1) { ORC_EV(e, ORC_EV_AP_REP0LEN1_CODED); encode_rep0len1(e); }
             else encode_rep_match(e, ap[next].dist - 1, next - i - 2);
             e->ctx = ap[next - 1].lit;
         } else {
@@ -950,6 +1021,7 @@ static void lz_compress_advanced(OrcEnc *e, uint32_t size)
     for (uint32_t i = 0; i < size;) {
         mf_find_priced(e, e->state, appt, e->rep_dist, e->wnd_curpos, size - i);
         if (appt[0].dist == 0) {
+            ORC_EV(e, ORC_EV_AP_LITERAL_NO_WINDOW);      /* :213-219 */
             encode_literal(e, e->wnd[e->wnd_curpos]);
             mf_slide_pos(e, e->wnd_curpos, 1, size - i);
             i++; e->wnd_curpos++;
@@ -960,6 +1032,12 @@ static void lz_compress_advanced(OrcEnc *e, uint32_t size)
         memcpy(ap[0].rep_dist, e->rep_dist, sizeof(e->rep_dist));
         ap[0].state = e->state;
         uint32_t aplimit = UMIN((uint32_t)AP_LIMIT, size - i);
+        if (aplimit < AP_LIMIT) ORC_EV(e, ORC_EV_AP_LIMIT_TAIL);      /* :227 */
+        /* Dead in the reference: appt[0] is find_match's LAST candidate (csc_mf.cpp:590-594), and rep0len1 (1, 1) is pushed only when
+         * the rep0 compare found match_len >= 1 past the gate `pmatch[minlen] == pcur[minlen]` with minlen == 1 < climit
+         * (csc_mf.cpp:266-287), i.e. bytes 0 and 1 both equal: match_len >= 2 > minlen, so the rep0 match itself is pushed right
+         * behind it.  Every later push only adds candidates.  So (1, 1) is never the last one. */
+        if (appt[0].len == 1 && appt[0].dist == 1) ORC_EV(e, ORC_EV_AP_FIRST_REP0LEN1);
         for (;;) {
             ap[apcur].lit = e->wnd[e->wnd_curpos];
             if (apcur) { /* fix cur state, :231-268 */
@@ -989,12 +1067,18 @@ static void lz_compress_advanced(OrcEnc *e, uint32_t size)
                 if (apcur < aplimit)
                     mf_find_priced(e, ap[apcur].state, appt, ap[apcur].rep_dist, e->wnd_curpos, size - i - apcur);
             }
+            /* Dead in the reference: apend <= aplimit always holds here -- a node is opened at apcur + len only when len + apcur <
+             * aplimit, every other case leaves through :290-299 -- so at apcur == aplimit - 1 either appt[0].len == 1, and then
+             * apcur + 1 == apend and :277-285 leaves, or appt[0].len > 1, and then len + apcur >= aplimit and :290-299 leaves
+             * (appt[0].len >= 1 always: mfcand[0] is {1, 0}).  apcur never gets to aplimit. */
             if (apcur == aplimit) { /* :271-275 */
+                ORC_EV(e, ORC_EV_AP_CUR_EQ_LIMIT);
                 lz_ap_backward(e, (int)apcur);
                 i += apcur;
                 break;
             }
             if (appt[0].len == 1 && apcur + 1 == apend) { /* :277-285 */
+                ORC_EV(e, ORC_EV_AP_EXIT_LITERAL);
                 lz_ap_backward(e, (int)apcur);
                 encode_literal(e, ap[apcur].lit);
                 i += apcur;
@@ -1005,6 +1089,7 @@ static void lz_compress_advanced(OrcEnc *e, uint32_t size)
             }
             if (apcur + 1 >= apend) ap[apend++].price = 0xFFFFFFFFu;
             if (appt[0].len >= e->lz_good_len || (appt[0].len > 1 && appt[0].len + apcur >= aplimit)) { /* :290-299 */
+                ORC_EV(e, appt[0].len >= e->lz_good_len ? ORC_EV_AP_EXIT_GOOD_LEN : ORC_EV_AP_EXIT_APLIMIT_LEN);
                 lz_ap_backward(e, (int)apcur);
                 i += apcur;
                 lz_encode_nonlit(e, appt[0]);
@@ -1066,7 +1151,7 @@ static void lz_encode_normal(OrcEnc *e, const uint8_t *src, uint32_t size, uint3
         } else {
             exit(0); /* the reference prints "Error!" and exits, :86-88 */
         }
-        if (e->wnd_curpos >= e->wnd_size) e->wnd_curpos = 0;
+        if (e->wnd_curpos >= e->wnd_size) { ORC_EV(e, ORC_EV_LZ_WND_WRAP); e->wnd_curpos = 0; }   /* :91-92 */
         i += cur;
     }
     if (lz_mode != 5) encode_match(e, 64, 0);

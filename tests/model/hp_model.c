@@ -232,7 +232,7 @@ static MFUnit hpm_find_best(OrcEnc *e, const uint32_t *rep_dist, uint32_t p)
     uint32_t best = 0;
     for (uint32_t i = 1; i <= n; i++) {
         if (!best) { best = i; continue; }
-        if (second_better(e->mfcand[best], e->mfcand[i])) best = i;
+        if (second_better(e, e->mfcand[best], e->mfcand[i])) best = i;
     }
     return e->mfcand[best];
 }
@@ -255,7 +255,7 @@ static void hpm_norm_pipe(OrcEnc *e, uint32_t size, int lazy)
             continue;
         }
         u2 = hpm_find_best(e, e->rep_dist, i + 1);
-        if (second_better(u1, u2)) {
+        if (second_better(e, u1, u2)) {
             encode_literal(e, e->wnd[e->wnd_curpos]);
             i++; e->wnd_curpos++;
             u1 = u2;
